@@ -365,6 +365,35 @@ def dist(ms):
             "steps_over_2x_median": [i for i, x in enumerate(ms) if x > 2 * med][:16], "n": len(a)}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_ROWS = 1 << 16
+
+
+def table_sample(table, seed):
+    """A fixed, seeded sample of the rows of a device table (the whole table when it is small): what --dump-outputs keeps of an output too large to write"""
+    a = table.read()
+    if len(a) <= DUMP_SAMPLE_ROWS:
+        return a
+    return a[np.sort(np.random.default_rng(seed).choice(len(a), DUMP_SAMPLE_ROWS, replace=False))]
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: the arrays the timed path returned in its last step as DIR/<name>.npy in float64. Field elements and proof words are uint64:
+    they are written as their 32-bit halves (little-endian order, last axis doubled), which float64 holds exactly."""
+    conv = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        if a.dtype == np.uint64:
+            a = a.view(np.uint32)
+        conv[name] = a.astype(np.float64)
+    total = sum(a.nbytes for a in conv.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in conv.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def prep_prove_leg(snark, inst, tape, step_tape, words, calls=6, oracle=None, used=None):
     """SpartanSNARK::prep_prove as a phase of its own, the protocol of benches/sha256_spartan.rs:206-222: setup outside, a FRESH prep_prove inside the timed
     routine, its output dropped outside (Criterion's iter_batched). min / median over `calls` calls of the C entry point, the driver's own phases
@@ -439,6 +468,7 @@ def main():
     ap.add_argument("--no-sharded", action="store_true", help="skip the config-4 sharded legs (profiling runs)")
     ap.add_argument("--extras-timeout", type=float, default=600.0, help="seconds the sharded extra legs of the default workload may take before the line is printed without them")
     ap.add_argument("--concurrent", type=int, default=8, help="extra (untimed) leg: this many independent proofs in flight on the one GPU; 0 = skip")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the timed path returned in its last step (rank 0) as DIR/<name>.npy, float64")
     args = ap.parse_args()
 
     from spartan2_amd import dist as spd
@@ -489,7 +519,7 @@ def main():
         c3_step_ms, c3_slowest = [], None
         for _ in range(args.steps):
             ts = time.perf_counter()
-            words, _, ph = nn.prove(step_tape)
+            words, used_s, ph = nn.prove(step_tape)
             c3_step_ms.append((time.perf_counter() - ts) * 1e3)
             if c3_step_ms[-1] >= max(c3_step_ms):
                 c3_slowest = dict(ph)
@@ -497,6 +527,8 @@ def main():
                 acc[k_] = acc.get(k_, 0.0) + v_
         barrier()
         elapsed = group.max_over_ranks(time.perf_counter() - t0)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, {"proof_words": words, "tape_blocks_used": np.array([used_s], dtype=np.uint64)})
         ncons = circs[0].num_cons * nsteps + core.num_cons
         # the reference-order driver (one thread, statement order of src/neutronnova_zk.rs:1609-2093, PCS::prove as one sp_hyrax_prove) on a prep state of its
         # own: its first proof must be the default driver's first proof (every prove rerandomizes its prep state in place), then the same number of steps
@@ -633,6 +665,9 @@ def main():
         ctx.synchronize()
         barrier()
         elapsed = group.max_over_ranks(time.perf_counter() - t0)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, {**{k_: v_ for k_, v_ in out.items() if isinstance(v_, np.ndarray)},
+                                             **{k_ + "_sample": table_sample(out[k_], 0xD0 + i) for i, k_ in enumerate(("A", "B", "C", "folded_W"))}})
         names = ("nifs_round0_small", "nifs_round0", "nifs_fold_prove", "nifs_prove_pairs", "nifs_fold", "nifs_cvals", "fold_tables")
         ks = {k_: ctx.kernel_stats(k_) for k_ in names}
         ctx.reset_stats(False)
@@ -702,11 +737,13 @@ def main():
         t0 = time.perf_counter()
         acc = {}
         for _ in range(args.steps):
-            words, _, ph = sn.prove(step_tape)
+            words, used_s, ph = sn.prove(step_tape)
             for k_, v_ in ph.items():
                 acc[k_] = acc.get(k_, 0.0) + v_
         barrier()
         elapsed = group.max_over_ranks(time.perf_counter() - t0)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, {"proof_words": words, "tape_blocks_used": np.array([used_s], dtype=np.uint64)})
         legs = None if args.no_sharded else sharded_legs(ctx, comm, group, 1, 2, False)
         unsharded = None
         if world == 1:
@@ -776,7 +813,7 @@ def main():
     step_ms = []  # each prove's own wall time around the call: shows an outlier the mean would hide
     for _ in range(args.steps):
         t_s = time.perf_counter()
-        words, _, phases = snark.prove(step_tape)
+        words, used_s, phases = snark.prove(step_tape)
         step_ms.append((time.perf_counter() - t_s) * 1e3)
         if step_ms[-1] >= max(step_ms):
             slowest = dict(phases)
@@ -785,6 +822,8 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     elapsed = group.max_over_ranks(elapsed)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"proof_words": words, "tape_blocks_used": np.array([used_s], dtype=np.uint64)})
     bind_ms, bind_launches, bind_bytes = ctx.kernel_stats("bind_stream_cubic")
     ctx.reset_stats(False)
     # the same loop with the transcript prefix's sponge state cached across proves (an API-level optimisation the reference does not make):
@@ -858,8 +897,7 @@ def main():
             # wait hook switching between them (ss_prove_multiplexed). What bounds it is stated with it.
             try:
                 r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "multiplex_bench.py"), "--sweep", "24x6", "--proofs", str(per), "--message-bytes",
-                                    str(args.message_bytes), "--device", str(local_rank), "--json"], capture_output=True, text=True, timeout=600,
-                                   env=dict(os.environ, GPU_MAX_HW_QUEUES="16"))
+                                    str(args.message_bytes), "--device", str(local_rank), "--json"], capture_output=True, text=True, timeout=600)
                 line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
                 if not line:
                     raise RuntimeError((r.stderr or r.stdout)[-400:])

@@ -1010,7 +1010,7 @@ static double now_us() { return std::chrono::duration<double, std::micro>(std::c
 // the resident tail takes a sum-check over from tables of 2^16 elements down (64 blocks: 256 pairs a block in its first step, HOST_SUM_MAX_BLOCKS
 // result slots; sweeps of 2^13 .. 2^16 measured within 5 us of each other, tools/tail_sweep.sh)
 static const size_t TAIL_MAX_LEN = [] {
-  const char* e = getenv("SPARTAN_TAIL_LOG2");  // A/B: table length from which the resident tail takes over (13 .. 16)
+  const char* e = getenv("SPARTAN_TAIL_LOG2");  // A/B: table length from which the resident tail takes over (2^10 .. 2^16)
   const int k = e ? atoi(e) : 16;  // 2^16 since the local regime (round 5): 0.8675 -> 0.8641 ms against 2^15 on one box, outer sum-check -5.6 us
   return (size_t)1 << (k < 10 ? 10 : (k > 16 ? 16 : k));
 }();

@@ -2,6 +2,7 @@
 through the C ABI vs the CPU oracle, bit-exact on canonical affine coordinates. Mirrors src/provider/msm.rs:878-934
 (naive vs msm, msm vs msm_small at nine bit widths)."""
 import ctypes
+import os
 
 import numpy as np
 import pytest
@@ -572,6 +573,11 @@ def test_commit_split_equals_commit_small_and_the_oracle(ctx, width):
         assert not k.commit_split_available()
         pytest.skip("SPARTAN_WALKERS=0: the split form is not offered")
     ncols = min(width, 16)
+    if os.environ.get("SPARTAN_HOST_T16", "1")[:1] == "0":  # no host copies of the window tables: the split form is refused, not mis-computed
+        assert not any(k.commit_split_available(n) for n in (1, ncols))
+        with pytest.raises(hip.SpartanHipError):
+            k.commit_split(np.arange(1, dtype=np.uint32), ol.random_field_array(rng, 1), None, np.arange(1, 2, dtype=np.uint32), ol.random_field_array(rng, 1))
+        pytest.skip("SPARTAN_HOST_T16=0: the split form is not offered")
     assert k.commit_split_available(ncols) and not k.commit_split_available(width + 1)
 
     def want(row, blind):

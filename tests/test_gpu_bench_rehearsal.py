@@ -1,4 +1,4 @@
-"""GPU: `python bench.py --gpus N` rehearsed on ONE GPU (SPARTAN_BENCH_REHEARSAL=1: every rank on device 0, gloo, the callback exchange): the whole
+"""GPU: `python bench.py --gpus N --full` rehearsed on ONE GPU (SPARTAN_BENCH_REHEARSAL=1: every rank on device 0, gloo, the callback exchange): the whole
 N > 1 control flow — self-launch, barriers, max-over-ranks timing, the sharded legs under their watchdogs, the sharded config-4 prove with its
 exchanges — runs and prints ONE well-formed line. The figures are not measurements (the ranks share the GPU); the line says so."""
 import json
@@ -16,8 +16,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_bench_rehearsal(workload, world):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["SPARTAN_BENCH_REHEARSAL"] = "1"
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--workload", workload, "--steps", "2", "--warmup", "1", "--concurrent", "0",
-           "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--workload", workload, "--steps", "2", "--warmup", "1", "--full", "--concurrent",
+           "0", "--no-cpu-baseline"]
     if workload == "c5":
         cmd += ["--instances", "8"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
@@ -39,7 +39,7 @@ def test_the_line_survives_a_process_that_dies_inside_a_sharded_leg():
     the legs finished before, the leg it died in marked."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["SPARTAN_BENCH_DIE_IN"] = "msm_general"
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--concurrent", "0", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--full", "--concurrent", "0", "--no-cpu-baseline"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode != 0
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

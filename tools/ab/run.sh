@@ -5,6 +5,6 @@ mkdir -p $out
 for rep in $(seq 1 $reps); do
   for v in "$@"; do
     cp tools/ab/$v/*.so spartan2_amd/lib/
-    python bench.py --steps $steps --warmup 5 --no-cpu-baseline --no-sharded --concurrent 0 > $out/$v.$rep.json 2> $out/$v.$rep.err
+    python bench.py --steps $steps --warmup 5 --full --no-cpu-baseline --no-sharded --concurrent 0 > $out/$v.$rep.json 2> $out/$v.$rep.err
   done
 done

@@ -5,6 +5,6 @@ mkdir -p $out
 for rep in $(seq 1 $reps); do
   for v in "$@"; do
     cp tools/ab/$v/*.so spartan2_amd/lib/
-    python bench.py --workload c3 --steps $steps --warmup 3 > $out/$v.$rep.json 2> $out/$v.$rep.err
+    python bench.py --workload c3 --steps $steps --warmup 3 --full > $out/$v.$rep.json 2> $out/$v.$rep.err
   done
 done

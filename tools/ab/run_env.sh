@@ -7,9 +7,9 @@ for rep in $(seq 1 $reps); do
   for spec in "$@"; do
     name=${spec%%=*}; assign=${spec#*=}
     if [ -n "$assign" ]; then
-      env "$assign" python bench.py --steps $steps --warmup 5 --no-cpu-baseline --no-sharded --concurrent 0 > $out/$name.$rep.json 2> $out/$name.$rep.err
+      env "$assign" python bench.py --steps $steps --warmup 5 --full --no-cpu-baseline --no-sharded --concurrent 0 > $out/$name.$rep.json 2> $out/$name.$rep.err
     else
-      python bench.py --steps $steps --warmup 5 --no-cpu-baseline --no-sharded --concurrent 0 > $out/$name.$rep.json 2> $out/$name.$rep.err
+      python bench.py --steps $steps --warmup 5 --full --no-cpu-baseline --no-sharded --concurrent 0 > $out/$name.$rep.json 2> $out/$name.$rep.err
     fi
   done
 done

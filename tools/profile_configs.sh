@@ -4,9 +4,9 @@
 RD=${1:-r06}
 R=$(pwd); O=$R/gpurun_out/profc_$RD; rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/c3 -o run -- python $R/bench.py --workload c3 --steps 10 --warmup 2 --no-cpu-baseline > $O/c3.log 2>&1
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/c4 -o run -- python $R/bench.py --workload c4 --steps 3 --warmup 1 --no-sharded --no-cpu-baseline > $O/c4.log 2>&1
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/c5 -o run -- python $R/bench.py --workload c5 --steps 2 --warmup 1 --no-cpu-baseline > $O/c5.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/c3 -o run -- python $R/bench.py --workload c3 --steps 10 --warmup 2 --full --no-cpu-baseline > $O/c3.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/c4 -o run -- python $R/bench.py --workload c4 --steps 3 --warmup 1 --full --no-sharded --no-cpu-baseline > $O/c4.log 2>&1
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/c5 -o run -- python $R/bench.py --workload c5 --steps 2 --warmup 1 --full --no-cpu-baseline > $O/c5.log 2>&1
 cd $R
 for c in c3 c4 c5; do
   f=$(find $O/$c -name "run_kernel_stats.csv" | head -1)

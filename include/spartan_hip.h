@@ -90,6 +90,30 @@ int sp_table_write_u64(sp_ctx* ctx, sp_table* t, size_t off, const uint64_t* val
 /* the same for a 0/1 witness packed 8 values a byte, value i = bit (i & 7) of bits[i >> 3] (the booleanised form of a SHA-256 / bit-decomposition witness:
  * 128 KiB for 2^20 values) */
 int sp_table_write_bits(sp_ctx* ctx, sp_table* t, size_t off, const uint8_t* bits, size_t cnt);
+/* ---- SHA-256 witness generation on the device --------------------------------------------------------------------------------------------------------
+ * For the SHA-256 benchmark circuits the witness is generated here instead of being synthesised by the frontend and uploaded: replaces, for these
+ * circuits, precommitted_witness (src/bellpepper/r1cs.rs:359-409) as driven by benches/sha256_spartan.rs:78-136 (Sha256Circuit) and
+ * benches/sha256_neutronnova.rs:49-183 (Sha256StepCircuit / CoreCircuit; the reference synthesises every step, src/neutronnova_zk.rs:1487-1518).
+ * The circuit's structure depends only on the message length, and every aux variable is one fixed bit of a word that a native SHA-256 compression
+ * computes on the way. A plan (spartan2_amd/frontend/sha256_witness_plan.hpp) holds, per aux variable in allocation order, a descriptor
+ * slot | bit << 11 | invert << 17 into the per-block trace of spartan2_amd/frontend/sha256_trace_layout.h; the first n_pre variables are the preimage
+ * bits (512 a block), the variables of compression b are [block_starts[b], block_starts[b + 1]), block_starts[n_blocks] = n_aux.
+ * sp_sha256_plan_create (replaces the per-call circuit synthesis of src/bellpepper/r1cs.rs:359-409 by a once-per-key table) copies the plan to the device;
+ * msg_len = bytes of a message it serves, padded != 0: the message is padded as SHA-256 pads it into n_blocks blocks (Sha256Circuit), 0: msg_len = 64 and the
+ * message is one raw block (the step circuit). Descriptors and offsets are validated here, so that the kernel's addresses are in range by construction. */
+typedef struct sp_sha256_plan sp_sha256_plan;
+int sp_sha256_plan_create(sp_ctx* ctx, const uint32_t* descriptors, size_t n_aux, const uint32_t* block_starts, size_t n_blocks, size_t n_pre, size_t msg_len,
+                          int padded, sp_sha256_plan** out);
+void sp_sha256_plan_free(sp_sha256_plan* plan);
+/* out = n_aux, n_blocks, n_pre, msg_len, padded (what a driver checks against its key before it launches anything) */
+int sp_sha256_plan_info(const sp_sha256_plan* plan, uint64_t out[5]);
+/* The witnesses of n_msgs messages of msg_len bytes each (msgs = n_msgs * msg_len bytes; msg_len must be the plan's) in one launch - replaces
+ * precommitted_witness (src/bellpepper/r1cs.rs:359-409) for Sha256Circuit (benches/sha256_spartan.rs:78-136) and, with n_msgs > 1, the per-step synthesis of
+ * benches/sha256_neutronnova.rs:49-183: tables[m][off + v] = aux variable v of message m as a Montgomery-form element (zero or ONE), v < n_aux. The chaining
+ * values are hashed on the host and uploaded with the message words; ordered on the context's stream like sp_table_write_u64; `msgs` is free on return.
+ * digests (optional, n_msgs * 32 bytes): the SHA-256 state after each message's last block - the digest for a padded plan. */
+int sp_sha256_witness(sp_ctx* ctx, const sp_sha256_plan* plan, const uint8_t* msgs, size_t msg_len, size_t n_msgs, sp_table* const* tables, size_t off,
+                      uint8_t* digests);
 /* zero-filled table of `len` elements with the given zero-structure hints */
 int sp_table_zeros(sp_ctx* ctx, size_t len, size_t lo_eff, size_t hi_eff, sp_table** out);
 /* host -> device write of cnt elements at element offset off */

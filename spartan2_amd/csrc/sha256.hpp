@@ -107,6 +107,11 @@ class Sha256 {
     memcpy(h_, iv, 32);
   }
   static bool accelerated() { return have_shani(); }
+  // nblocks compressions on a chaining value the caller holds (the SHA-256 witness generator uploads the value every block starts from)
+  static void compress(uint32_t st[8], const uint8_t* p, size_t nblocks) {
+    if (have_shani()) blocks_shani(st, p, nblocks);
+    else blocks_portable(st, p, nblocks);
+  }
   void update(const void* data, size_t n) {
     const uint8_t* p = (const uint8_t*)data;
     total_ += n;

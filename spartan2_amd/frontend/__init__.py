@@ -30,6 +30,10 @@ def lib():
         L.spf_witness.restype = ctypes.POINTER(ctypes.c_uint64)
         L.spf_publics.restype = ctypes.POINTER(ctypes.c_uint64)
         L.spf_last_error.restype = ctypes.c_char_p
+        L.spf_sha256_witness_plan.restype = ctypes.c_void_p
+        L.spf_sha256_step_witness_plan.restype = ctypes.c_void_p
+        L.spf_sha256_plan_descriptors.restype = ctypes.POINTER(ctypes.c_uint32)
+        L.spf_sha256_plan_block_starts.restype = ctypes.POINTER(ctypes.c_uint32)
         _lib = L
     return _lib
 
@@ -95,3 +99,51 @@ def sha256_rest_circuit(preimage: bytes) -> R1CSInstanceInt:
     """Sha256Circuit of the reference's NeutronNova test (src/neutronnova_zk.rs:2357-2418): the whole circuit in synthesize, i.e. REST variables only;
     preimage bits LSB first per byte, x = 0 inputized."""
     return R1CSInstanceInt(lib().spf_sha256_rest_circuit(bytes(preimage), ctypes.c_size_t(len(preimage))))
+
+
+class Sha256WitnessPlan:
+    """For every aux variable of a SHA-256 circuit structure, the bit of its block's native compression trace that it equals
+    (sha256_witness_plan.hpp): `descriptors` (n_aux,) uint32 = slot | bit << 11 | invert << 17, `block_starts` (n_blocks + 1,), the first `n_pre`
+    variables being the preimage bits (512 per block). One plan serves every message of `msg_len` bytes."""
+
+    def __init__(self, handle):
+        if not handle:
+            raise RuntimeError(lib().spf_last_error().decode())
+        self._h = ctypes.c_void_p(handle)
+        d = (ctypes.c_uint64 * 6)()
+        lib().spf_sha256_plan_dims(self._h, d)
+        self.msg_len, padded, self.n_aux, self.n_pre, self.n_blocks, self.trace_slots = [int(x) for x in d]
+        self.padded = bool(padded)
+        self.descriptors = np.ctypeslib.as_array(lib().spf_sha256_plan_descriptors(self._h), (self.n_aux,)).copy()
+        self.block_starts = np.ctypeslib.as_array(lib().spf_sha256_plan_block_starts(self._h), (self.n_blocks + 1,)).copy()
+
+    def eval(self, msg: bytes, with_digest=False):
+        """The witness (n_aux,) uint64 of the plan's circuit for `msg`: native compressions -> trace -> bits, no circuit synthesis."""
+        if len(msg) != self.msg_len:
+            raise ValueError(f"this plan serves messages of {self.msg_len} bytes, got {len(msg)}")
+        out = np.zeros(self.n_aux, dtype=np.uint64)
+        dig = np.zeros(32, dtype=np.uint8)
+        if lib().spf_sha256_plan_eval(self._h, bytes(msg), out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), dig.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))) != 0:
+            raise RuntimeError(lib().spf_last_error().decode())
+        return (out, dig.tobytes()) if with_digest else out
+
+    def close(self):
+        if self._h:
+            lib().spf_sha256_plan_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def sha256_witness_plan(msg_len: int) -> Sha256WitnessPlan:
+    """Plan for sha256_circuit(msg) with len(msg) == msg_len >= 1 (the circuit's structure depends only on the length)."""
+    return Sha256WitnessPlan(lib().spf_sha256_witness_plan(ctypes.c_size_t(msg_len)))
+
+
+def sha256_step_witness_plan() -> Sha256WitnessPlan:
+    """Plan for sha256_step_circuit(block) (and the core circuit: the same shape on bytes(64))."""
+    return Sha256WitnessPlan(lib().spf_sha256_step_witness_plan())

@@ -4,6 +4,7 @@
 #include <string>
 
 #include "r1cs_builder.hpp"
+#include "sha256_witness_plan.hpp"
 
 using namespace sp_frontend;
 static thread_local std::string g_err;
@@ -96,4 +97,45 @@ int spf_sha256_selfcheck(const uint8_t* msg, size_t n, uint64_t* num_cons, uint6
   }
 }
 void spf_sha256_plain(const uint8_t* msg, size_t n, uint8_t* out32) { sha256_plain(msg, n, out32); }
+
+// ---- witness plans (sha256_witness_plan.hpp) ----
+void* spf_sha256_witness_plan(size_t msg_len) {
+  try {
+    return new Sha256WitnessPlan(sha256_witness_plan(msg_len));
+  } catch (const std::exception& e) {
+    g_err = e.what();
+    return nullptr;
+  }
+}
+void* spf_sha256_step_witness_plan() {
+  try {
+    return new Sha256WitnessPlan(sha256_step_witness_plan());
+  } catch (const std::exception& e) {
+    g_err = e.what();
+    return nullptr;
+  }
+}
+void spf_sha256_plan_free(void* p) { delete (Sha256WitnessPlan*)p; }
+// out: msg_len, padded, n_aux, n_pre, n_blocks, trace slots per block
+void spf_sha256_plan_dims(void* p, uint64_t out[6]) {
+  auto* P = (Sha256WitnessPlan*)p;
+  uint64_t v[6] = {P->msg_len, P->padded ? 1u : 0u, P->n_aux, P->n_pre, P->n_blocks, sha256_trace::SLOTS};
+  memcpy(out, v, sizeof v);
+}
+const uint32_t* spf_sha256_plan_descriptors(void* p) { return ((Sha256WitnessPlan*)p)->desc.data(); }
+const uint32_t* spf_sha256_plan_block_starts(void* p) { return ((Sha256WitnessPlan*)p)->block_starts.data(); }
+// witness of the plan's circuit for `msg` (the plan's msg_len bytes): n_aux values in {0, 1}; digest32 (optional): SHA-256 state after the last block
+int spf_sha256_plan_eval(void* p, const uint8_t* msg, uint64_t* out_u64, uint8_t* digest32) {
+  try {
+    uint32_t H[8];
+    sha256_plan_eval(*(Sha256WitnessPlan*)p, msg, out_u64, H);
+    if (digest32)
+      for (int i = 0; i < 8; ++i)
+        for (int k = 0; k < 4; ++k) digest32[4 * i + k] = (uint8_t)(H[i] >> (24 - 8 * k));
+    return 0;
+  } catch (const std::exception& e) {
+    g_err = e.what();
+    return -1;
+  }
+}
 }

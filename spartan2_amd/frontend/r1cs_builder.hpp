@@ -21,6 +21,8 @@
 #include <utility>
 #include <vector>
 
+#include "sha256_trace_layout.h"
+
 namespace sp_frontend {
 
 static const uint32_t INPUT_FLAG = 0x80000000u;
@@ -37,7 +39,19 @@ struct CsrInt {
   std::vector<uint64_t> indptr{0};
 };
 
+// Witness-plan recorder (sha256_witness_plan.hpp): while a SHA-256 circuit is generated with one attached, the gadget calls note for every aux variable
+// they allocate which bit of its block's native trace (sha256_trace_layout.h) the variable equals. Recording changes nothing the generator emits.
+struct PlanRecorder {
+  std::vector<uint32_t> desc;          // per aux variable, allocation order: sha256_trace::desc_pack(slot, bit, invert)
+  std::vector<uint32_t> block_starts;  // first aux variable allocated inside compression b
+  void tag(uint32_t var, uint32_t slot, uint32_t bit, bool invert) {
+    if (desc.size() <= var) desc.resize((size_t)var + 1, sha256_trace::DESC_UNSET);
+    desc[var] = sha256_trace::desc_pack(slot, bit, invert);
+  }
+};
+
 struct ConstraintSystem {
+  PlanRecorder* rec = nullptr;
   std::vector<uint64_t> aux;     // aux assignment
   std::vector<uint64_t> inputs;  // input assignment, inputs[0] == 1
   CsrInt A, B, C;
@@ -303,28 +317,55 @@ static const uint32_t SHA256_K[64] = {
     0x682e6ff3, 0x748f82ee, 0x78a5636f, 0x84c87814, 0x8cc70208, 0x90befffa, 0xa4506ceb, 0xbef9a3f7, 0xc67178f2};
 static const uint32_t SHA256_IV[8] = {0x6a09e667, 0xbb67ae85, 0x3c6ef372, 0xa54ff53a, 0x510e527f, 0x9b05688c, 0x1f83d9ab, 0x5be0cd19};
 
+// PlanRecorder helpers. `first` = cs.aux.size() before the gadget call. A result bit that is a variable allocated by the call (var >= first) carries
+// the logical value of trace bit (slot, k) - inverted when the gadget handed back the variable's negation.
+inline void plan_tag_word(ConstraintSystem& cs, size_t first, const UInt32& r, uint32_t slot) {
+  if (!cs.rec) return;
+  for (uint32_t k = 0; k < 32; ++k)
+    if (r.bits[k].kind != Boolean::Const && r.bits[k].var >= first) cs.rec->tag(r.bits[k].var, slot, k, r.bits[k].kind == Boolean::Not);
+}
+inline void plan_tag_sum(ConstraintSystem& cs, size_t first, uint32_t slot) {  // u32_addmany: result bit j (carries included) is variable first + j
+  if (!cs.rec) return;
+  for (size_t v = first; v < cs.aux.size(); ++v) cs.rec->tag((uint32_t)v, slot, (uint32_t)(v - first), false);
+}
+
 // one compression: 512 input bits (big-endian words) + current state -> new state. Statement order, deferred additions (`Maybe`) and the operand lists
 // are those of bellpepper::gadgets::sha256::sha256_compression_function (bellpepper 0.4.0, a fork of bellman's gadget; the crate is not under
 // /root/reference): the working variables a and e are kept as operand lists and only become bits at the start of the next round — or, after the last
 // round, together with the chaining value they are added to (h0 and h4 are ONE addition of 8 / 7 operands each).
 inline void sha256_compression(ConstraintSystem& cs, const Boolean* input512, UInt32 state[8]) {
+  namespace T = sha256_trace;
+  if (cs.rec) cs.rec->block_starts.push_back((uint32_t)cs.aux.size());
+  // (with a recorder attached) a ^ b into trace slot `slot`
+  auto xor_into = [&cs](const UInt32& a, const UInt32& b, uint32_t slot) {
+    const size_t first = cs.aux.size();
+    UInt32 r = u32_xor(cs, a, b);
+    plan_tag_word(cs, first, r, slot);
+    return r;
+  };
   MultiEqSim me;
   std::vector<UInt32> w(64);
   for (int i = 0; i < 16; ++i) w[i] = UInt32::from_bits_be(input512 + 32 * i);
   for (int i = 16; i < 64; ++i) {
-    UInt32 s0 = u32_xor(cs, u32_xor(cs, w[i - 15].rotr(7), w[i - 15].rotr(18)), w[i - 15].shr(3));
-    UInt32 s1 = u32_xor(cs, u32_xor(cs, w[i - 2].rotr(17), w[i - 2].rotr(19)), w[i - 2].shr(10));
+    const uint32_t sl = T::SCHED + 4 * (uint32_t)(i - 16);
+    UInt32 s0 = xor_into(xor_into(w[i - 15].rotr(7), w[i - 15].rotr(18), sl + 0), w[i - 15].shr(3), sl + 1);
+    UInt32 s1 = xor_into(xor_into(w[i - 2].rotr(17), w[i - 2].rotr(19), sl + 2), w[i - 2].shr(10), sl + 3);
+    const size_t first = cs.aux.size();
     w[i] = u32_addmany(cs, {w[i - 16], s0, w[i - 7], s1}, &me);
+    plan_tag_sum(cs, first, T::W + (uint32_t)i);
   }
   struct Maybe {  // Deferred(operands) | Concrete(value)
     bool deferred = false;
     std::vector<UInt32> ops;
     UInt32 value;
-    UInt32 compute(ConstraintSystem& cs, MultiEqSim& me, const std::vector<UInt32>& others) {
+    UInt32 compute(ConstraintSystem& cs, MultiEqSim& me, const std::vector<UInt32>& others, uint32_t slot) {
       if (!deferred) return value;
       std::vector<UInt32> v = ops;
       v.insert(v.end(), others.begin(), others.end());
-      return u32_addmany(cs, v, &me);
+      const size_t first = cs.aux.size();
+      UInt32 r = u32_addmany(cs, v, &me);
+      plan_tag_sum(cs, first, slot);
+      return r;
     }
   };
   Maybe a, e;
@@ -332,15 +373,26 @@ inline void sha256_compression(ConstraintSystem& cs, const Boolean* input512, UI
   e.value = state[4];
   UInt32 b = state[1], c = state[2], d = state[3], f = state[5], g = state[6], h = state[7];
   for (int i = 0; i < 64; ++i) {
-    const UInt32 new_e = e.compute(cs, me, {});
-    UInt32 s1 = u32_xor(cs, u32_xor(cs, new_e.rotr(6), new_e.rotr(11)), new_e.rotr(25));
+    const uint32_t sl = T::ROUND + 9 * (uint32_t)i;
+    const UInt32 new_e = e.compute(cs, me, {}, sl + 0);
+    UInt32 s1 = xor_into(xor_into(new_e.rotr(6), new_e.rotr(11), sl + 1), new_e.rotr(25), sl + 2);
     UInt32 ch;
-    for (int k = 0; k < 32; ++k) ch.bits[k] = sha256_ch(cs, new_e.bits[k], f.bits[k], g.bits[k]);
+    {
+      const size_t first = cs.aux.size();
+      for (int k = 0; k < 32; ++k) ch.bits[k] = sha256_ch(cs, new_e.bits[k], f.bits[k], g.bits[k]);
+      plan_tag_word(cs, first, ch, sl + 3);
+    }
     const std::vector<UInt32> temp1 = {h, s1, ch, UInt32::constant(SHA256_K[i]), w[i]};
-    const UInt32 new_a = a.compute(cs, me, {});
-    UInt32 s0 = u32_xor(cs, u32_xor(cs, new_a.rotr(2), new_a.rotr(13)), new_a.rotr(22));
+    const UInt32 new_a = a.compute(cs, me, {}, sl + 4);
+    UInt32 s0 = xor_into(xor_into(new_a.rotr(2), new_a.rotr(13), sl + 5), new_a.rotr(22), sl + 6);
     UInt32 maj;
-    for (int k = 0; k < 32; ++k) maj.bits[k] = sha256_maj(cs, new_a.bits[k], b.bits[k], c.bits[k]);
+    for (int k = 0; k < 32; ++k) {
+      const size_t first = cs.aux.size();
+      maj.bits[k] = sha256_maj(cs, new_a.bits[k], b.bits[k], c.bits[k]);
+      // two variables: b & c, then maj; one: the AND (or its negation) that maj folds to beside a constant operand
+      if (cs.rec && cs.aux.size() == first + 2) cs.rec->tag((uint32_t)first, sl + 7, (uint32_t)k, false);
+      if (cs.rec && cs.aux.size() > first) cs.rec->tag(maj.bits[k].var, sl + 8, (uint32_t)k, maj.bits[k].kind == Boolean::Not);
+    }
     h = g;
     g = f;
     f = new_e;
@@ -356,14 +408,20 @@ inline void sha256_compression(ConstraintSystem& cs, const Boolean* input512, UI
     a.ops.push_back(maj);
   }
   UInt32 out[8];
-  out[0] = a.compute(cs, me, {state[0]});
-  out[1] = u32_addmany(cs, {state[1], b}, &me);
-  out[2] = u32_addmany(cs, {state[2], c}, &me);
-  out[3] = u32_addmany(cs, {state[3], d}, &me);
-  out[4] = e.compute(cs, me, {state[4]});
-  out[5] = u32_addmany(cs, {state[5], f}, &me);
-  out[6] = u32_addmany(cs, {state[6], g}, &me);
-  out[7] = u32_addmany(cs, {state[7], h}, &me);
+  auto add_into = [&cs, &me](const UInt32& x, const UInt32& y, uint32_t slot) {
+    const size_t first = cs.aux.size();
+    UInt32 r = u32_addmany(cs, {x, y}, &me);
+    plan_tag_sum(cs, first, slot);
+    return r;
+  };
+  out[0] = a.compute(cs, me, {state[0]}, T::OUT + 0);
+  out[1] = add_into(state[1], b, T::OUT + 1);
+  out[2] = add_into(state[2], c, T::OUT + 2);
+  out[3] = add_into(state[3], d, T::OUT + 3);
+  out[4] = e.compute(cs, me, {state[4]}, T::OUT + 4);
+  out[5] = add_into(state[5], f, T::OUT + 5);
+  out[6] = add_into(state[6], g, T::OUT + 6);
+  out[7] = add_into(state[7], h, T::OUT + 7);
   for (int i = 0; i < 8; ++i) state[i] = out[i];
   me.flush();
   cs.stat_multieq_rows += me.rows;
@@ -450,11 +508,18 @@ inline R1CSInstanceInt finalize(ConstraintSystem& cs, size_t num_shared, size_t 
 
 // Sha256Circuit of benches/sha256_spartan.rs:36-152: all preimage bits (MSB first per byte) are
 // precommitted witness bits; digest bits are the 256 public inputs tied by `bit * 1 = num`.
-inline R1CSInstanceInt sha256_spartan_circuit(const std::vector<uint8_t>& preimage) {
+// `rec`: see PlanRecorder. Preimage bit p (MSB first per byte) is bit 31 - p % 32 of message word (p % 512) / 32 of block p / 512.
+inline void plan_tag_preimage(ConstraintSystem& cs, const std::vector<Boolean>& bits) {
+  if (!cs.rec) return;
+  for (size_t p = 0; p < bits.size(); ++p) cs.rec->tag(bits[p].var, sha256_trace::W + (uint32_t)(p % 512) / 32, 31 - (uint32_t)(p % 32), false);
+}
+inline R1CSInstanceInt sha256_spartan_circuit(const std::vector<uint8_t>& preimage, PlanRecorder* rec = nullptr) {
   ConstraintSystem cs;
+  cs.rec = rec;
   std::vector<Boolean> bits;
   for (uint8_t byte : preimage)
     for (int i = 7; i >= 0; --i) bits.push_back(alloc_bit(cs, (byte >> i) & 1));
+  plan_tag_preimage(cs, bits);
   std::vector<Boolean> hash = sha256_gadget(cs, bits);
   uint8_t expect[32];
   sha256_plain(preimage.data(), preimage.size(), expect);
@@ -473,15 +538,18 @@ inline R1CSInstanceInt sha256_spartan_circuit(const std::vector<uint8_t>& preima
 // Sha256StepCircuit / CoreCircuit of benches/sha256_neutronnova.rs:49-183: the 512 block bits (MSB first per byte) are precommitted witness bits,
 // the chaining value is the constant IV, ONE compression (no padding block), then x = 0 allocated and inputized (AllocatedNum::inputize:
 // input * 1 = x). The core circuit is the same shape on 512 zero bits (:161-182).
-inline R1CSInstanceInt sha256_step_circuit(const uint8_t block[64]) {
+inline R1CSInstanceInt sha256_step_circuit(const uint8_t block[64], PlanRecorder* rec = nullptr) {
   ConstraintSystem cs;
+  cs.rec = rec;
   std::vector<Boolean> bits;
   for (int k = 0; k < 64; ++k)
     for (int i = 7; i >= 0; --i) bits.push_back(alloc_bit(cs, (block[k] >> i) & 1));
+  plan_tag_preimage(cs, bits);
   UInt32 state[8];
   for (int i = 0; i < 8; ++i) state[i] = UInt32::constant(SHA256_IV[i]);
   sha256_compression(cs, bits.data(), state);
   const uint32_t x = cs.alloc_aux(0);
+  if (rec) rec->tag(x, sha256_trace::ZERO, 0, false);
   const uint32_t in = cs.alloc_input(0);
   cs.enforce({{in, 1}}, {{ConstraintSystem::one(), 1}}, {{x, 1}});
   size_t num_aux = cs.aux.size();

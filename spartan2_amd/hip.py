@@ -207,6 +207,43 @@ class Table:
             pass
 
 
+class Sha256Plan:
+    """A frontend.Sha256WitnessPlan resident on the device (sp_sha256_plan_create): witness generation for the SHA-256 circuits by
+    sp_sha256_witness instead of circuit synthesis + upload."""
+
+    def __init__(self, ctx: Context, plan):
+        self.ctx = ctx
+        self.n_aux, self.n_blocks, self.n_pre, self.msg_len, self.padded = plan.n_aux, plan.n_blocks, plan.n_pre, plan.msg_len, plan.padded
+        desc = np.ascontiguousarray(plan.descriptors, dtype=np.uint32)
+        starts = np.ascontiguousarray(plan.block_starts, dtype=np.uint32)
+        self.h = ctypes.c_void_p()
+        u32p = ctypes.POINTER(ctypes.c_uint32)
+        check(lib().sp_sha256_plan_create(ctx.h, desc.ctypes.data_as(u32p), ctypes.c_size_t(len(desc)), starts.ctypes.data_as(u32p), ctypes.c_size_t(plan.n_blocks),
+                                          ctypes.c_size_t(plan.n_pre), ctypes.c_size_t(plan.msg_len), int(plan.padded), ctypes.byref(self.h)))
+
+    def witness(self, msgs, tables, off=0):
+        """sp_sha256_witness: tables[m][off + v] = aux variable v of msgs[m]; returns the SHA-256 state after each message's last block (bytes)."""
+        msgs = [bytes(m) for m in msgs]
+        assert len(msgs) == len(tables) and all(len(m) == self.msg_len for m in msgs)
+        n = len(msgs)
+        buf, _ = _bytes(b"".join(msgs))
+        dig = np.zeros(32 * max(n, 1), dtype=np.uint8)
+        tarr = (ctypes.c_void_p * max(n, 1))(*[t.h for t in tables])
+        check(lib().sp_sha256_witness(self.ctx.h, self.h, p8(buf), ctypes.c_size_t(self.msg_len), ctypes.c_size_t(n), tarr, ctypes.c_size_t(off), p8(dig)))
+        return [dig[32 * i : 32 * i + 32].tobytes() for i in range(n)]
+
+    def free(self):
+        if self.h:
+            lib().sp_sha256_plan_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 class Transcript:
     """Keccak256Transcript (src/provider/keccak.rs:26-105)."""
 

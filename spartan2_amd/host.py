@@ -108,6 +108,8 @@ class SpartanSNARK:
         self.dims = {k: int(v) for k, v in zip(DIM_NAMES, d)}
         self.vk_digest = dig
         self.ps = None
+        self.publics = np.ascontiguousarray(inst.publics, dtype=np.uint64)  # the public values prove() states: the instance's, or prep_prove_sha256's
+        self._sha_plan = None
         si = (ctypes.c_uint64 * 8)()
         _check(lib().ss_pk_shape_info(self.pk, si))
         self.shape_info = {"nnz": [int(si[i]) for i in range(3)], "nnz_filtered": [int(si[3 + i]) for i in range(3)], "long_columns": int(si[6]),
@@ -122,7 +124,35 @@ class SpartanSNARK:
         if self.ps:
             lib().ss_prep_free(self.ps)
         self.ps = ps
+        self.publics = np.ascontiguousarray(self.inst.publics, dtype=np.uint64)
         return used.value
+
+    def prep_prove_sha256(self, msg: bytes, tape: np.ndarray, is_small=True):
+        """prep_prove with the witness generated on the device (ss_prep_prove_sha256) for a key set up from frontend.sha256_circuit(m), len(m) == len(msg):
+        callable again and again on one key with different messages; the prove() that follows uses the digest bits of `msg` as public values (self.publics).
+        The plan (frontend.sha256_witness_plan(len(msg))) is made on the first call and kept with the key."""
+        msg = bytes(msg)
+        if self._sha_plan is None or self._sha_plan.msg_len != len(msg):
+            from . import frontend
+
+            self._sha_plan = hip.Sha256Plan(self.ctx, frontend.sha256_witness_plan(len(msg)))
+        used = ctypes.c_size_t(0)
+        ps = ctypes.c_void_p()
+        pub = np.zeros(256, dtype=np.uint64)
+        buf = np.frombuffer(msg, dtype=np.uint8).copy()
+        _check(lib().ss_prep_prove_sha256(self.pk, self._sha_plan.h, hip.p8(buf), ctypes.c_size_t(len(msg)), int(is_small), hip.p8(tape), ctypes.c_size_t(tape.shape[0]),
+                                          ctypes.byref(used), ctypes.byref(ps), hip.p64(pub)))
+        if self.ps:
+            lib().ss_prep_free(self.ps)
+        self.ps = ps
+        self.publics = pub
+        return used.value
+
+    def prep_phases(self):
+        """host wall-clock of the last prep_prove's phases, ms (ss_prep_phases)"""
+        out = (ctypes.c_double * 8)()
+        lib().ss_prep_phases(self.ps, out)
+        return dict(witness=out[0], commit=out[1], tables=out[2], matvec=out[3], scratch=out[4], total=out[6])
 
     def set_flags(self, prefix_cache=None, lz_direct=None, reference_order=None):
         """Driver options of the current prep state (spartan_snark.cpp FLAG_*): prefix_cache = keep the transcript prefix's sponge state across
@@ -155,7 +185,7 @@ class SpartanSNARK:
         words = np.zeros(n, dtype=np.uint64)
         used = ctypes.c_size_t(0)
         ms = (ctypes.c_double * 7)()
-        pub = np.ascontiguousarray(self.inst.publics, dtype=np.uint64)
+        pub = self.publics
         cb = None
         if synthesize is not None:
             nrest = self.dims["num_rest_unpadded"]
@@ -214,6 +244,9 @@ class SpartanSNARK:
         if self.ps:
             lib().ss_prep_free(self.ps)
             self.ps = None
+        if getattr(self, "_sha_plan", None) is not None:
+            self._sha_plan.free()
+            self._sha_plan = None
         if self.pk:
             lib().ss_pk_free(self.pk)
             self.pk = None
@@ -511,6 +544,7 @@ class NeutronNovaZkSNARK:
         self.info = dict(zip(("nb", "nx", "ny", "vc_rounds", "vc_vars", "vc_cons", "vc_cons_unpadded", "vc_public"), [int(x) for x in info]))
         self.vk_digest = dig
         self.ps = None
+        self._sha_plan = None
         lib().nnz_proof_words.restype = ctypes.c_size_t
 
     def prep_prove(self, tape: np.ndarray, is_small=True):
@@ -522,6 +556,25 @@ class NeutronNovaZkSNARK:
         ps = ctypes.c_void_p()
         _check(lib().nnz_prep_prove(self.pk, ctypes.c_size_t(len(self.steps)), hip.p64(sw), ctypes.c_size_t(sw.shape[1]), hip.p64(sp), ctypes.c_size_t(sp.shape[1]), hip.p64(cw),
                                     hip.p64(cp), int(is_small), hip.p8(tape), ctypes.c_size_t(tape.shape[0]), ctypes.byref(used), ctypes.byref(ps)))
+        if self.ps:
+            lib().nnz_prep_free(self.ps)
+        self.ps = ps
+        return used.value
+
+    def prep_prove_sha256(self, blocks, tape: np.ndarray, is_small=True):
+        """prep_prove with every step's witness and the core circuit's generated on the device in one launch (nnz_prep_prove_sha256) for a key set up from
+        frontend.sha256_step_circuit instances: blocks = one 64-byte block per step; the core circuit is the zero block, every public value is x = 0."""
+        blocks = [bytes(b) for b in blocks]
+        assert all(len(b) == 64 for b in blocks)
+        if self._sha_plan is None:
+            from . import frontend
+
+            self._sha_plan = hip.Sha256Plan(self.ctx, frontend.sha256_step_witness_plan())
+        buf = np.frombuffer(b"".join(blocks), dtype=np.uint8).copy()
+        used = ctypes.c_size_t(0)
+        ps = ctypes.c_void_p()
+        _check(lib().nnz_prep_prove_sha256(self.pk, self._sha_plan.h, hip.p8(buf), ctypes.c_size_t(len(blocks)), int(is_small), hip.p8(tape), ctypes.c_size_t(tape.shape[0]),
+                                           ctypes.byref(used), ctypes.byref(ps)))
         if self.ps:
             lib().nnz_prep_free(self.ps)
         self.ps = ps
@@ -573,6 +626,9 @@ class NeutronNovaZkSNARK:
         if self.ps:
             lib().nnz_prep_free(self.ps)
             self.ps = None
+        if getattr(self, "_sha_plan", None) is not None:
+            self._sha_plan.free()
+            self._sha_plan = None
         if self.pk:
             lib().nnz_pk_free(self.pk)
             self.pk = None

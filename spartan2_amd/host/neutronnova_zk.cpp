@@ -249,19 +249,18 @@ static NNZkKey* nn_setup(sp_ctx* ctx, const R1CSIntView& Rs, const R1CSIntView& 
 // The witness of one circuit as a device table [shared | precommitted | rest] at the padded offsets (bellpepper/r1cs.rs:306-409): the machine words cross the bus
 // as they are and become Montgomery-form elements on the device (sp_table_write_u64). `shared_words`: step 0's shared segment - every circuit of a batch
 // carries it (src/neutronnova_zk.rs:1485-1488).
-static void upload_witness(sp_ctx* ctx, const sp_dims& d, const uint64_t* w, const uint64_t* shared_words, size_t shared_count, sp_table** out) {
-  ck(sp_table_zeros(ctx, d.num_shared + d.num_precommitted + d.num_rest, (size_t)-1, (size_t)-1, out), "alloc W");
-  ck(sp_table_write_u64(ctx, *out, 0, shared_words, shared_count), "upload W (shared)");
-  ck(sp_table_write_u64(ctx, *out, d.num_shared, w + d.num_shared_unpadded, d.num_precommitted_unpadded), "upload W (precommitted)");
-  ck(sp_table_write_u64(ctx, *out, d.num_shared + d.num_precommitted, w + d.num_shared_unpadded + d.num_precommitted_unpadded, d.num_rest_unpadded), "upload W (rest)");
+static void upload_witness(sp_ctx* ctx, const sp_dims& d, const uint64_t* w, const uint64_t* shared_words, size_t shared_count, sp_table* out) {
+  ck(sp_table_write_u64(ctx, out, 0, shared_words, shared_count), "upload W (shared)");
+  ck(sp_table_write_u64(ctx, out, d.num_shared, w + d.num_shared_unpadded, d.num_precommitted_unpadded), "upload W (precommitted)");
+  ck(sp_table_write_u64(ctx, out, d.num_shared + d.num_precommitted, w + d.num_shared_unpadded + d.num_precommitted_unpadded, d.num_rest_unpadded), "upload W (rest)");
 }
 
-// prep_prove (:1477-1603): shared commitment from step 0's witness, one precommitted commitment per step and for the core
-static NNZkPrep* nn_prep_prove(const NNZkKey& pk, size_t n, const uint64_t* step_wit, size_t wit_len, const uint64_t* step_pub, size_t npub, const uint64_t* core_wit,
-                               const uint64_t* core_pub, bool is_small, Tape& tape) {
+// prep_prove (:1477-1603) behind its witness source: shared commitment from step 0's shared segment (`shared_words`), one precommitted commitment per step
+// and for the core. `fill_W(Ws)` writes the witnesses into the zeroed tables Ws[0 .. n) (the steps) and Ws[n] (the core); the blinds are drawn from the
+// tape in the same order whichever source fills them: machine words from the frontend (nn_prep_prove) or the SHA-256 witness kernel (nn_prep_prove_sha256).
+static NNZkPrep* nn_prep_prove_from(const NNZkKey& pk, size_t n, const uint64_t* shared_words, const uint64_t* step_pub, size_t npub, const uint64_t* core_pub, bool is_small,
+                                    Tape& tape, const std::function<void(sp_table* const* Ws)>& fill_W) {
   const sp_dims& d = pk.dims;
-  if (n != pk.num_steps || wit_len != d.num_shared_unpadded + d.num_precommitted_unpadded + d.num_rest_unpadded || npub != d.num_public)
-    throw Error(SP_ERR_INVALID_WITNESS_LENGTH, "InvalidWitnessLength");
   auto* ps = new NNZkPrep();
   try {
     sp_ctx* ctx = pk.ctx;
@@ -273,14 +272,23 @@ static NNZkPrep* nn_prep_prove(const NNZkKey& pk, size_t n, const uint64_t* step
       for (auto& b : ps->r_shared) b = tape.next();
       sp_table* t = nullptr;
       ck(sp_table_zeros(ctx, d.num_shared, (size_t)-1, (size_t)-1, &t), "alloc shared");
-      int rc = sp_table_write_u64(ctx, t, 0, step_wit, d.num_shared_unpadded);
+      int rc = sp_table_write_u64(ctx, t, 0, shared_words, d.num_shared_unpadded);
       ps->comm_shared.resize(rows_sh);
       if (!rc) rc = sp_hyrax_commit(ctx, pk.ck, t, 0, d.num_shared, u64p(ps->r_shared.data()), is_small ? 1 : 0, u64p(&ps->comm_shared[0].x));
       sp_table_free(t);
       ck(rc, "commit shared");
     }
-    auto precommit = [&](const sp_dims& dd, const uint64_t* wit, const uint64_t* pub, NNPre* p) {
-      upload_witness(ctx, dd, wit, step_wit, d.num_shared_unpadded, &p->W);  // every circuit shares step 0's shared witness (:1485-1488)
+    {
+      std::vector<sp_table*> Ws(n + 1);
+      for (size_t i = 0; i <= n; ++i) {
+        const sp_dims& dd = i < n ? d : pk.dims_core;
+        NNPre* p = i < n ? &ps->steps[i] : &ps->core;
+        ck(sp_table_zeros(ctx, dd.num_shared + dd.num_precommitted + dd.num_rest, (size_t)-1, (size_t)-1, &p->W), "alloc W");
+        Ws[i] = p->W;
+      }
+      fill_W(Ws.data());
+    }
+    auto precommit = [&](const sp_dims& dd, const uint64_t* pub, NNPre* p) {
       p->publics.resize(dd.num_public);
       for (size_t i = 0; i < dd.num_public; ++i) p->publics[i] = fe_from_u64<S>(pub[i]);
       if (dd.num_precommitted_unpadded) {
@@ -291,8 +299,8 @@ static NNZkPrep* nn_prep_prove(const NNZkKey& pk, size_t n, const uint64_t* step
         ck(sp_hyrax_commit(ctx, pk.ck, p->W, dd.num_shared, dd.num_precommitted, u64p(p->r_pre.data()), is_small ? 1 : 0, u64p(&p->comm_pre[0].x)), "commit precommitted");
       }
     };
-    for (size_t i = 0; i < n; ++i) precommit(d, step_wit + i * wit_len, step_pub + i * npub, &ps->steps[i]);
-    precommit(pk.dims_core, core_wit, core_pub, &ps->core);
+    for (size_t i = 0; i < n; ++i) precommit(d, step_pub + i * npub, &ps->steps[i]);
+    precommit(pk.dims_core, core_pub, &ps->core);
     {  // can_cache_matvec (:1523) always holds here: nn_setup rejects rest variables and challenges, so z = [W | 1 | X] is fully known
       std::vector<fe_t> X(n * d.num_public);
       std::vector<const sp_table*> Ws(n);
@@ -307,6 +315,40 @@ static NNZkPrep* nn_prep_prove(const NNZkKey& pk, size_t n, const uint64_t* step
     throw;
   }
   return ps;
+}
+
+static NNZkPrep* nn_prep_prove(const NNZkKey& pk, size_t n, const uint64_t* step_wit, size_t wit_len, const uint64_t* step_pub, size_t npub, const uint64_t* core_wit,
+                               const uint64_t* core_pub, bool is_small, Tape& tape) {
+  const sp_dims& d = pk.dims;
+  if (n != pk.num_steps || wit_len != d.num_shared_unpadded + d.num_precommitted_unpadded + d.num_rest_unpadded || npub != d.num_public)
+    throw Error(SP_ERR_INVALID_WITNESS_LENGTH, "InvalidWitnessLength");
+  sp_ctx* ctx = pk.ctx;
+  return nn_prep_prove_from(pk, n, step_wit, step_pub, npub, core_pub, is_small, tape, [&](sp_table* const* Ws) {
+    // every circuit shares step 0's shared witness (:1485-1488)
+    for (size_t i = 0; i < n; ++i) upload_witness(ctx, d, step_wit + i * wit_len, step_wit, d.num_shared_unpadded, Ws[i]);
+    upload_witness(ctx, pk.dims_core, core_wit, step_wit, d.num_shared_unpadded, Ws[n]);
+  });
+}
+
+// prep_prove for Sha256StepCircuit / CoreCircuit (benches/sha256_neutronnova.rs:49-183) with the witnesses generated on the device: the reference synthesises
+// every step inside prep_prove (src/neutronnova_zk.rs:1487-1518); here all n step witnesses and the core circuit's (the same plan on the zero block, :161-182)
+// are ONE sp_sha256_witness launch. blocks = n x 64 bytes; the circuits' one public value is x = 0.
+static NNZkPrep* nn_prep_prove_sha256(const NNZkKey& pk, const sp_sha256_plan* plan, const uint8_t* blocks, size_t n, bool is_small, Tape& tape) {
+  const sp_dims &d = pk.dims, &dc = pk.dims_core;
+  uint64_t info[5];
+  ck(sp_sha256_plan_info(plan, info), "plan info");
+  if (n != pk.num_steps || d.num_shared_unpadded != 0 || d.num_rest_unpadded != 0 || dc.num_shared_unpadded != 0 || dc.num_rest_unpadded != 0 ||
+      info[0] != d.num_precommitted_unpadded || info[0] != dc.num_precommitted_unpadded)
+    throw Error(SP_ERR_INVALID_WITNESS_LENGTH, "InvalidWitnessLength: the plan's variable count is not the key's");
+  if (info[3] != 64 || info[4] || d.num_public != 1 || dc.num_public != 1 || d.num_shared != dc.num_shared)
+    throw Error(SP_ERR_INVALID_INPUT_LENGTH, "not the step circuit's plan / key");
+  sp_ctx* ctx = pk.ctx;
+  const std::vector<uint64_t> zeros(n + 1, 0);  // x = 0 for every step and the core
+  return nn_prep_prove_from(pk, n, nullptr, zeros.data(), 1, zeros.data(), is_small, tape, [&](sp_table* const* Ws) {
+    std::vector<uint8_t> msgs(64 * (n + 1), 0);  // the core circuit: the zero block
+    memcpy(msgs.data(), blocks, 64 * n);
+    ck(sp_sha256_witness(ctx, plan, msgs.data(), 64, n + 1, Ws, d.num_shared, nullptr), "sha256 witness");
+  });
 }
 
 struct ProofBuf {
@@ -1765,6 +1807,18 @@ void nnz_pk_info(void* pk_, uint64_t out[8], uint8_t digest[32]) {
   memcpy(digest, pk->vk_digest, 32);
 }
 size_t nnz_proof_words(void* pk_) { return proof_words(*(NNZkKey*)pk_); }
+// prep_prove with the step / core witnesses generated on the device (see nn_prep_prove_sha256): blocks = n x 64 bytes
+int nnz_prep_prove_sha256(void* pk, const sp_sha256_plan* plan, const uint8_t* blocks, size_t n, int is_small, const uint8_t* tape, size_t tape_blocks, size_t* tape_used,
+                          void** out_ps) {
+  try {
+    Tape t{tape, tape_blocks};
+    *out_ps = nn_prep_prove_sha256(*(NNZkKey*)pk, plan, blocks, n, is_small != 0, t);
+    if (tape_used) *tape_used = t.pos;
+    return 0;
+  } catch (...) {
+    return catch_all_nn();
+  }
+}
 int nnz_prep_prove(void* pk, size_t n, const uint64_t* step_wit, size_t wit_len, const uint64_t* step_pub, size_t npub, const uint64_t* core_wit, const uint64_t* core_pub,
                    int is_small, const uint8_t* tape, size_t tape_blocks, size_t* tape_used, void** out_ps) {
   try {

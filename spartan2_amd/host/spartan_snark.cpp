@@ -153,10 +153,11 @@ SpartanProverKey* setup(sp_ctx* ctx, const R1CSIntView& R) {
 
 static double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
-// SpartanSNARK::prep_prove (src/spartan.rs:176-216)
-SpartanPrepSNARK* prep_prove(const SpartanProverKey& pk, const uint64_t* witness_u64, size_t n_witness, bool is_small, Tape& tape) {
+// SpartanSNARK::prep_prove (src/spartan.rs:176-216) behind its witness source. `fill_W` writes the witness segments into the zeroed table W (each segment
+// at its padded offset); everything after it - blinds drawn from the tape in the same order, commitments, tables, cached Az/Bz/Cz, scratch - is shared by
+// the sources: machine words from the frontend (prep_prove) or the SHA-256 witness kernel (prep_prove_sha256).
+static SpartanPrepSNARK* prep_prove_from(const SpartanProverKey& pk, bool is_small, Tape& tape, const std::function<void(sp_table* W)>& fill_W) {
   const sp_dims& d = pk.dims;
-  if (n_witness != d.num_shared_unpadded + d.num_precommitted_unpadded + d.num_rest_unpadded) throw Error(SP_ERR_INVALID_WITNESS_LENGTH, "InvalidWitnessLength");
   auto* ps = new SpartanPrepSNARK();
   ps->bg.set_spin_policy(&helper_may_spin);
   ps->bg2.set_spin_policy(&helper_may_spin);
@@ -182,11 +183,7 @@ SpartanPrepSNARK* prep_prove(const SpartanProverKey& pk, const uint64_t* witness
     // The words go to the device as they are (8 bytes a value) and become Montgomery-form elements there: sp_table_write_u64 (the reference hands the same
     // machine words to msm_small, hyrax_pc.rs:266-292, and never builds wide scalars for the commitment either).
     ck(sp_table_zeros(ctx, M, (size_t)-1, (size_t)-1, &ps->W), "alloc W");
-    auto put = [&](size_t dst, size_t src, size_t cnt) { ck(sp_table_write_u64(ctx, ps->W, dst, witness_u64 + src, cnt), "upload W"); };
-    put(0, 0, d.num_shared_unpadded);
-    put(d.num_shared, d.num_shared_unpadded, d.num_precommitted_unpadded);
-    // (with verifier challenges the rest segment is synthesized inside every prove, after the challenges are drawn: bellpepper/r1cs.rs:443-461)
-    if (d.num_challenges == 0) put(d.num_shared + d.num_precommitted, d.num_shared_unpadded + d.num_precommitted_unpadded, d.num_rest_unpadded);
+    fill_W(ps->W);
     phase(0);
     const size_t CW = DEFAULT_COMMITMENT_WIDTH;
     ps->rows_shared = d.num_shared_unpadded ? (d.num_shared + CW - 1) / CW : 0;
@@ -246,6 +243,40 @@ SpartanPrepSNARK* prep_prove(const SpartanProverKey& pk, const uint64_t* witness
     delete ps;
     throw;
   }
+  return ps;
+}
+
+SpartanPrepSNARK* prep_prove(const SpartanProverKey& pk, const uint64_t* witness_u64, size_t n_witness, bool is_small, Tape& tape) {
+  const sp_dims& d = pk.dims;
+  if (n_witness != d.num_shared_unpadded + d.num_precommitted_unpadded + d.num_rest_unpadded) throw Error(SP_ERR_INVALID_WITNESS_LENGTH, "InvalidWitnessLength");
+  sp_ctx* ctx = pk.ctx;
+  return prep_prove_from(pk, is_small, tape, [&](sp_table* W) {
+    auto put = [&](size_t dst, size_t src, size_t cnt) { ck(sp_table_write_u64(ctx, W, dst, witness_u64 + src, cnt), "upload W"); };
+    put(0, 0, d.num_shared_unpadded);
+    put(d.num_shared, d.num_shared_unpadded, d.num_precommitted_unpadded);
+    // (with verifier challenges the rest segment is synthesized inside every prove, after the challenges are drawn: bellpepper/r1cs.rs:443-461)
+    if (d.num_challenges == 0) put(d.num_shared + d.num_precommitted, d.num_shared_unpadded + d.num_precommitted_unpadded, d.num_rest_unpadded);
+  });
+}
+
+// prep_prove for Sha256Circuit (benches/sha256_spartan.rs:78-136) with the witness generated on the device: the reference's prep_prove INCLUDES witness
+// synthesis (src/spartan.rs:176-216 -> precommitted_witness, bellpepper/r1cs.rs:359-409); here it is sp_sha256_witness on a plan made once per key.
+// The key is a sha256_spartan_circuit key (everything precommitted, 256 public digest bits) for the plan's message length; one key serves every message
+// of that length. out_publics: the 256 digest bits in the order the circuit allocates them (big-endian bit order), from the host's SHA-256.
+SpartanPrepSNARK* prep_prove_sha256(const SpartanProverKey& pk, const sp_sha256_plan* plan, const uint8_t* msg, size_t len, bool is_small, Tape& tape, uint64_t out_publics[256]) {
+  const sp_dims& d = pk.dims;
+  uint64_t info[5];
+  ck(sp_sha256_plan_info(plan, info), "plan info");
+  if (d.num_shared_unpadded != 0 || d.num_rest_unpadded != 0 || d.num_challenges != 0 || info[0] != d.num_precommitted_unpadded)
+    throw Error(SP_ERR_INVALID_WITNESS_LENGTH, "InvalidWitnessLength: the plan's variable count is not the key's");
+  if (len != info[3] || !info[4] || d.num_public != 256) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "the plan does not serve this message length / this key is not a SHA-256 digest circuit");
+  sp_ctx* ctx = pk.ctx;
+  uint8_t digest[32];
+  SpartanPrepSNARK* ps = prep_prove_from(pk, is_small, tape, [&](sp_table* W) {
+    sp_table* tabs[1] = {W};
+    ck(sp_sha256_witness(ctx, plan, msg, len, 1, tabs, d.num_shared, digest), "sha256 witness");
+  });
+  for (int i = 0; i < 256; ++i) out_publics[i] = (digest[i / 8] >> (7 - i % 8)) & 1u;
   return ps;
 }
 
@@ -1420,6 +1451,18 @@ int ss_prep_prove(void* pk, const uint64_t* witness_u64, size_t n, int is_small,
   try {
     Tape t{tape, tape_blocks};
     *out_ps = prep_prove(*(SpartanProverKey*)pk, witness_u64, n, is_small != 0, t);
+    if (tape_used) *tape_used = t.pos;
+    return 0;
+  } catch (...) {
+    return catch_all();
+  }
+}
+// prep_prove with the SHA-256 witness generated on the device (see prep_prove_sha256): out_publics = the 256 digest bits to hand to ss_prove
+int ss_prep_prove_sha256(void* pk, const sp_sha256_plan* plan, const uint8_t* msg, size_t len, int is_small, const uint8_t* tape, size_t tape_blocks, size_t* tape_used,
+                         void** out_ps, uint64_t out_publics[256]) {
+  try {
+    Tape t{tape, tape_blocks};
+    *out_ps = prep_prove_sha256(*(SpartanProverKey*)pk, plan, msg, len, is_small != 0, t, out_publics);
     if (tape_used) *tape_used = t.pos;
     return 0;
   } catch (...) {

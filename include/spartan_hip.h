@@ -36,6 +36,7 @@ extern "C" {
 #define SP_ERR_DIVISION_BY_ZERO (-3)     /* SpartanError::DivisionByZero       */
 #define SP_ERR_INTERNAL_TRANSCRIPT (-4)  /* SpartanError::InternalTranscriptError */
 #define SP_ERR_INTERNAL (-5)             /* SpartanError::InternalError        */
+#define SP_ERR_UNSAT (-6)                /* SpartanError::UnSat { reason }     */
 #define SP_ERR_NO_DEVICE (-100)          /* no usable gfx950 device / HIP failure */
 
 typedef struct sp_ctx sp_ctx;               /* one device + stream + scratch */
@@ -266,6 +267,27 @@ int sp_multiply_vec_incremental_round0(sp_ctx* ctx, const sp_shape* s, const sp_
 /* SplitR1CSShape::bind_and_prepare_poly_ABC[_full] (:1235-1321): out[col] = sum_row rx[row] (A + r B + r^2 C)[row,col],
  * written into the first out_len elements of `out` */
 int sp_poly_abc(sp_ctx* ctx, const sp_shape* s, const sp_table* rx, const uint64_t r[4], size_t out_len, sp_table* out);
+
+/* R1CSShape::is_sat / is_sat_relaxed (src/r1cs/mod.rs:358-394, :430-471): the witness checked against the constraints ON THE DEVICE - the drivers never
+ * hold W on the host once witnesses are generated there. The entry points return SP_OK whenever the check itself RAN; whether the instance is satisfied
+ * is read from the report (a driver turns a finding into SP_ERR_UNSAT). `first` = the num_listed = min(16, num_failing) smallest failing row indices,
+ * ascending, read off a failure bitmap that is fetched only when num_failing > 0. Rows are those of the PADDED shape; padding only appends empty rows
+ * (src/r1cs/mod.rs:871-880), so an index below num_cons_unpadded is the caller's own constraint number. */
+typedef struct sp_sat_report {
+  uint64_t num_failing;
+  uint64_t num_listed;
+  uint64_t first[16];
+} sp_sat_report;
+/* the row check alone: row i < n fails when az[i] * bz[i] - u * cz[i] - E[i] != 0 (u == NULL: 1, E == NULL: 0 - the plain check of :375; both given: the
+ * relaxed one of :444). Any n >= 1; a table shorter than n fails with SP_ERR_INVALID_INPUT_LENGTH. One streaming launch and one copy of two words. */
+int sp_r1cs_residual(sp_ctx* ctx, const sp_table* az, const sp_table* bz, const sp_table* cz, const uint64_t* u, const sp_table* E, size_t n, sp_sat_report* out);
+/* the same for `count` instances of equal n in one launch (the step instances of NeutronNova, src/neutronnova_zk.rs:1487-1518): arrays of `count` tables
+ * and `count` reports; u = count x 4 words or NULL, E = `count` tables or NULL */
+int sp_r1cs_residual_batched(sp_ctx* ctx, const sp_table* const* az, const sp_table* const* bz, const sp_table* const* cz, const uint64_t* u, const sp_table* const* E,
+                             size_t count, size_t n, sp_sat_report* out);
+/* is_sat's `res_eq` (:367-376; relaxed :440-445): sp_multiply_vec into scratch the context keeps (grow-only), then the row check over num_cons rows.
+ * z = [W | 1 or u | X] has num_vars + 1 + num_public + num_challenges elements, otherwise SP_ERR_INVALID_WITNESS_LENGTH as multiply_vec (:412-414). */
+int sp_shape_is_sat(sp_ctx* ctx, const sp_shape* s, const sp_table* z, const uint64_t* u, const sp_table* E, sp_sat_report* out);
 
 /* ---- group / MSM (src/provider/traits.rs:118-162 DlogGroupExt, src/provider/msm.rs) --------------------- */
 /* DlogGroupExt::vartime_multiscalar_mul (msm.rs:187-222): sum s_i * g_i. scalars / bases on the host. Below 4096 points the one-block-per-window

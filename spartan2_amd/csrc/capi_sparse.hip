@@ -4,6 +4,7 @@
 //   k_polyabc*  K7     bind_and_prepare_poly_ABC / accumulate_rows (src/r1cs/mod.rs:1235-1398) as a column-major GATHER
 //                      (no 256-bit atomics): short columns one lane each, long columns (the constant-1 column of the
 //                      booleanity rows) one block each.
+//   k_r1cs_residual    R1CSShape::is_sat / is_sat_relaxed (src/r1cs/mod.rs:358-394, :430-471): the row check behind multiply_vec (kernels_sat.hpp)
 // Entries keep the reference's classes: +-1 and |k| in 2..7 as an int8 code (add / sub / double-add chains, sparse.rs:137-155),
 // everything else as a full field coefficient.
 #include <algorithm>
@@ -12,6 +13,7 @@
 
 #include "core.hpp"
 #include "device_utils.hpp"
+#include "kernels_sat.hpp"
 
 using sp::fail;
 typedef FqP S;
@@ -623,6 +625,96 @@ int sp_poly_abc(sp_ctx* c, const sp_shape* s, const sp_table* rx, const uint64_t
                        s->n_short, out->d, s->d_long_cols, (unsigned)s->n_long_cols, partials, tickets, (unsigned)blocks, (size_t)s->num_cols, zero_n, s->col_permuted ? 1 : 0);
   });
   return SP_OK;
+}
+
+// ---- is_sat / is_sat_relaxed (src/r1cs/mod.rs:358-394, :430-471) -----------------------------------------------------------------------------------
+// The residual pass over `count` instances of n rows each: bitmaps and (count, first) pairs in the context's workspaces, one launch per SAT_BATCH
+// instances, then an ordinary copy of the pairs; a bitmap is fetched only for an instance with failing rows, from the word of its first one on.
+static int residual_run(sp_ctx* c, const sp_table* const* az, const sp_table* const* bz, const sp_table* const* cz, const uint64_t* u, const sp_table* const* E,
+                        size_t count, size_t n, sp_sat_report* out) {
+  if (!out || (count && (!az || !bz || !cz))) return fail(SP_ERR_INVALID_INPUT_LENGTH, "r1cs_residual: null argument");
+  if (n < 1) return fail(SP_ERR_INVALID_INPUT_LENGTH, "r1cs_residual: n must be at least 1");
+  for (size_t k = 0; k < count; ++k) {
+    if (!az[k] || !bz[k] || !cz[k] || (E && !E[k])) return fail(SP_ERR_INVALID_INPUT_LENGTH, "r1cs_residual: null table");
+    if (az[k]->len < n || bz[k]->len < n || cz[k]->len < n || (E && E[k]->len < n)) return fail(SP_ERR_INVALID_INPUT_LENGTH, "r1cs_residual: a table is shorter than n");
+  }
+  if (count == 0) return SP_OK;
+  const size_t words = (n + 63) / 64;
+  unsigned long long* bitmap = (unsigned long long*)c->workspace(sp_ctx::WS_SAT_BITMAP, count * words * 8);
+  unsigned long long* summary = (unsigned long long*)c->workspace(sp_ctx::WS_SAT_SUMMARY, 2 * count * 8);  // counts, then first indices
+  if (!bitmap || !summary) return SP_ERR_NO_DEVICE;
+  SP_HIP(hipMemsetAsync(summary, 0, count * 8, c->stream));
+  SP_HIP(hipMemsetAsync(summary + count, 0xff, count * 8, c->stream));
+  size_t blocks = (n + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  for (size_t k0 = 0; k0 < count; k0 += spk::SAT_BATCH) {
+    const size_t nb = std::min<size_t>(spk::SAT_BATCH, count - k0);
+    spk::SatArgs a;
+    memset(&a, 0, sizeof a);
+    for (size_t j = 0; j < nb; ++j) {
+      const size_t k = k0 + j;
+      spk::SatInst& in = a.inst[j];
+      in.az = az[k]->d;
+      in.bz = bz[k]->d;
+      in.cz = cz[k]->d;
+      in.E = E ? E[k]->d : nullptr;
+      if (u) memcpy(&in.u, u + 4 * k, 32);
+      in.bitmap = bitmap + k * words;
+      in.count = summary + k;
+      in.first = summary + count + k;
+    }
+    const uint64_t bytes = (uint64_t)nb * ((E ? 128ull : 96ull) * n + 8ull * words);
+    const dim3 grid((unsigned)blocks, (unsigned)nb), block(256);
+    if (u && E) c->timed_kernel("r1cs_residual", bytes, spk::k_r1cs_residual<true, true>, grid, block, a, n);
+    else if (u) c->timed_kernel("r1cs_residual", bytes, spk::k_r1cs_residual<true, false>, grid, block, a, n);
+    else if (E) c->timed_kernel("r1cs_residual", bytes, spk::k_r1cs_residual<false, true>, grid, block, a, n);
+    else c->timed_kernel("r1cs_residual", bytes, spk::k_r1cs_residual<false, false>, grid, block, a, n);
+  }
+  std::vector<unsigned long long> sum(2 * count);
+  SP_HIP(hipMemcpyAsync(sum.data(), summary, 2 * count * 8, hipMemcpyDeviceToHost, c->stream));
+  SP_HIP(sp::stream_sync(c->stream));
+  std::vector<unsigned long long> chunk;
+  for (size_t k = 0; k < count; ++k) {
+    sp_sat_report& r = out[k];
+    memset(&r, 0, sizeof r);
+    r.num_failing = sum[k];
+    if (!r.num_failing) continue;
+    const uint64_t want = r.num_failing < 16 ? r.num_failing : 16;
+    for (size_t w = (size_t)(sum[count + k] >> 6); w < words && r.num_listed < want;) {
+      const size_t take = std::min<size_t>(4096, words - w);
+      chunk.resize(take);
+      SP_HIP(hipMemcpy(chunk.data(), bitmap + k * words + w, take * 8, hipMemcpyDeviceToHost));
+      for (size_t i = 0; i < take && r.num_listed < want; ++i)
+        for (unsigned long long m = chunk[i]; m && r.num_listed < want; m &= m - 1) r.first[r.num_listed++] = 64 * (uint64_t)(w + i) + (uint64_t)(__builtin_ffsll((long long)m) - 1);
+      w += take;
+    }
+  }
+  return SP_OK;
+}
+
+int sp_r1cs_residual(sp_ctx* c, const sp_table* az, const sp_table* bz, const sp_table* cz, const uint64_t* u, const sp_table* E, size_t n, sp_sat_report* out) {
+  return residual_run(c, &az, &bz, &cz, u, E ? &E : nullptr, 1, n, out);
+}
+int sp_r1cs_residual_batched(sp_ctx* c, const sp_table* const* az, const sp_table* const* bz, const sp_table* const* cz, const uint64_t* u, const sp_table* const* E,
+                             size_t count, size_t n, sp_sat_report* out) {
+  return residual_run(c, az, bz, cz, u, E, count, n, out);
+}
+int sp_shape_is_sat(sp_ctx* c, const sp_shape* s, const sp_table* z, const uint64_t* u, const sp_table* E, sp_sat_report* out) {
+  if (!s || !z || !out) return fail(SP_ERR_INVALID_INPUT_LENGTH, "shape_is_sat: null argument");
+  const size_t nrows = s->dims.num_cons;
+  if (z->len != s->num_cols) return fail(SP_ERR_INVALID_WITNESS_LENGTH, "shape_is_sat: z has the wrong length");
+  fe_t* prod = (fe_t*)c->workspace(sp_ctx::WS_SAT_PRODUCTS, 3 * nrows * sizeof(fe_t));
+  if (!prod) return SP_ERR_NO_DEVICE;
+  sp_table t[3];
+  for (int m = 0; m < 3; ++m) {
+    t[m].ctx = c;
+    t[m].d = prod + (size_t)m * nrows;
+    t[m].cap = t[m].len = nrows;
+    t[m].view = true;
+  }
+  int rc = sp_multiply_vec(c, s, z, &t[0], &t[1], &t[2]);
+  if (rc) return rc;
+  return sp_r1cs_residual(c, &t[0], &t[1], &t[2], u, E, nrows, out);
 }
 
 }  // extern "C"

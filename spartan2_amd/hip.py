@@ -740,6 +740,14 @@ class Shape:
     def multiply_vec_incremental(self, z, caz, cbz, ccz, az, bz, cz):
         check(lib().sp_multiply_vec_incremental(self.ctx.h, self.h, z.h, caz.h, cbz.h, ccz.h, az.h, bz.h, cz.h))
 
+    def is_sat(self, z: Table, u=None, E: Table = None) -> "SatReport":
+        """R1CSShape::is_sat / is_sat_relaxed's row check (src/r1cs/mod.rs:367-376, :440-445) for z = [W | 1 or u | X] resident on the device: the products into
+        scratch the context keeps, then r1cs_residual over num_cons rows. A z of the wrong length raises (rc = -2, InvalidWitnessLength)."""
+        uu = _u_arg(u)
+        rep = _SatReport()
+        check(lib().sp_shape_is_sat(self.ctx.h, self.h, z.h, p64(uu) if uu is not None else None, E.h if E is not None else None, ctypes.byref(rep)))
+        return SatReport(rep)
+
     def poly_abc(self, rx: Table, r, out_len, out: Table):
         r = np.ascontiguousarray(r, dtype=np.uint64).reshape(4)
         check(lib().sp_poly_abc(self.ctx.h, self.h, rx.h, p64(r), ctypes.c_size_t(out_len), out.h))
@@ -750,6 +758,55 @@ class Shape:
                 lib().sp_shape_free(self.h)
         except Exception:
             pass
+
+
+class _SatReport(ctypes.Structure):  # sp_sat_report
+    _fields_ = [("num_failing", ctypes.c_uint64), ("num_listed", ctypes.c_uint64), ("first", ctypes.c_uint64 * 16)]
+
+
+REASON_UNSAT = "R1CS is unsatisfiable"  # SpartanError::UnSat reasons (src/r1cs/mod.rs:381-391)
+REASON_COMMITMENT = "Invalid commitment"
+
+
+class SatReport:
+    """What is_sat found (R1CSShape::is_sat, src/r1cs/mod.rs:358-394): ok, reason (None or the reference's UnSat reason), num_failing rows of the padded
+    shape, first_failing = the (at most 16) smallest failing row indices, bad_commitment_rows = committed rows that are not the commitment of the witness."""
+
+    def __init__(self, raw: _SatReport, bad_commitment_rows=()):
+        self.num_failing = int(raw.num_failing)
+        self.first_failing = [int(raw.first[i]) for i in range(int(raw.num_listed))]
+        self.bad_commitment_rows = [int(r) for r in bad_commitment_rows]
+        self.reason = REASON_UNSAT if self.num_failing else (REASON_COMMITMENT if self.bad_commitment_rows else None)
+        self.ok = self.reason is None
+
+    def __repr__(self):
+        return f"SatReport(ok={self.ok}, reason={self.reason!r}, num_failing={self.num_failing}, first_failing={self.first_failing}, bad_commitment_rows={self.bad_commitment_rows})"
+
+
+def _u_arg(u):
+    return None if u is None else np.ascontiguousarray(u, dtype=np.uint64).reshape(4)
+
+
+def r1cs_residual(ctx, az: Table, bz: Table, cz: Table, u=None, E: Table = None, n=None) -> SatReport:
+    """The row check of is_sat / is_sat_relaxed (src/r1cs/mod.rs:375, :444) on resident products: row i < n fails when az[i] bz[i] - u cz[i] - E[i] != 0
+    (u None = 1, E None = 0). n defaults to len(az)."""
+    n = len(az) if n is None else int(n)
+    uu = _u_arg(u)
+    rep = _SatReport()
+    check(lib().sp_r1cs_residual(ctx.h, az.h, bz.h, cz.h, p64(uu) if uu is not None else None, E.h if E is not None else None, ctypes.c_size_t(n), ctypes.byref(rep)))
+    return SatReport(rep)
+
+
+def r1cs_residual_batched(ctx, azs, bzs, czs, us=None, Es=None, n=None):
+    """r1cs_residual for several instances of equal n in one launch: lists of tables (us: (count, 4) or None) -> list of SatReport."""
+    cnt = len(azs)
+    n = len(azs[0]) if n is None else int(n)
+    arr = lambda ts: (ctypes.c_void_p * cnt)(*[t.h for t in ts])
+    uu = None if us is None else np.ascontiguousarray(us, dtype=np.uint64).reshape(cnt, 4)
+    reps = (_SatReport * cnt)()
+    check(lib().sp_r1cs_residual_batched(ctx.h, arr(azs), arr(bzs), arr(czs), p64(uu) if uu is not None else None, arr(Es) if Es is not None else None, ctypes.c_size_t(cnt),
+                                         ctypes.c_size_t(n), reps))
+    return [SatReport(r) for r in reps]
 
 
 # ---- NeutronNova kernel-level rows ------------------------------------------------------------------------------------------

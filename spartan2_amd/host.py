@@ -90,6 +90,7 @@ def from_label(label: bytes, n: int):
 
 
 REST_HOOK = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, hip.c_u64p, ctypes.c_size_t, hip.c_u64p)
+SP_ERR_UNSAT = -6  # SpartanError::UnSat: what ss_prep_is_sat / nnz_prep_is_sat return for a finding (the reason is in the report)
 PHASES = ("witness_commit", "matrix_vector_multiply", "outer_sumcheck", "prepare_poly_ABC", "inner_sumcheck", "pcs_prove", "total")
 
 
@@ -178,6 +179,26 @@ class SpartanSNARK:
         _check(lib().ss_prep_export(self.pk, self.ps, hip.p64(comm) if rows else None, hip.p64(caz), hip.p64(cbz), hip.p64(ccz)))
         return comm, caz, cbz, ccz
 
+    def _rest_hook(self, synthesize):
+        """the circuit's synthesize callback (challenges (k, 4) -> rest witness (num_rest_unpadded, 4)) behind the C hook type prove and is_sat take"""
+        if synthesize is None:
+            return None
+        nrest = self.dims["num_rest_unpadded"]
+
+        def raw(_user, ch_ptr, nch, out_ptr):
+            try:
+                ch = np.ctypeslib.as_array(ch_ptr, shape=(4 * nch,)).reshape(nch, 4).copy()
+                rest = np.ascontiguousarray(synthesize(ch), dtype=np.uint64).reshape(nrest, 4)
+                np.ctypeslib.as_array(out_ptr, shape=(4 * max(nrest, 1),))[: 4 * nrest] = rest.reshape(-1)
+                return 0
+            except Exception:  # noqa: BLE001
+                import traceback
+
+                traceback.print_exc()
+                return 1
+
+        return REST_HOOK(raw)
+
     def prove(self, tape: np.ndarray, synthesize=None):
         """Returns (proof words in the canonical layout, tape blocks used, {phase: ms}). Circuits with verifier challenges pass
         synthesize(challenges (k, 4)) -> rest witness (num_rest_unpadded, 4) Montgomery limbs (circuit.synthesize, bellpepper/r1cs.rs:443-461)."""
@@ -186,26 +207,41 @@ class SpartanSNARK:
         used = ctypes.c_size_t(0)
         ms = (ctypes.c_double * 7)()
         pub = self.publics
-        cb = None
-        if synthesize is not None:
-            nrest = self.dims["num_rest_unpadded"]
-
-            def raw(_user, ch_ptr, nch, out_ptr):
-                try:
-                    ch = np.ctypeslib.as_array(ch_ptr, shape=(4 * nch,)).reshape(nch, 4).copy()
-                    rest = np.ascontiguousarray(synthesize(ch), dtype=np.uint64).reshape(nrest, 4)
-                    np.ctypeslib.as_array(out_ptr, shape=(4 * max(nrest, 1),))[: 4 * nrest] = rest.reshape(-1)
-                    return 0
-                except Exception:  # noqa: BLE001
-                    import traceback
-
-                    traceback.print_exc()
-                    return 1
-
-            cb = REST_HOOK(raw)
+        cb = self._rest_hook(synthesize)
         _check(lib().ss_prove_hook(self.pk, self.ps, hip.p64(pub) if len(pub) else None, ctypes.c_size_t(len(pub)), hip.p8(tape), ctypes.c_size_t(tape.shape[0]),
                                    ctypes.byref(used), hip.p64(words), ctypes.c_size_t(n), ms, cb, None))
         return words, used.value, dict(zip(PHASES, list(ms)))
+
+    def is_sat(self, publics=None, challenges=None, synthesize=None, commitment=None) -> hip.SatReport:
+        """R1CSShape::is_sat (src/r1cs/mod.rs:358-394) on the prepared state, on the device: does the witness the state holds satisfy the circuit for these
+        public values (default: self.publics - after prep_prove_sha256 the digest bits of that message), and are the rows committed at prep_prove the
+        commitment of that witness? Circuits with verifier challenges pass challenges (k, 4) - a prove's, or any - and the synthesize callback prove takes.
+        commitment: (rows, 8) affine rows to compare with instead of the state's own (prep_export()[0] has that layout). A finding is the returned
+        SatReport, not an exception; a later prove() on the state is unaffected."""
+        if not self.ps:
+            raise hip.SpartanHipError("is_sat before prep_prove")
+        pub = self.publics if publics is None else np.ascontiguousarray(publics, dtype=np.uint64).reshape(-1)
+        cb = self._rest_hook(synthesize)
+        ch = None
+        if challenges is not None:
+            ch = np.ascontiguousarray(challenges, dtype=np.uint64).reshape(-1, 4)
+            if ch.shape[0] != self.dims["num_challenges"]:
+                raise hip.SpartanHipError(f"is_sat: {ch.shape[0]} challenges for a circuit with {self.dims['num_challenges']}")
+        d = self.dims
+        rows = ((d["num_shared"] + 2047) // 2048 if d["num_shared_unpadded"] else 0) + ((d["num_precommitted"] + 2047) // 2048 if d["num_precommitted_unpadded"] else 0)
+        comm = None
+        if commitment is not None:
+            comm = np.ascontiguousarray(commitment, dtype=np.uint64).reshape(-1, 8)
+            if comm.shape[0] != rows:
+                raise hip.SpartanHipError(f"is_sat: {comm.shape[0]} commitment rows, the state holds {rows}")
+        rep = hip._SatReport()
+        bad = np.zeros(max(rows, 1), dtype=np.uint64)
+        nbad = ctypes.c_size_t(0)
+        rc = lib().ss_prep_is_sat(self.pk, self.ps, hip.p64(pub) if len(pub) else None, ctypes.c_size_t(len(pub)), hip.p64(ch) if ch is not None and len(ch) else None, cb,
+                                  None, hip.p64(comm) if comm is not None and rows else None, ctypes.byref(rep), hip.p64(bad), ctypes.c_size_t(len(bad)), ctypes.byref(nbad))
+        if rc not in (0, SP_ERR_UNSAT):
+            _check(rc)
+        return hip.SatReport(rep, bad[: nbad.value])
 
     def verify(self, words: np.ndarray) -> int:
         """SpartanSNARK::verify (src/spartan.rs:469-578) with the matrix evaluations and MSMs on the device: 0 = accept, 1..6 = failed check."""
@@ -589,6 +625,27 @@ class NeutronNovaZkSNARK:
         fn = lib().nnz_prove_reference_order if reference_order else lib().nnz_prove
         _check(fn(self.pk, self.ps, hip.p8(tape), ctypes.c_size_t(tape.shape[0]), ctypes.byref(used), hip.p64(words), ctypes.c_size_t(n), ms))
         return words, used.value, dict(zip(NN_PHASES, list(ms)))
+
+    def is_sat(self):
+        """R1CSShape::is_sat (src/r1cs/mod.rs:358-394) of every instance the prepared state holds, on the device: a list of hip.SatReport, the step instances
+        (against S_step, one batched launch), then the core instance (against S_core); bad_commitment_rows counts over an instance's [shared | precommitted]
+        rows. A finding is a return value; a later prove() on the state is unaffected."""
+        if not self.ps:
+            raise hip.SpartanHipError("is_sat before prep_prove")
+        n = len(self.steps) + 1
+        reps = (hip._SatReport * n)()
+        cap = 1024
+        while True:  # (instance, row) pairs; a list longer than the buffer is asked for again with room for all of it
+            bad = np.zeros((cap, 2), dtype=np.uint64)
+            nbad = ctypes.c_size_t(0)
+            rc = lib().nnz_prep_is_sat(self.pk, self.ps, reps, hip.p64(bad), ctypes.c_size_t(cap), ctypes.byref(nbad))
+            if rc not in (0, SP_ERR_UNSAT):
+                _check(rc)
+            if nbad.value <= cap:
+                break
+            cap = nbad.value
+        pairs = bad[: nbad.value]
+        return [hip.SatReport(reps[i], [int(r) for k, r in pairs if int(k) == i]) for i in range(n)]
 
     def verify(self, words: np.ndarray) -> int:
         """NeutronNovaZkSNARK::verify (src/neutronnova_zk.rs:2096-2343) with the commitment fold, the six matrix evaluations and the opening's MSMs on the

@@ -1766,6 +1766,74 @@ static int nn_verify(const NNZkKey& pk, const uint64_t* words, size_t nwords) {
   return 0;
 }
 
+// ---- R1CSShape::is_sat (src/r1cs/mod.rs:358-394) on every instance of a prepared state ---------------------------------------------------------------
+// Each step instance against S_step - z_i = [W_i | 1 | X_i] (src/neutronnova_zk.rs:1487-1518), the products through sp_multiply_vec_batched and the row
+// check of all steps in one launch (sp_r1cs_residual_batched) - and the core instance against S_core; then `res_comm` (:379) per instance: PCS::commit of
+// its shared and its precommitted rows with the stored blinds, compared with comm_shared / comm_pre. reports: the steps, then the core. bad: (instance, row)
+// pairs, row counted over the instance's [shared | precommitted] rows. The verifier-circuit and folded instances are host-side and tiny: not checked here.
+// Works on tables of its own (freed on return): nothing a later prove reads is written.
+static bool nn_is_sat(const NNZkKey& pk, NNZkPrep& ps, sp_sat_report* reports, std::vector<uint64_t>* bad, const char** reason) {
+  sp_ctx* ctx = pk.ctx;
+  const size_t n = ps.steps.size();
+  struct Tabs {
+    std::vector<sp_table*> v;
+    ~Tabs() {
+      for (sp_table* t : v) sp_table_free(t);
+    }
+    sp_table* zeros(sp_ctx* c, size_t len) {
+      sp_table* t = nullptr;
+      ck(sp_table_zeros(c, len, (size_t)-1, (size_t)-1, &t), "alloc (is_sat)");
+      v.push_back(t);
+      return t;
+    }
+  } tabs;
+  auto make_z = [&](const sp_dims& dd, const NNPre& p) {
+    const size_t M = dd.num_shared + dd.num_precommitted + dd.num_rest;
+    sp_table* z = tabs.zeros(ctx, M + 1 + dd.num_public);
+    ck(sp_table_copy(ctx, z, 0, p.W, 0, M), "z <- W");
+    std::vector<fe_t> tail(1 + dd.num_public);
+    tail[0] = fe_one<S>();
+    std::copy(p.publics.begin(), p.publics.end(), tail.begin() + 1);
+    ck(sp_table_write(ctx, z, M, u64p(tail.data()), tail.size()), "z tail");
+    return z;
+  };
+  const size_t N = pk.dims.num_cons;
+  std::vector<const sp_table*> zs(n), azc(n), bzc(n), czc(n);
+  std::vector<sp_table*> az(n), bz(n), cz(n);
+  for (size_t i = 0; i < n; ++i) {
+    zs[i] = make_z(pk.dims, ps.steps[i]);
+    azc[i] = az[i] = tabs.zeros(ctx, N);
+    bzc[i] = bz[i] = tabs.zeros(ctx, N);
+    czc[i] = cz[i] = tabs.zeros(ctx, N);
+  }
+  ck(sp_multiply_vec_batched(ctx, pk.S_step, zs.data(), n, az.data(), bz.data(), cz.data()), "multiply_vec_batched (is_sat)");
+  ck(sp_r1cs_residual_batched(ctx, azc.data(), bzc.data(), czc.data(), nullptr, nullptr, n, N, reports), "r1cs_residual_batched");
+  ck(sp_shape_is_sat(ctx, pk.S_core, make_z(pk.dims_core, ps.core), nullptr, nullptr, &reports[n]), "shape_is_sat (core)");
+  bad->clear();
+  bool rows_ok = true;
+  *reason = nullptr;
+  for (size_t i = 0; i <= n; ++i) {
+    const sp_dims& dd = i < n ? pk.dims : pk.dims_core;
+    const NNPre& p = i < n ? ps.steps[i] : ps.core;
+    const size_t rows_sh = ps.comm_shared.size(), rows_pre = p.comm_pre.size();
+    std::vector<aff_t> again(rows_sh + rows_pre);
+    if (rows_sh) ck(sp_hyrax_commit(ctx, pk.ck, p.W, 0, dd.num_shared, u64p(ps.r_shared.data()), ps.is_small ? 1 : 0, u64p(&again[0].x)), "commit shared (is_sat)");
+    if (rows_pre)
+      ck(sp_hyrax_commit(ctx, pk.ck, p.W, dd.num_shared, dd.num_precommitted, u64p(p.r_pre.data()), ps.is_small ? 1 : 0, u64p(&again[rows_sh].x)), "commit precommitted (is_sat)");
+    for (size_t r = 0; r < rows_sh + rows_pre; ++r) {
+      const aff_t& want = r < rows_sh ? ps.comm_shared[r] : p.comm_pre[r - rows_sh];
+      if (memcmp(&again[r], &want, sizeof(aff_t)) != 0) {
+        bad->push_back(i);
+        bad->push_back(r);
+        rows_ok = false;
+      }
+    }
+    if (reports[i].num_failing) *reason = "R1CS is unsatisfiable";  // takes precedence (:381-391)
+  }
+  if (!*reason && !rows_ok) *reason = "Invalid commitment";
+  return *reason == nullptr;
+}
+
 }  // namespace spartan2
 
 using namespace spartan2;
@@ -1831,6 +1899,24 @@ int nnz_prep_prove(void* pk, size_t n, const uint64_t* step_wit, size_t wit_len,
   }
 }
 void nnz_prep_free(void* ps) { delete (NNZkPrep*)ps; }
+// is_sat of the step instances and the core instance of a prepared state (nn_is_sat): reports = num_steps + 1 entries, the steps, then the core; bad_rows =
+// (instance, row) pairs of commitment rows that do not match, at most bad_rows_cap pairs of the *n_bad_rows found. 0 = every instance satisfied and committed
+// to; SP_ERR_UNSAT with ss_last_error() = "R1CS is unsatisfiable" (takes precedence) or "Invalid commitment"; another negative value = library error.
+int nnz_prep_is_sat(void* pk, void* ps, sp_sat_report* reports, uint64_t* bad_rows, size_t bad_rows_cap, size_t* n_bad_rows) {
+  try {
+    if (!ps || !reports) throw Error(SP_ERR_INTERNAL, "is_sat before prep_prove");
+    std::vector<uint64_t> bad;
+    const char* reason = nullptr;
+    const bool ok = nn_is_sat(*(NNZkKey*)pk, *(NNZkPrep*)ps, reports, &bad, &reason);
+    if (n_bad_rows) *n_bad_rows = bad.size() / 2;
+    if (bad_rows) std::copy(bad.begin(), bad.begin() + 2 * std::min(bad.size() / 2, bad_rows_cap), bad_rows);
+    if (ok) return 0;
+    ss_set_error(reason);
+    return SP_ERR_UNSAT;
+  } catch (...) {
+    return catch_all_nn();
+  }
+}
 // 0 = accept, 1..6 = the failed check (nn_verify above), < 0 = error
 int nnz_verify(void* pk, const uint64_t* words, size_t nwords) {
   try {

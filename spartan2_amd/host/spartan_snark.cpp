@@ -80,6 +80,7 @@ struct SpartanPrepSNARK {  // src/spartan.rs:107-124
   sp_table *az = nullptr, *bz = nullptr, *cz = nullptr, *z = nullptr;          // scratch reused across prove calls
   sp_table *rx = nullptr, *abc = nullptr;
   sp_table *p0 = nullptr, *p1 = nullptr;  // per-pair products of the outer sum-check's first round (sp_multiply_vec_incremental_round0)
+  sp_table* sat_z = nullptr;              // is_sat's own z = [W | 1 | X]: allocated by the first check on the state; no prove reads or writes it
   std::vector<aff_t> comm_W_fixed;  // rows committed at prep time: shared rows, then precommitted rows
   std::vector<fe_t> r_W_fixed;      // their blinds, same order
   size_t rows_shared = 0, rows_precommitted = 0;
@@ -117,7 +118,7 @@ struct SpartanPrepSNARK {  // src/spartan.rs:107-124
     sp_points_free(comm_pts);
     sp_absorb_state_free(poly_com);
     sp_transcript_free(tr_prefix);
-    for (sp_table* t : {W, caz, cbz, ccz, az, bz, cz, z, rx, abc, p0, p1}) sp_table_free(t);
+    for (sp_table* t : {W, caz, cbz, ccz, az, bz, cz, z, rx, abc, p0, p1, sat_z}) sp_table_free(t);
   }
 };
 
@@ -1214,6 +1215,49 @@ SpartanProofBuf prove_reference_order(const SpartanProverKey& pk, SpartanPrepSNA
   return proof;
 }
 
+// ---- R1CSShape::is_sat (src/r1cs/mod.rs:358-394) on a prepared state ----------------------------------------------------------------------------
+// z = [W | 1 | X] formed as prove forms it (src/spartan.rs:246-253) but in a table of its own, the row check on the device (sp_shape_is_sat), then
+// `res_comm` (:379): PCS::commit of the rows committed at prep_prove - shared, then precommitted - with the stored blinds and the state's is_small,
+// compared with comm_W_fixed (or with `expect_comm`, the same number of rows, when the caller holds the commitment it wants checked). For circuits with
+// verifier challenges the caller supplies them - its last prove's, or any: the constraints hold for every challenge - and the rest witness comes
+// through the hook prove takes. Nothing a later prove reads is written: W, the cached products, the working tables and the randomness tape are left alone.
+// Returns true when both checks hold; *reason = the reference's reason string otherwise ("R1CS is unsatisfiable" first, :381-391).
+bool is_sat(const SpartanProverKey& pk, SpartanPrepSNARK& ps, const uint64_t* publics_u64, size_t npub, const uint64_t* challenges, ss_rest_hook synth, void* synth_user,
+            const uint64_t* expect_comm, sp_sat_report* report, std::vector<uint64_t>* bad_rows, const char** reason) {
+  const sp_dims& d = pk.dims;
+  sp_ctx* ctx = pk.ctx;
+  const size_t M = pk.num_vars, fixed = d.num_shared + d.num_precommitted;
+  if (npub != d.num_public) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "public_values length");
+  if (d.num_challenges && (!challenges || !synth)) throw Error(SP_ERR_INTERNAL, "a circuit with verifier challenges needs its challenges and its synthesize callback");
+  ck(sp_ctx_bind_thread(ctx), "device");
+  if (!ps.sat_z) ck(sp_table_zeros(ctx, pk.num_cols, (size_t)-1, (size_t)-1, &ps.sat_z), "alloc z (is_sat)");
+  ck(sp_table_copy(ctx, ps.sat_z, 0, ps.W, 0, M), "z <- W");
+  if (d.num_challenges) {  // circuit.synthesize(.., Some(&challenges)) (bellpepper/r1cs.rs:443-461); the rest segment goes into z, not into W
+    std::vector<fe_t> rest(d.num_rest_unpadded + 1);
+    if (synth(synth_user, challenges, d.num_challenges, u64p(rest.data())) != 0) throw Error(SP_ERR_INTERNAL, "SynthesisError: the circuit's synthesize callback failed");
+    if (d.num_rest_unpadded) ck(sp_table_write(ctx, ps.sat_z, fixed, u64p(rest.data()), d.num_rest_unpadded), "z rest");
+  }
+  std::vector<fe_t> tail(pk.num_extra);
+  tail[0] = fe_one<S>();
+  for (size_t i = 0; i < npub; ++i) tail[1 + i] = fe_from_u64<S>(publics_u64[i]);
+  if (d.num_challenges) memcpy(&tail[1 + npub], challenges, d.num_challenges * sizeof(fe_t));
+  ck(sp_table_write(ctx, ps.sat_z, M, u64p(tail.data()), tail.size()), "z tail");
+  ck(sp_shape_is_sat(ctx, pk.S, ps.sat_z, nullptr, nullptr, report), "shape_is_sat");
+  // res_comm
+  const size_t rows = ps.comm_W_fixed.size();
+  std::vector<aff_t> again(rows);
+  if (ps.rows_shared) ck(sp_hyrax_commit(ctx, pk.ck, ps.W, 0, d.num_shared, u64p(ps.r_W_fixed.data()), ps.is_small ? 1 : 0, u64p(&again[0].x)), "commit shared (is_sat)");
+  if (ps.rows_precommitted)
+    ck(sp_hyrax_commit(ctx, pk.ck, ps.W, d.num_shared, d.num_precommitted, u64p(ps.r_W_fixed.data() + ps.rows_shared), ps.is_small ? 1 : 0, u64p(&again[ps.rows_shared].x)),
+       "commit precommitted (is_sat)");
+  const aff_t* want = expect_comm ? reinterpret_cast<const aff_t*>(expect_comm) : ps.comm_W_fixed.data();
+  bad_rows->clear();
+  for (size_t i = 0; i < rows; ++i)
+    if (memcmp(&again[i], &want[i], sizeof(aff_t)) != 0) bad_rows->push_back(i);
+  *reason = report->num_failing ? "R1CS is unsatisfiable" : (!bad_rows->empty() ? "Invalid commitment" : nullptr);
+  return *reason == nullptr;
+}
+
 // ---- SpartanSNARK::verify (src/spartan.rs:469-578) — SURVEY 8(f) rank 3 ---------------------------------------------------------------
 // The work that scales with the instance runs on the device through the same ABI: the three matrix evaluations A(rx,ry), B, C
 // (`evaluate_with_tables_fast`, src/r1cs/mod.rs:1216-1226) as ONE sp_multiply_vec against the table T_y = eq(r_y) followed by three dot
@@ -1491,6 +1535,27 @@ int ss_prep_export(void* pk_, void* ps_, uint64_t* comm_rows, uint64_t* caz, uin
     if (cbz) ck(sp_table_read(pk->ctx, ps->cbz, 0, N, cbz), "read cbz");
     if (ccz) ck(sp_table_read(pk->ctx, ps->ccz, 0, N, ccz), "read ccz");
     return 0;
+  } catch (...) {
+    return catch_all();
+  }
+}
+// R1CSShape::is_sat on a prepared state (see is_sat): 0 = satisfied and the commitment matches; SP_ERR_UNSAT with ss_last_error() = the reference's reason
+// ("R1CS is unsatisfiable", which takes precedence, or "Invalid commitment"); another negative value = misuse / library error. The report and the list of
+// mismatching commitment rows (at most bad_rows_cap of the *n_bad_rows found; shared rows first) are filled in either case. challenges (num_challenges x 4
+// Montgomery limbs) and synth: circuits with verifier challenges only. expect_comm_rows: NULL = compare with the commitment the state holds.
+int ss_prep_is_sat(void* pk, void* ps, const uint64_t* publics_u64, size_t npub, const uint64_t* challenges, ss_rest_hook synth, void* synth_user,
+                   const uint64_t* expect_comm_rows, sp_sat_report* report, uint64_t* bad_rows, size_t bad_rows_cap, size_t* n_bad_rows) {
+  try {
+    if (!ps) throw Error(SP_ERR_INTERNAL, "is_sat before prep_prove");
+    sp_sat_report local;
+    std::vector<uint64_t> bad;
+    const char* reason = nullptr;
+    const bool ok = is_sat(*(SpartanProverKey*)pk, *(SpartanPrepSNARK*)ps, publics_u64, npub, challenges, synth, synth_user, expect_comm_rows, report ? report : &local, &bad, &reason);
+    if (n_bad_rows) *n_bad_rows = bad.size();
+    if (bad_rows) std::copy(bad.begin(), bad.begin() + std::min(bad.size(), bad_rows_cap), bad_rows);
+    if (ok) return 0;
+    g_err = reason;
+    return SP_ERR_UNSAT;
   } catch (...) {
     return catch_all();
   }

@@ -255,6 +255,15 @@ int sp_multiply_vec(sp_ctx* ctx, const sp_shape* s, const sp_table* z, sp_table*
 /* SplitR1CSShape::multiply_vec_batched (:1130-1166 -> PrecomputedSparseMatrix::multiply_vec_batched, sparse.rs:237-302): the three products for
  * `count` vectors z_k; az / bz / cz are arrays of `count` output tables */
 int sp_multiply_vec_batched(sp_ctx* ctx, const sp_shape* s, const sp_table* const* zs, size_t count, sp_table* const* az, sp_table* const* bz, sp_table* const* cz);
+/* R1CSShape::evaluate_with_tables_fast (src/r1cs/mod.rs:1216-1226; the verifier's call, src/spartan.rs:540-548) for `count` pairs of tables in chunks that
+ * share one walk over A, B, C: out[12 k + 4 m ..] = sum_(row, col) M[row, col] tx[k][row] ty[k][col] for M = A, B, C (m = 0, 1, 2), Montgomery limbs like
+ * every scalar of this ABI. No product table is formed. tx[k] has at least num_cons elements, ty[k] at least num_vars + 1 + num_public + num_challenges
+ * (e.g. eq tables of 2^ell entries); a shorter table is SP_ERR_INVALID_WITNESS_LENGTH as for multiply_vec. count == 0 is a no-op. Returns with `out`
+ * written (the call ends synchronised). */
+/* how many pairs one launch of sp_shape_matrix_evals_batched serves (a compile-time constant of the kernel): a caller that builds its tables chunk by
+ * chunk needs this many (T_x, T_y) pairs alive at a time, whatever the batch */
+size_t sp_shape_matrix_evals_chunk(void);
+int sp_shape_matrix_evals_batched(sp_ctx* ctx, const sp_shape* s, const sp_table* const* tx, const sp_table* const* ty, size_t count, uint64_t* out);
 /* SplitR1CSShape::multiply_vec_incremental_into (:1170-1211) */
 int sp_multiply_vec_incremental(sp_ctx* ctx, const sp_shape* s, const sp_table* z, const sp_table* caz, const sp_table* cbz, const sp_table* ccz,
                                 sp_table* az, sp_table* bz, sp_table* cz);

@@ -4,6 +4,7 @@
 //   k_polyabc*  K7     bind_and_prepare_poly_ABC / accumulate_rows (src/r1cs/mod.rs:1235-1398) as a column-major GATHER
 //                      (no 256-bit atomics): short columns one lane each, long columns (the constant-1 column of the
 //                      booleanity rows) one block each.
+//   k_matrix_evals_batched  evaluate_with_tables_fast (src/r1cs/mod.rs:1216-1226) for a chunk of (T_x, T_y) pairs in one walk (kernels_mateval.hpp)
 //   k_r1cs_residual    R1CSShape::is_sat / is_sat_relaxed (src/r1cs/mod.rs:358-394, :430-471): the row check behind multiply_vec (kernels_sat.hpp)
 // Entries keep the reference's classes: +-1 and |k| in 2..7 as an int8 code (add / sub / double-add chains, sparse.rs:137-155),
 // everything else as a full field coefficient.
@@ -240,6 +241,8 @@ __global__ void __launch_bounds__(256) k_polyabc_short_and_long(PolyAbcArgs a, c
   }
 }
 }  // namespace spk
+
+#include "kernels_mateval.hpp"
 
 // ---- host side: classification and upload ---------------------------------------------------------------------------
 namespace {
@@ -624,6 +627,52 @@ int sp_poly_abc(sp_ctx* c, const sp_shape* s, const sp_table* rx, const uint64_t
     hipLaunchKernelGGL(spk::k_polyabc_short_and_long, dim3((unsigned)(blocks + spk::LONG_NB_MAX * s->n_long_cols + zblocks)), dim3(256), 0, c->stream, a, rx->d, s->d_short_order,
                        s->n_short, out->d, s->d_long_cols, (unsigned)s->n_long_cols, partials, tickets, (unsigned)blocks, (size_t)s->num_cols, zero_n, s->col_permuted ? 1 : 0);
   });
+  return SP_OK;
+}
+
+// evaluate_with_tables_fast (src/r1cs/mod.rs:1216-1226; call site src/spartan.rs:540-548) for `count` pairs of tables: chunks of MATEVAL_KC pairs, one
+// launch each (the structure is read once per chunk), the 3 results of every pair collected on the device and copied out once at the end.
+size_t sp_shape_matrix_evals_chunk(void) { return (size_t)spk::MATEVAL_KC; }
+int sp_shape_matrix_evals_batched(sp_ctx* c, const sp_shape* s, const sp_table* const* tx, const sp_table* const* ty, size_t count, uint64_t* out) {
+  if (!s || (count && (!tx || !ty || !out))) return fail(SP_ERR_INVALID_INPUT_LENGTH, "matrix_evals_batched: null argument");
+  const size_t nrows = s->dims.num_cons;
+  for (size_t k = 0; k < count; ++k) {
+    if (!tx[k] || !ty[k]) return fail(SP_ERR_INVALID_INPUT_LENGTH, "matrix_evals_batched: null table");
+    if (tx[k]->len < nrows) return fail(SP_ERR_INVALID_WITNESS_LENGTH, "matrix_evals_batched: a T_x table has fewer than num_cons elements");
+    if (ty[k]->len < s->num_cols) return fail(SP_ERR_INVALID_WITNESS_LENGTH, "matrix_evals_batched: a T_y table is shorter than z");
+  }
+  if (count == 0) return SP_OK;
+  size_t blocks = (nrows + 255) / 256;
+  if (blocks > spk::MATEVAL_MAX_BLOCKS) blocks = spk::MATEVAL_MAX_BLOCKS;
+  if (blocks == 0) blocks = 1;
+  // the arrival counters first, zeroed in the same breath as they are allocated (every launch leaves them at zero again): a later allocation that fails
+  // must not leave a ticket buffer behind that the next call takes for a used one
+  const bool fresh = c->ws_bytes[sp_ctx::WS_MATEVAL_TICKETS] < 3 * sizeof(unsigned);
+  unsigned* tickets = (unsigned*)c->workspace(sp_ctx::WS_MATEVAL_TICKETS, 3 * sizeof(unsigned));
+  if (!tickets) return SP_ERR_NO_DEVICE;
+  if (fresh) SP_HIP(hipMemsetAsync(tickets, 0, c->ws_bytes[sp_ctx::WS_MATEVAL_TICKETS], c->stream));
+  fe_t* partials = (fe_t*)c->workspace(sp_ctx::WS_MATEVAL_PARTIALS, 3 * (size_t)spk::MATEVAL_MAX_BLOCKS * spk::MATEVAL_KC * sizeof(fe_t));
+  fe_t* d_out = (fe_t*)c->workspace(sp_ctx::WS_MATEVAL_OUT, count * 3 * sizeof(fe_t));
+  if (!partials || !d_out) return SP_ERR_NO_DEVICE;
+  const uint64_t nnz = s->nnz[0] + s->nnz[1] + s->nnz[2];
+  for (size_t k0 = 0; k0 < count; k0 += spk::MATEVAL_KC) {
+    const size_t kc = std::min<size_t>(spk::MATEVAL_KC, count - k0);
+    spk::MatEvalArgs a;
+    for (int m = 0; m < 3; ++m) a.m[m] = s->row[m].view();
+    for (size_t j = 0; j < (size_t)spk::MATEVAL_KC; ++j) {  // (the unused slots of a ragged chunk are never dereferenced)
+      a.tx[j] = tx[k0 + (j < kc ? j : 0)]->d;
+      a.ty[j] = ty[k0 + (j < kc ? j : 0)]->d;
+    }
+    a.partials = partials;
+    a.tickets = tickets;
+    a.out = d_out + 3 * k0;
+    a.kc = (int)kc;
+    // structure once per chunk (4-byte index + code, row pointers of both classes) + one 32-byte gather per entry and pair + T_x once per matrix and pair
+    const uint64_t bytes = 5ull * nnz + 24ull * nrows + kc * (32ull * nnz + 96ull * nrows);
+    c->timed_kernel("matrix_evals_batched", bytes, spk::k_matrix_evals_batched, dim3((unsigned)blocks, 3), dim3(256), a, nrows);
+  }
+  SP_HIP(hipMemcpyAsync(out, d_out, count * 3 * sizeof(fe_t), hipMemcpyDeviceToHost, c->stream));
+  SP_HIP(sp::stream_sync(c->stream));
   return SP_OK;
 }
 

@@ -53,6 +53,12 @@ def lib():
     return _lib
 
 
+def matrix_evals_chunk() -> int:
+    """pairs per launch of sp_shape_matrix_evals_batched (sp_shape_matrix_evals_chunk): where a batch crosses into the next chunk"""
+    lib().sp_shape_matrix_evals_chunk.restype = ctypes.c_size_t
+    return int(lib().sp_shape_matrix_evals_chunk())
+
+
 class SpartanHipError(RuntimeError):
     pass
 
@@ -733,6 +739,16 @@ class Shape:
         n = len(zs)
         arr = lambda ts: (ctypes.c_void_p * n)(*[t.h for t in ts])
         check(lib().sp_multiply_vec_batched(self.ctx.h, self.h, arr(zs), ctypes.c_size_t(n), arr(azs), arr(bzs), arr(czs)))
+
+    def matrix_evals_batched(self, txs, tys) -> np.ndarray:
+        """evaluate_with_tables_fast (src/r1cs/mod.rs:1216-1226) for every pair (txs[k], tys[k]) in chunks that share one walk over A, B, C:
+        -> (len(txs), 3, 4) uint64, the Montgomery limbs of A, B, C per pair. A table shorter than num_cons / the length of z raises (rc = -2)."""
+        n = len(txs)
+        assert len(tys) == n
+        out = np.zeros((n, 3, 4), dtype=np.uint64)
+        arr = lambda ts: (ctypes.c_void_p * max(n, 1))(*[t.h for t in ts])
+        check(lib().sp_shape_matrix_evals_batched(self.ctx.h, self.h, arr(txs), arr(tys), ctypes.c_size_t(n), p64(out) if n else None))
+        return out
 
     def multiply_vec_incremental_round0(self, z, caz, cbz, ccz, az, bz, cz, p0, p1):
         check(lib().sp_multiply_vec_incremental_round0(self.ctx.h, self.h, z.h, caz.h, cbz.h, ccz.h, az.h, bz.h, cz.h, p0.h, p1.h))

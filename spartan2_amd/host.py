@@ -94,6 +94,13 @@ SP_ERR_UNSAT = -6  # SpartanError::UnSat: what ss_prep_is_sat / nnz_prep_is_sat 
 PHASES = ("witness_commit", "matrix_vector_multiply", "outer_sumcheck", "prepare_poly_ABC", "inner_sumcheck", "pcs_prove", "total")
 
 
+class VerifyBatchInfo(ctypes.Structure):  # ss_verify_batch_info
+    _fields_ = [(n, ctypes.c_uint64) for n in ("matrix_chunks", "opening_batched_ok", "fallback_proofs", "opening_proofs")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
 class SpartanSNARK:
     """setup -> prep_prove -> prove, as benches/sha256_spartan.rs:171-243 drives them."""
 
@@ -275,6 +282,40 @@ class SpartanSNARK:
         if rc < 0:
             _check(rc)
         return rc
+
+    def _verify_batch(self, fn, items, lens, keep, seed, info):
+        n = len(lens)  # (items is a ctypes array of at least one slot; keep holds the arrays it points into)
+        npub = self.dims["num_public"]
+        codes = (ctypes.c_int * max(n, 1))()
+        pub = np.zeros((max(n, 1), max(npub, 1), 4), dtype=np.uint64)
+        inf = VerifyBatchInfo()
+        sd = None
+        if seed is not None:
+            sd = np.frombuffer(bytes(seed), dtype=np.uint8).copy()
+            assert sd.shape[0] == 32, "seed must be 32 bytes"
+        _check(fn(self.pk, items, (ctypes.c_size_t * max(n, 1))(*lens), ctypes.c_size_t(n), hip.p8(sd) if sd is not None else None, codes, hip.p64(pub),
+                  ctypes.byref(inf)))
+        out = [int(codes[k]) for k in range(n)]
+        if not info:
+            return out
+        return out, [pub[k, :npub].copy() if out[k] == 0 else None for k in range(n)], inf.as_dict()
+
+    def verify_batch(self, proofs, seed=None, info=False):
+        """verify() for every proof of `proofs` (flat word arrays of this key) in one pass: the matrix evaluations of KC proofs per launch, the openings of
+        all proofs as one random linear combination (spartan_snark.cpp verify_batch). -> the list of verify()'s codes; with info=True
+        (codes, publics, info): publics[k] = the accepted public values or None, info = {matrix_chunks, opening_batched_ok, fallback_proofs,
+        opening_proofs}. seed: 32 bytes mixed into the weights of the combined check, or None. A batch of one is verify() itself."""
+        ws = [np.ascontiguousarray(w, dtype=np.uint64).reshape(-1) for w in proofs]
+        n = len(ws)
+        ptrs = (hip.c_u64p * max(n, 1))(*[hip.p64(w) if w.shape[0] else None for w in ws])
+        return self._verify_batch(lib().ss_verify_batch, ptrs, [w.shape[0] for w in ws], ws, seed, info)
+
+    def verify_bytes_batch(self, blobs, seed=None, info=False):
+        """verify_batch() over serialised proofs (proof_to_bytes): bytes that do not decode to a proof of this key's shape get code 1."""
+        bs = [np.frombuffer(bytes(b), dtype=np.uint8).copy() if len(b) else np.zeros(1, dtype=np.uint8) for b in blobs]
+        n = len(bs)
+        ptrs = (hip.c_u8p * max(n, 1))(*[hip.p8(b) for b in bs])
+        return self._verify_batch(lib().ss_verify_bytes_batch, ptrs, [len(b) for b in blobs], bs, seed, info)
 
     def close(self):
         if self.ps:

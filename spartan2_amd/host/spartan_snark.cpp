@@ -12,7 +12,21 @@
 // Randomness is injected: every blind / mask is the next 64-byte block of a caller-supplied tape reduced with from_uniform,
 // in the reference's call order.
 // Generators: this build's own derivation (the reference's is a third-party hash-to-curve): PARITY UNPINNED, see DESIGN.md.
+#include <future>
+#include <memory>
+
 #include "snark_common.hpp"
+
+// What ss_verify_batch / ss_verify_bytes_batch report beside the codes (C layout: four 64-bit words; host.py VerifyBatchInfo mirrors it). The ss_* surface
+// of this library has no header of its own: its types are declared here, at global scope, as a C caller would repeat them.
+extern "C" {
+typedef struct ss_verify_batch_info {
+  uint64_t matrix_chunks;       // sp_shape_matrix_evals_batched calls
+  uint64_t opening_batched_ok;  // 1: the combined equations held (or no proof reached them)
+  uint64_t fallback_proofs;     // proofs that went through the single-proof opening_check
+  uint64_t opening_proofs;      // proofs that reached the combined equations
+} ss_verify_batch_info;
+}
 
 namespace spartan2 {
 
@@ -28,7 +42,10 @@ struct SpartanProverKey {  // src/spartan.rs:30-58
   // verify()'s device workspaces (T_x, T_y, the three products M T_y): allocated by the first verify on this key and kept - five hipMalloc / hipFree
   // pairs of 32-64 MB were half of a 3.3 ms verify. One verify at a time per key (as for every handle of the ABI).
   mutable sp_table *v_Tx = nullptr, *v_Ty = nullptr, *v_mv[3] = {nullptr, nullptr, nullptr};
+  mutable std::vector<sp_table*> vb_Tx, vb_Ty;  // verify_batch()'s (T_x, T_y) pairs of one chunk, kept like the above
   ~SpartanProverKey() {
+    for (sp_table* t : vb_Tx) sp_table_free(t);
+    for (sp_table* t : vb_Ty) sp_table_free(t);
     sp_table_free(v_Tx);
     sp_table_free(v_Ty);
     for (sp_table* t : v_mv) sp_table_free(t);
@@ -1264,7 +1281,47 @@ bool is_sat(const SpartanProverKey& pk, SpartanPrepSNARK& ps, const uint64_t* pu
 // products with T_x = eq(r_x); comm_LZ = <L, comm rows> (hyrax_pc.rs:480-531) and the IPA check's <z_vec, ck> (ipa.rs:173-221) as device MSMs.
 // The O(log N) parts (transcript, round-polynomial checks, single scalar multiplications) stay on the host. Returns 0 = accept, else the index
 // of the failed check (1 shape, 2 outer sum-check, 3 outer claim, 4 inner sum-check, 5 inner claim, 6 opening) — the oracle's codes.
-int verify(const SpartanProverKey& pk, const uint64_t* words, size_t nwords, uint64_t* out_publics) {
+//
+// The function is three steps, which verify() runs on one proof and verify_batch() on many:
+//   (a) verify_step_a    parse, canonicity and on-curve checks, transcript, both sum-check verifications, eval_Z: checks 1-4 (host only)
+//   (b) verify_step_b    the three matrix evaluations and check 5 (single proof); check5() is the comparison both forms share
+//   (c) opening_prepare_host, opening_comm_LZ, opening_challenge  the opening up to the IPA's challenge r: R and <z_vec, R> (can fail check 6), comm_LZ, comm_eval_W
+//       opening_check    the two group equations of InnerProductArgumentLinear::verify for ONE proof: check 6
+
+// <z_vec, ck> (ipa.rs:196-203) depends on nothing but the proof: verify() starts its device part before the transcript work
+struct ZJob {
+  sp_ctx* ctx = nullptr;
+  const sp_ck* key = nullptr;
+  sp_msm_job* job = nullptr;
+  ZJob() = default;
+  ZJob(const ZJob&) = delete;
+  ZJob& operator=(const ZJob&) = delete;
+  ~ZJob() {
+    uint64_t sink[8];
+    if (job) sp_msm_ck_finish(ctx, key, job, nullptr, sink);  // an early return still owns the job
+  }
+};
+
+struct VerifyState {  // one proof between the steps
+  // views into the caller's words
+  const aff_t* comm_W = nullptr;
+  const fe_t *publics = nullptr, *z_vec = nullptr;
+  fe_t eval_W, blind_eval_W, z_delta, z_beta;
+  aff_t delta, beta;
+  size_t rows = 0, lx = 0, ly = 0, nz = 0;
+  // step (a)
+  ZJob zjob;
+  std::unique_ptr<Tr> tr;
+  std::vector<fe_t> r_x, r_y;
+  fe_t r, r2, claim_inner_final, eval_Z;
+  // opening_prepare
+  aff_t comm_LZ, comm_eval_W;
+  std::vector<fe_t> L;  // eq(point[..nvr]); empty for a single-row polynomial (comm_LZ = comm_W[0])
+  fe_t rr, ip;  // the IPA challenge and <z_vec, R>
+};
+
+// step (a). start_z: begin <z_vec, ck> on the auxiliary stream as soon as the proof has parsed (the single-proof form; a batch folds all z_vec into one MSM)
+static int verify_step_a(const SpartanProverKey& pk, const uint64_t* words, size_t nwords, bool start_z, VerifyState& st) {
   sp_ctx* ctx = pk.ctx;
   const sp_dims& d = pk.dims;
 
@@ -1304,20 +1361,26 @@ int verify(const SpartanProverKey& pk, const uint64_t* words, size_t nwords, uin
   for (size_t i = 0; i < rows; ++i)
     if (!aff_on_curve(comm_W[i])) return 1;
   if (!aff_on_curve(delta) || !aff_on_curve(beta)) return 1;
+  st.comm_W = comm_W;
+  st.publics = publics;
+  st.z_vec = z_vec;
+  st.eval_W = eval_W;
+  st.blind_eval_W = blind_eval_W;
+  st.z_delta = z_delta;
+  st.z_beta = z_beta;
+  st.delta = delta;
+  st.beta = beta;
+  st.rows = rows;
+  st.lx = lx;
+  st.ly = ly;
+  st.nz = nz;
 
-  // <z_vec, ck> (ipa.rs:196-203) depends on nothing but the proof: its device part runs under everything that follows
-  struct ZJob {
-    sp_ctx* ctx;
-    const sp_ck* key;
-    sp_msm_job* job = nullptr;
-    ~ZJob() {
-      uint64_t sink[8];
-      if (job) sp_msm_ck_finish(ctx, key, job, nullptr, sink);  // an early return still owns the job
-    }
-  } zjob{ctx, pk.ck};
-  ck(sp_msm_ck_begin(ctx, pk.ck, u64p(z_vec), nz, &zjob.job), "<z, ck> (begin)");
+  st.zjob.ctx = ctx;
+  st.zjob.key = pk.ck;
+  if (start_z) ck(sp_msm_ck_begin(ctx, pk.ck, u64p(z_vec), nz, &st.zjob.job), "<z, ck> (begin)");
 
-  Tr tr(ctx, "SpartanSNARK");
+  st.tr.reset(new Tr(ctx, "SpartanSNARK"));
+  Tr& tr = *st.tr;
   tr.absorb("vk", pk.vk_digest, 32);
   tr.absorb_scalars("public_values", publics, d.num_public);
   auto absorb_rows = [&](const char* label, size_t lo, size_t cnt) {
@@ -1332,7 +1395,7 @@ int verify(const SpartanProverKey& pk, const uint64_t* words, size_t nwords, uin
   std::vector<fe_t> tau(lx);
   for (auto& t : tau) t = tr.squeeze("t");
   fe_t claim_outer_final;
-  std::vector<fe_t> r_x, r_y;
+  std::vector<fe_t>&r_x = st.r_x, &r_y = st.r_y;
   if (!sumcheck_verify(tr, fe_zero(), lx, 3, outer, &claim_outer_final, &r_x)) return 2;
   const fe_t one = fe_one<S>();
   fe_t taus_bound_rx = one;  // EqPolynomial::evaluate (src/polys/eq.rs:45-57)
@@ -1342,14 +1405,26 @@ int verify(const SpartanProverKey& pk, const uint64_t* words, size_t nwords, uin
   tr.absorb_scalars("claims_outer", claims, 3);
   const fe_t r = tr.squeeze("r"), r2 = fe_mul<S>(r, r);
   const fe_t claim_inner_joint = fe_add<S>(fe_add<S>(claims[0], fe_mul<S>(r, claims[1])), fe_mul<S>(r2, claims[2]));
-  fe_t claim_inner_final;
-  if (!sumcheck_verify(tr, claim_inner_joint, ly, 2, inner, &claim_inner_final, &r_y)) return 4;
+  if (!sumcheck_verify(tr, claim_inner_joint, ly, 2, inner, &st.claim_inner_final, &r_y)) return 4;
   std::vector<fe_t> X(1 + d.num_public + d.num_challenges);
   X[0] = one;
   std::copy(publics, publics + d.num_public + d.num_challenges, X.begin() + 1);  // challenges follow the public values in the buffer and in X
   const fe_t eval_X = sparse_poly_evaluate(ly - 1, X, r_y.data() + 1);
-  const fe_t eval_Z = fe_add<S>(fe_mul<S>(fe_sub<S>(one, r_y[0]), eval_W), fe_mul<S>(r_y[0], eval_X));
-  // A(rx,ry), B(rx,ry), C(rx,ry) = T_x^T (M T_y): one SpMV against T_y, three dot products with T_x
+  st.eval_Z = fe_add<S>(fe_mul<S>(fe_sub<S>(one, r_y[0]), eval_W), fe_mul<S>(r_y[0], eval_X));
+  st.r = r;
+  st.r2 = r2;
+  return 0;
+}
+
+// check 5 given A(rx,ry), B(rx,ry), C(rx,ry)
+static bool check5(const VerifyState& st, const fe_t eabc[3]) {
+  return fe_eq(st.claim_inner_final, fe_mul<S>(fe_add<S>(fe_add<S>(eabc[0], fe_mul<S>(st.r, eabc[1])), fe_mul<S>(st.r2, eabc[2])), st.eval_Z));
+}
+
+// step (b), single proof: A(rx,ry), B(rx,ry), C(rx,ry) = T_x^T (M T_y): one SpMV against T_y, three dot products with T_x
+static int verify_step_b(const SpartanProverKey& pk, const VerifyState& st) {
+  sp_ctx* ctx = pk.ctx;
+  const size_t N = pk.dims.num_cons, lx = st.lx, ly = st.ly;
   fe_t eabc[3];
   {
     if (!pk.v_Tx) {
@@ -1360,66 +1435,282 @@ int verify(const SpartanProverKey& pk, const uint64_t* words, size_t nwords, uin
     sp_table *Tx = pk.v_Tx, *Ty = pk.v_Ty, **mv = pk.v_mv;
     ck(sp_table_set_len(Tx, (size_t)1 << lx, (size_t)-1, (size_t)-1), "T_x len");
     ck(sp_table_set_len(Ty, (size_t)1 << ly, (size_t)-1, (size_t)-1), "T_y len");
-    ck(sp_eq_table_into(ctx, u64p(r_x.data()), lx, Tx), "T_x");
-    ck(sp_eq_table_into(ctx, u64p(r_y.data()), ly, Ty), "T_y");
+    ck(sp_eq_table_into(ctx, u64p(st.r_x.data()), lx, Tx), "T_x");
+    ck(sp_eq_table_into(ctx, u64p(st.r_y.data()), ly, Ty), "T_y");
     ck(sp_table_set_len(Ty, pk.num_cols, (size_t)-1, (size_t)-1), "T_y as z");
     ck(sp_multiply_vec(ctx, pk.S, Ty, mv[0], mv[1], mv[2]), "M T_y");
     for (int i = 0; i < 3; ++i) ck(sp_table_dot(ctx, Tx, mv[i], N, u64p(&eabc[i])), "T_x . (M T_y)");
   }
-  if (!fe_eq(claim_inner_final, fe_mul<S>(fe_add<S>(fe_add<S>(eabc[0], fe_mul<S>(r, eabc[1])), fe_mul<S>(r2, eabc[2])), eval_Z))) return 5;
-  // HyraxPCS::verify (hyrax_pc.rs:480-531) + InnerProductArgumentLinear::verify (ipa.rs:173-221)
-  aff_t comm_eval_W;
-  ck(sp_hyrax_commit_small(ctx, pk.ck_s, u64p(&eval_W), 1, u64p(&blind_eval_W), u64p(&comm_eval_W.x)), "commit eval_W");
+  return check5(st, eabc) ? 0 : 5;
+}
+
+// step (c), transcript part. HyraxPCS::verify (hyrax_pc.rs:480-531) + InnerProductArgumentLinear::verify (ipa.rs:173-221) up to the challenge r:
+// comm_eval_W and comm_LZ are absorbed before r is drawn, so both exist per proof in a batch as well. Two halves: opening_prepare_host touches the
+// proof's own transcript and host memory only (a batch runs it on host threads); opening_comm_LZ and opening_challenge make the device calls and draw r.
+static int opening_prepare_host(VerifyState& st) {
+  Tr& tr = *st.tr;
   {
-    std::vector<uint8_t> b = commitment_bytes(comm_W, rows);
+    std::vector<uint8_t> b = commitment_bytes(st.comm_W, st.rows);
     tr.absorb("poly_com", b.data(), b.size());
   }
-  const fe_t* point = r_y.data() + 1;
-  const size_t npoint = ly - 1, num_rows = ((size_t)1 << npoint) / nz, nvr = log2_ceil(num_rows);
-  aff_t comm_LZ;
+  const fe_t* point = st.r_y.data() + 1;
+  const size_t npoint = st.ly - 1, nz = st.nz, num_rows = ((size_t)1 << npoint) / nz, nvr = log2_ceil(num_rows);
   std::vector<fe_t> R;
   if (nvr == 0) {
-    comm_LZ = comm_W[0];
+    st.L.clear();
     R = eq_evals_host(point, npoint);
   } else {
-    std::vector<fe_t> L = eq_evals_host(point, nvr);
+    st.L = eq_evals_host(point, nvr);
     R = eq_evals_host(point + nvr, npoint - nvr);
-    if (rows < L.size()) return 6;
-    ck(sp_msm(ctx, u64p(L.data()), reinterpret_cast<const uint64_t*>(comm_W), L.size(), u64p(&comm_LZ.x)), "comm_LZ");
+    if (st.rows < st.L.size()) return 6;
   }
+  if (R.size() != nz) return 6;
+  fe_t ip = fe_zero();
+  for (size_t i = 0; i < nz; ++i) ip = fe_add<S>(ip, fe_mul<S>(st.z_vec[i], R[i]));
+  st.ip = ip;
+  return 0;
+}
+// comm_LZ = <L, comm rows> (hyrax_pc.rs:497-506) on the main stream
+static void opening_comm_LZ(const SpartanProverKey& pk, VerifyState& st) {
+  if (st.L.empty()) st.comm_LZ = st.comm_W[0];
+  else ck(sp_msm(pk.ctx, u64p(st.L.data()), reinterpret_cast<const uint64_t*>(st.comm_W), st.L.size(), u64p(&st.comm_LZ.x)), "comm_LZ");
+}
+// comm_eval_W, then the IPA's transcript steps up to its challenge (ipa.rs:181-194)
+static void opening_challenge(const SpartanProverKey& pk, VerifyState& st) {
+  Tr& tr = *st.tr;
+  ck(sp_hyrax_commit_small(pk.ctx, pk.ck_s, u64p(&st.eval_W), 1, u64p(&st.blind_eval_W), u64p(&st.comm_eval_W.x)), "commit eval_W");
   tr.dom_sep("inner product argument (linear)");
   {
     uint8_t b[128];
-    point_bytes(comm_LZ, b);
-    point_bytes(comm_eval_W, b + 64);
+    point_bytes(st.comm_LZ, b);
+    point_bytes(st.comm_eval_W, b + 64);
     tr.absorb("U", b, 128);
-    point_bytes(delta, b);
+    point_bytes(st.delta, b);
     tr.absorb("delta", b, 64);
-    point_bytes(beta, b);
+    point_bytes(st.beta, b);
     tr.absorb("beta", b, 64);
   }
-  const fe_t rr = tr.squeeze("r");
-  if (R.size() != nz) return 6;
+  st.rr = tr.squeeze("r");
+}
+
+// step (c), the group equations of one proof (ipa.rs:196-221)
+static int opening_check(const SpartanProverKey& pk, VerifyState& st) {
+  sp_ctx* ctx = pk.ctx;
   // r * comm_LZ and r * comm_eval_W: one wNAF scalar per pair of points (vartime_scalar_mul, msm.rs:779-867); h * z_delta and
   // <z_vec, R> * ck_c + z_beta * h_c through the fixed-base tables of the keys (hyrax_pc.rs:81-96)
-  aff_t pr2[2] = {comm_LZ, comm_eval_W}, rp[2], hzd, rhs2;
-  ck(sp_vartime_scalar_mul(ctx, u64p(&pr2[0].x), 2, u64p(&rr), u64p(&rp[0].x)), "r * (comm_LZ, comm_eval_W)");
-  ck(sp_fixed_base_mul_h(ctx, pk.ck, u64p(&z_delta), 1, u64p(&hzd.x)), "h * z_delta");
-  fe_t ip = fe_zero();
-  for (size_t i = 0; i < nz; ++i) ip = fe_add<S>(ip, fe_mul<S>(z_vec[i], R[i]));
-  ck(sp_hyrax_commit_small(ctx, pk.ck_s, u64p(&ip), 1, u64p(&z_beta), u64p(&rhs2.x)), "<z, R> * ck_c + z_beta * h_c");
-  aff_t zc;  // <z_vec, ck>: started before the transcript work
+  aff_t pr2[2] = {st.comm_LZ, st.comm_eval_W}, rp[2], hzd, rhs2;
+  ck(sp_vartime_scalar_mul(ctx, u64p(&pr2[0].x), 2, u64p(&st.rr), u64p(&rp[0].x)), "r * (comm_LZ, comm_eval_W)");
+  ck(sp_fixed_base_mul_h(ctx, pk.ck, u64p(&st.z_delta), 1, u64p(&hzd.x)), "h * z_delta");
+  ck(sp_hyrax_commit_small(ctx, pk.ck_s, u64p(&st.ip), 1, u64p(&st.z_beta), u64p(&rhs2.x)), "<z, R> * ck_c + z_beta * h_c");
+  aff_t zc;  // <z_vec, ck>: verify() started it before the transcript work
   {
-    sp_msm_job* j = zjob.job;
-    zjob.job = nullptr;
+    if (!st.zjob.job) ck(sp_msm_ck_begin(ctx, pk.ck, u64p(st.z_vec), st.nz, &st.zjob.job), "<z, ck> (begin)");
+    sp_msm_job* j = st.zjob.job;
+    st.zjob.job = nullptr;
     ck(sp_msm_ck_finish(ctx, pk.ck, j, nullptr, u64p(&zc.x)), "<z, ck> (finish)");
   }
-  const jac_t lhs1 = jac_add_mixed(jac_from_affine(rp[0]), delta), rhs1 = jac_add_mixed(jac_from_affine(zc), hzd);
+  const jac_t lhs1 = jac_add_mixed(jac_from_affine(rp[0]), st.delta), rhs1 = jac_add_mixed(jac_from_affine(zc), hzd);
   if (!same_point(lhs1, rhs1)) return 6;
-  const jac_t lhs2 = jac_add_mixed(jac_from_affine(rp[1]), beta);
+  const jac_t lhs2 = jac_add_mixed(jac_from_affine(rp[1]), st.beta);
   if (!same_point(lhs2, jac_from_affine(rhs2))) return 6;
-  if (out_publics) memcpy(out_publics, publics, d.num_public * sizeof(fe_t));  // verify() returns the public values it accepted (src/spartan.rs:577)
   return 0;
+}
+
+int verify(const SpartanProverKey& pk, const uint64_t* words, size_t nwords, uint64_t* out_publics) {
+  VerifyState st;
+  int code;
+  if ((code = verify_step_a(pk, words, nwords, true, st))) return code;
+  if ((code = verify_step_b(pk, st))) return code;
+  if ((code = opening_prepare_host(st))) return code;
+  opening_comm_LZ(pk, st);
+  opening_challenge(pk, st);
+  if ((code = opening_check(pk, st))) return code;
+  if (out_publics) memcpy(out_publics, st.publics, pk.dims.num_public * sizeof(fe_t));  // verify() returns the public values it accepted (src/spartan.rs:577)
+  return 0;
+}
+
+// ---- verify_batch: `count` proofs under one key in one pass ---------------------------------------------------------
+// codes[k] == verify(proof k) for every k; a batch of one IS verify; from two proofs on, what the proofs share is paid once:
+//   step (a) and the host part of the opening per proof on host threads (they touch no device state);
+//   step (b) per chunk of sp_shape_matrix_evals_chunk() survivors: the chunk's eq tables and ONE sp_shape_matrix_evals_batched (no product tables); check 5 is exact;
+//   step (c) comm_LZ_k per proof on the auxiliary stream under step (b), the IPA challenge r_k per proof, then the group equations of all survivors as one random linear combination
+//       sum_k rho_k (r_k comm_LZ_k + delta_k)  ==  < sum_k rho_k z_vec_k, ck >  +  (sum_k rho_k z_delta_k) h
+//       sum_k rho'_k beta_k  ==  (sum_k rho'_k (<z_vec_k, R_k> - r_k eval_W_k)) ck_c  +  (sum_k rho'_k (z_beta_k - r_k blind_eval_W_k)) h_c
+//     (comm_LZ_k = sum_i L_k[i] comm_W_k[i] is formed per proof all the same: its bytes go into the transcript r_k is drawn from, so the left side of the
+//     first equation is an MSM over the 2 K points comm_LZ_k, delta_k rather than over the K (rows + 1) rows).
+//     If either equation fails, opening_check names the proofs with code 6 one by one.
+// The weights come from the library's Keccak transcript over everything the batch holds (batch_weights), so a prover who fixes the proofs first cannot
+// aim at them: a false accept needs a guessed 256-bit challenge.
+// rho_k = w[2 k], rho'_k = w[2 k + 1]. Transcript "SpartanSNARK::verify_batch": absorb "vk" (digest), "count" (K, 8 bytes LE), then per proof in batch
+// order "proof_len" (words, 8 bytes LE) and "proof" (the words as they are, LE), then "seed" (32 bytes) if the caller gave one; squeeze "rho" 2 K times.
+static std::vector<fe_t> batch_weights(const SpartanProverKey& pk, const uint64_t* const* words, const size_t* nwords, size_t count, const uint8_t* seed) {
+  Tr tr(pk.ctx, "SpartanSNARK::verify_batch");
+  tr.absorb("vk", pk.vk_digest, 32);
+  auto le8 = [](uint64_t v, uint8_t b[8]) {
+    for (int i = 0; i < 8; ++i) b[i] = (uint8_t)(v >> (8 * i));
+  };
+  uint8_t b8[8];
+  le8(count, b8);
+  tr.absorb("count", b8, 8);
+  for (size_t k = 0; k < count; ++k) {
+    le8(nwords[k], b8);
+    tr.absorb("proof_len", b8, 8);
+    tr.absorb("proof", reinterpret_cast<const uint8_t*>(words[k]), nwords[k] * 8);
+  }
+  if (seed) tr.absorb("seed", seed, 32);
+  std::vector<fe_t> w(2 * count);
+  for (auto& x : w) x = tr.squeeze("rho");
+  return w;
+}
+
+void verify_batch(const SpartanProverKey& pk, const uint64_t* const* words, const size_t* nwords, size_t count, const uint8_t* seed, int* codes,
+                  uint64_t* out_publics, ss_verify_batch_info* info) {
+  sp_ctx* ctx = pk.ctx;
+  ss_verify_batch_info inf{0, 1, 0, 0};
+  if (info) *info = inf;
+  if (count == 0) return;
+  ck(sp_ctx_bind_thread(ctx), "device");  // the caller may be a thread other than the one that created the context
+  const size_t npub = pk.dims.num_public;
+  if (count == 1) {  // nothing to share: the single-proof form, which starts <z_vec, ck> under its transcript work (no chunk, no combined equations)
+    codes[0] = verify(pk, words[0], nwords[0], out_publics);
+    return;
+  }
+  const size_t KC = sp_shape_matrix_evals_chunk();  // pairs per launch: the device memory of a batch is this many (T_x, T_y) pairs
+  // the weights need the proofs alone: hashed on a thread of their own under steps (a) and (b)
+  std::future<std::vector<fe_t>> weights = std::async(std::launch::async, [&] { return batch_weights(pk, words, nwords, count, seed); });
+  struct Join {
+    std::future<std::vector<fe_t>>& f;
+    ~Join() {
+      if (f.valid()) f.wait();
+    }
+  } join{weights};
+  std::vector<VerifyState> st(count);
+  std::vector<int> host6(count, 0);  // what the opening's host part says (0 or 6): counts only for a proof that passes check 5
+  parallel_for(count, (size_t)1 << 20, [&](size_t k) {
+    if ((codes[k] = verify_step_a(pk, words[k], nwords[k], false, st[k])) == 0) host6[k] = opening_prepare_host(st[k]);
+  });
+  std::vector<size_t> live;
+  for (size_t k = 0; k < count; ++k)
+    if (codes[k] == 0) live.push_back(k);
+  // comm_LZ_k needs r_y alone: a helper thread runs these MSMs on the auxiliary stream (sp_msm_eq_begin: sum_i eq(r, i) comm_W[i], the same group element)
+  // under the matrix evaluations of step (b) on the main stream. A proof that then fails check 5 has had its comm_LZ formed for nothing (an upload and
+  // one MSM beside the main stream's work): waiting for check 5 instead would put every MSM behind the matrix evaluations again.
+  const std::vector<size_t> after_a = live;
+  std::future<void> lz = std::async(std::launch::async, [&] {
+    ck(sp_ctx_bind_thread(ctx), "helper thread: device");  // a new thread starts on device 0; the context may live on another GPU
+    struct Pts {
+      sp_points* p = nullptr;
+      ~Pts() { sp_points_free(p); }
+    } pts;
+    for (size_t k : after_a) {
+      VerifyState& s = st[k];
+      if (host6[k]) continue;
+      if (s.L.empty()) {
+        s.comm_LZ = s.comm_W[0];
+        continue;
+      }
+      sp_msm_job* job = nullptr;
+      ck(sp_points_upload(ctx, reinterpret_cast<const uint64_t*>(s.comm_W), s.L.size(), &pts.p), "comm_W upload");
+      ck(sp_msm_eq_begin(ctx, pts.p, u64p(s.r_y.data() + 1), log2_ceil(s.L.size()), &job), "comm_LZ (begin)");
+      ck(sp_msm_job_finish(ctx, job, u64p(&s.comm_LZ.x)), "comm_LZ (finish)");
+    }
+  });
+  struct JoinLz {
+    std::future<void>& f;
+    ~JoinLz() {
+      if (f.valid()) f.wait();
+    }
+  } join_lz{lz};
+  // step (b)
+  if (!live.empty()) {
+    const size_t lx = st[live[0]].lx, ly = st[live[0]].ly;
+    if (pk.vb_Tx.empty()) {
+      for (size_t j = 0; j < KC; ++j) {
+        sp_table *tx = nullptr, *ty = nullptr;
+        ck(sp_table_zeros(ctx, (size_t)1 << lx, (size_t)-1, (size_t)-1, &tx), "T_x alloc");
+        pk.vb_Tx.push_back(tx);
+        ck(sp_table_zeros(ctx, (size_t)1 << ly, (size_t)-1, (size_t)-1, &ty), "T_y alloc");
+        pk.vb_Ty.push_back(ty);
+      }
+    }
+    std::vector<size_t> next;
+    for (size_t c0 = 0; c0 < live.size(); c0 += KC) {
+      const size_t kc = std::min(KC, live.size() - c0);
+      std::vector<fe_t> eabc(3 * kc);
+      for (size_t j = 0; j < kc; ++j) {
+        const VerifyState& s = st[live[c0 + j]];
+        ck(sp_eq_table_into(ctx, u64p(s.r_x.data()), lx, pk.vb_Tx[j]), "T_x");
+        ck(sp_eq_table_into(ctx, u64p(s.r_y.data()), ly, pk.vb_Ty[j]), "T_y");
+      }
+      ck(sp_shape_matrix_evals_batched(ctx, pk.S, pk.vb_Tx.data(), pk.vb_Ty.data(), kc, u64p(eabc.data())), "matrix_evals_batched");
+      inf.matrix_chunks++;
+      for (size_t j = 0; j < kc; ++j) {
+        const size_t k = live[c0 + j];
+        if (check5(st[k], eabc.data() + 3 * j)) next.push_back(k);
+        else codes[k] = 5;
+      }
+    }
+    live.swap(next);
+  }
+  // step (c): the challenge of every proof that is left
+  lz.get();
+  {
+    std::vector<size_t> next;
+    for (size_t k : live)
+      if ((codes[k] = host6[k]) == 0) {
+        opening_challenge(pk, st[k]);
+        next.push_back(k);
+      }
+    live.swap(next);
+  }
+  const std::vector<fe_t> w = weights.get();
+  if (!live.empty()) {
+    const size_t nz = st[live[0]].nz, n = live.size();
+    inf.opening_proofs = n;
+    std::vector<fe_t> zsum(nz, fe_zero()), s1(2 * n), s2(n);
+    std::vector<aff_t> p1(2 * n), p2(n);
+    fe_t zd = fe_zero(), c2 = fe_zero(), b2 = fe_zero();
+    for (size_t i = 0; i < n; ++i) {
+      const VerifyState& s = st[live[i]];
+      const fe_t rho = w[2 * live[i]], rho2 = w[2 * live[i] + 1];
+      zd = fe_add<S>(zd, fe_mul<S>(rho, s.z_delta));
+      p1[2 * i] = s.comm_LZ;
+      s1[2 * i] = fe_mul<S>(rho, s.rr);
+      p1[2 * i + 1] = s.delta;
+      s1[2 * i + 1] = rho;
+      p2[i] = s.beta;
+      s2[i] = rho2;
+      c2 = fe_add<S>(c2, fe_mul<S>(rho2, fe_sub<S>(s.ip, fe_mul<S>(s.rr, s.eval_W))));
+      b2 = fe_add<S>(b2, fe_mul<S>(rho2, fe_sub<S>(s.z_beta, fe_mul<S>(s.rr, s.blind_eval_W))));
+    }
+    parallel_for(8, (size_t)1 << 20, [&](size_t part) {  // sum_k rho_k z_vec_k, a column range per thread
+      for (size_t j = part * nz / 8, e = (part + 1) * nz / 8; j < e; ++j)
+        for (size_t i = 0; i < n; ++i) zsum[j] = fe_add<S>(zsum[j], fe_mul<S>(w[2 * live[i]], st[live[i]].z_vec[j]));
+    });
+    ZJob zj;
+    zj.ctx = ctx;
+    zj.key = pk.ck;
+    ck(sp_msm_ck_begin(ctx, pk.ck, u64p(zsum.data()), nz, &zj.job), "<sum rho z, ck> (begin)");
+    aff_t lhs1, lhs2, rhs1, rhs2;
+    ck(sp_msm(ctx, u64p(s1.data()), u64p(&p1[0].x), 2 * n, u64p(&lhs1.x)), "sum rho (r comm_LZ + delta)");
+    ck(sp_msm(ctx, u64p(s2.data()), u64p(&p2[0].x), n, u64p(&lhs2.x)), "sum rho' beta");
+    ck(sp_hyrax_commit_small(ctx, pk.ck_s, u64p(&c2), 1, u64p(&b2), u64p(&rhs2.x)), "combined right side of the second equation");
+    {
+      sp_msm_job* j = zj.job;
+      zj.job = nullptr;
+      ck(sp_msm_ck_finish(ctx, pk.ck, j, u64p(&zd), u64p(&rhs1.x)), "<sum rho z, ck> (finish)");
+    }
+    const bool ok = same_point(jac_from_affine(lhs1), jac_from_affine(rhs1)) && same_point(jac_from_affine(lhs2), jac_from_affine(rhs2));
+    inf.opening_batched_ok = ok ? 1 : 0;
+    if (!ok) {
+      for (size_t k : live) codes[k] = opening_check(pk, st[k]);
+      inf.fallback_proofs = n;
+    }
+  }
+  if (out_publics)
+    for (size_t k = 0; k < count; ++k)
+      if (codes[k] == 0) memcpy(out_publics + 4 * npub * k, st[k].publics, npub * sizeof(fe_t));
+  if (info) *info = inf;
 }
 
 }  // namespace spartan2
@@ -1569,6 +1860,18 @@ int ss_verify(void* pk, const uint64_t* words, size_t nwords, uint64_t* out_publ
     return catch_all();
   }
 }
+// verify_batch (see spartan2::verify_batch): `count` proofs of this key, codes[k] = what ss_verify returns for proof k (0 accept, 1..6). seed: 32 bytes
+// mixed into the weights of the combined opening check, or NULL. out_publics (may be NULL): count x num_public scalars, row k written when codes[k] == 0.
+// info may be NULL. Returns 0, or < 0 = library error (the codes are then meaningless).
+int ss_verify_batch(void* pk, const uint64_t* const* words, const size_t* nwords, size_t count, const uint8_t* seed, int* codes, uint64_t* out_publics,
+                    ss_verify_batch_info* info) {
+  try {
+    verify_batch(*(SpartanProverKey*)pk, words, nwords, count, seed, codes, out_publics, info);
+    return 0;
+  } catch (...) {
+    return catch_all();
+  }
+}
 // SpartanSNARK's shape-dependent lengths (what the bincode length prefixes of a proof for this key must say)
 static sp_spartan_layout proof_layout(const SpartanProverKey& pk) {
   const sp_dims& d = pk.dims;
@@ -1607,6 +1910,31 @@ int ss_verify_bytes(void* pk_, const uint8_t* bytes, size_t n, uint64_t* out_pub
     std::vector<uint64_t> words(nwords);
     ck(sp_proof_deserialize(bytes, n, &L, words.data(), words.size(), &nwords), "proof_deserialize");
     return verify(*pk, words.data(), nwords, out_publics);
+  } catch (...) {
+    return catch_all();
+  }
+}
+// the same over serialised proofs: bytes that do not decode to a proof of this key's shape get code 1, as in ss_verify_bytes
+int ss_verify_bytes_batch(void* pk_, const uint8_t* const* bytes, const size_t* nbytes, size_t count, const uint8_t* seed, int* codes, uint64_t* out_publics,
+                          ss_verify_batch_info* info) {
+  try {
+    auto* pk = (SpartanProverKey*)pk_;
+    const sp_spartan_layout want = proof_layout(*pk);
+    std::vector<std::vector<uint64_t>> store(count);
+    std::vector<const uint64_t*> words(count);
+    std::vector<size_t> nwords(count);
+    for (size_t k = 0; k < count; ++k) {
+      sp_spartan_layout L;
+      size_t nw = 0;
+      if (sp_proof_deserialize(bytes[k], nbytes[k], &L, nullptr, 0, &nw) == SP_OK && memcmp(&L, &want, sizeof L) == 0) {
+        store[k].resize(nw);
+        ck(sp_proof_deserialize(bytes[k], nbytes[k], &L, store[k].data(), store[k].size(), &nw), "proof_deserialize");
+      }  // else: no words, which fails the length check of step (a) with code 1
+      words[k] = store[k].data();
+      nwords[k] = store[k].size();
+    }
+    verify_batch(*pk, words.data(), nwords.data(), count, seed, codes, out_publics, info);
+    return 0;
   } catch (...) {
     return catch_all();
   }

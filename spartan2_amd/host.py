@@ -20,6 +20,7 @@ def lib():
         L = ctypes.CDLL(LIB_PATH)
         L.ss_last_error.restype = ctypes.c_char_p
         L.ss_proof_words.restype = ctypes.c_size_t
+        L.ssd_proof_words.restype, L.ssd_proof_words.argtypes = ctypes.c_size_t, [ctypes.c_void_p]
         _lib = L
     return _lib
 
@@ -560,10 +561,7 @@ class ShardedSpartanSNARK:
         return used.value
 
     def proof_words(self):
-        d = self.dims
-        M = d["num_shared"] + d["num_precommitted"] + d["num_rest"]
-        lx, ly = d["num_cons"].bit_length() - 1, M.bit_length()
-        return 8 * (M // 2048) + 4 * d["num_public"] + 12 * lx + 12 + 8 * ly + 8 + 16 + 4 * 2048 + 8
+        return lib().ssd_proof_words(self.pk)
 
     def prove(self, tape: np.ndarray):
         n = self.proof_words()

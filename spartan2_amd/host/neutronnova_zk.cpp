@@ -10,8 +10,7 @@
 #include <deque>
 
 #include "neutronnova_nifs.hpp"
-#include "snark_common.hpp"
-#include "verifier_circuit.hpp"
+#include "proof_layout.hpp"
 
 namespace spartan2 {
 
@@ -94,6 +93,7 @@ struct NNZkKey {
   sp_ck *ck = nullptr, *vc_ck = nullptr;
   std::vector<aff_t> gens;  // "ck": 2048 bases + h; the width-32 key is its first 32 bases with gens[32] as h (PCS::setup(b"ck", ., 32), src/r1cs/mod.rs:1690-1693)
   vcirc::Shape vc;
+  NNLayout layout;  // of a proof under this key (proof_layout.hpp)
   size_t nb = 0, nx = 0, ny = 0, num_steps = 0, num_vars = 0;
   uint8_t vk_digest[32];
   // verify(): eq tables and the three M * T_y products of the matrix evaluations, allocated on first use
@@ -219,6 +219,7 @@ static NNZkKey* nn_setup(sp_ctx* ctx, const R1CSIntView& Rs, const R1CSIntView& 
     pk->nx = log2_ceil(Ps.dims.num_cons);
     pk->ny = log2_ceil(pk->num_vars) + 1;
     pk->vc = vcirc::Shape::from_circuit(vcirc::Circuit(pk->nb, pk->nx, pk->ny, 32));
+    pk->layout = NNLayout(pk->dims, pk->dims_core, num_steps, pk->vc);
     {  // NeutronNovaVerifierKey::write_bytes (src/neutronnova_zk.rs:1305-1333) -> SHA-256 (src/digest.rs:62-76)
       struct Sink {
         sp_wire* w = nullptr;
@@ -351,38 +352,12 @@ static NNZkPrep* nn_prep_prove_sha256(const NNZkKey& pk, const sp_sha256_plan* p
   });
 }
 
-struct ProofBuf {
-  std::vector<uint64_t> words;
-  void pf(const fe_t& f) { words.insert(words.end(), u64p(&f), u64p(&f) + 4); }
-  void pp(const aff_t& a) {
-    pf(a.x);
-    pf(a.y);
-  }
-  void pc(const std::vector<aff_t>& c) {
-    for (const aff_t& a : c) pp(a);
-  }
-};
-
 static void absorb_instance(Tr& tr, const char* label, const std::vector<aff_t>& comm, const std::vector<fe_t>& X) {  // R1CSInstance bytes (src/r1cs/mod.rs:728-736)
   std::vector<uint8_t> b = commitment_bytes(comm.data(), comm.size());
   const size_t off = b.size();
   b.resize(off + 32 * X.size());
   for (size_t j = 0; j < X.size(); ++j) sp::fe_to_be_bytes<S>(X[j], b.data() + off + 32 * j);
   tr.absorb(label, b.data(), b.size());
-}
-static std::vector<fe_t> eq_evals(const fe_t* r, size_t ell) {  // EqPolynomial::evals_from_points (src/polys/eq.rs:59-92), host side for O(sqrt) tables
-  std::vector<fe_t> ev((size_t)1 << ell, fe_zero());
-  ev[0] = fe_one<S>();
-  size_t size = 1;
-  for (size_t k = ell; k-- > 0;) {
-    for (size_t i = 0; i < size; ++i) {
-      const fe_t y = fe_mul<S>(ev[i], r[k]);
-      ev[size + i] = y;
-      ev[i] = fe_sub<S>(ev[i], y);
-    }
-    size *= 2;
-  }
-  return ev;
 }
 // rows of `n` host scalars committed with the width-32 key in one device call (many rows: T, the random instance)
 // slot `i` of the prep state's scratch tables holding `n` elements of host data
@@ -443,7 +418,7 @@ static void prove_direct(size_t num_cols, const std::vector<fe_t>& poly, const s
     return;
   }
   const size_t nvr = log2_ceil(rows);
-  const std::vector<fe_t> L = eq_evals(point, nvr);
+  const std::vector<fe_t> L = eq_evals_host(point, nvr);
   v->assign(num_cols, fe_zero());
   for (size_t j = 0; j < L.size(); ++j)
     for (size_t i = 0; i < num_cols; ++i) {
@@ -811,7 +786,7 @@ static ProofBuf nn_prove(const NNZkKey& pk, NNZkPrep& ps, Tape& tape, double* ph
   }
   if (t_fold) {  // r_y is known: the halves of comm_LZ and beta, under the verifier-circuit phase
     const size_t nvr = log2_ceil(rows);
-    t_open = ps.wk.submit([&pk, &ps, &f_comm, &core_comm, rows, L = eq_evals(r_y.data() + 1, nvr), Rv = eq_evals(r_y.data() + 1 + nvr, pk.ny - 1 - nvr)] {
+    t_open = ps.wk.submit([&pk, &ps, &f_comm, &core_comm, rows, L = eq_evals_host(r_y.data() + 1, nvr), Rv = eq_evals_host(r_y.data() + 1 + nvr, pk.ny - 1 - nvr)] {
       NNZkPrep::OpeningAhead& O = ps.open;
       try {
         if (!O.delta_valid || Rv.size() != O.dv.size() || L.size() > rows) return;
@@ -1003,7 +978,7 @@ static ProofBuf nn_prove(const NNZkKey& pk, NNZkPrep& ps, Tape& tape, double* ph
   lap("folds + relaxed outer sc");
   tr.absorb_scalars("claims_outer", v_claims, 3);
   const fe_t vr = tr.squeeze("r"), vr2 = fe_mul<S>(vr, vr);
-  const std::vector<fe_t> v_evals_rx = eq_evals(v_rx.data(), vlx);
+  const std::vector<fe_t> v_evals_rx = eq_evals_host(v_rx.data(), vlx);
   fe_t claim_E = fe_zero();
   {
     fe_t partial[32];
@@ -1116,7 +1091,7 @@ static ProofBuf nn_prove(const NNZkKey& pk, NNZkPrep& ps, Tape& tape, double* ph
     lap("pcs: absorb poly_com");
     const fe_t* point = r_y.data() + 1;
     const size_t npoint = pk.ny - 1, nvr = log2_ceil(rows);
-    const std::vector<fe_t> L = eq_evals(point, nvr);
+    const std::vector<fe_t> L = eq_evals_host(point, nvr);
     const size_t ncols = (size_t)1 << (npoint - nvr);
     if (t_open) ps.wk.wait(t_open);
     lap("pcs: wait for the opening's points");
@@ -1156,7 +1131,7 @@ static ProofBuf nn_prove(const NNZkKey& pk, NNZkPrep& ps, Tape& tape, double* ph
     } else {
       if (laps && side) fprintf(stderr, "nn_prove: opening inputs computed inline (delta %d, points %d, tape %zu vs %zu)\n", (int)ps.open.delta_valid, (int)ps.open.points_valid, ps.open.tape_from, tape.pos);
       // the mask d and its blinds do not depend on the transcript (ipa.rs:139-147): delta's MSM runs on the auxiliary stream beside comm_LZ's
-      Rv = eq_evals(point + nvr, npoint - nvr);
+      Rv = eq_evals_host(point + nvr, npoint - nvr);
       dv.resize(Rv.size());
       for (auto& x : dv) x = tape.next();
       r_delta = tape.next();
@@ -1222,188 +1197,10 @@ static ProofBuf nn_prove(const NNZkKey& pk, NNZkPrep& ps, Tape& tape, double* ph
     phase_ms[6] = t_end - t_start;
     phase_ms[7] = vst.commit_ms;  // inside the phases above: the per-round verifier-circuit commitments (process_round)
   }
+  if (proof.words.size() != pk.layout.words()) throw Error(SP_ERR_INTERNAL, "nn_prove: the proof does not fill the key's layout");
   return proof;
 }
 
-
-// number of 64-bit words of a proof in the canonical layout (NNProof::serialize)
-static size_t proof_words(const NNZkKey& pk) {
-  const sp_dims& d = pk.dims;
-  const size_t CW = DEFAULT_COMMITMENT_WIDTH, rows_sh = d.num_shared_unpadded ? d.num_shared / CW : 0, rows_pre = d.num_precommitted_unpadded ? d.num_precommitted / CW : 0,
-               rows_rest = d.num_rest / CW;
-  const vcirc::Shape& vs = pk.vc;
-  const size_t vlx = log2_ceil(vs.num_cons), vly = log2_ceil(next_pow2(vs.total_vars)) + 1;
-  size_t w = 8 * rows_sh + pk.num_steps * (8 * (rows_pre + rows_rest) + 4 * d.num_public) + 8 * (rows_pre + rows_rest) + 4 * pk.dims_core.num_public + 16 + 4 * CW + 8;
-  w += 8 * (vs.total_vars / 32) + 4 * vs.num_public + 4 * vs.total_challenges;
-  w += 8 * (vs.num_cons / 32) + 8 * (vs.total_vars / 32) + 8 * (vs.num_cons / 32) + 4 + 4 * vs.num_io();
-  w += 12 * vlx + 12 + 8 * vly + 4 * 32 + 4 + 4 * 32 + 4;
-  return w;
-}
-
-// ---- NeutronNovaZkSNARK on the wire (src/neutronnova_zk.rs:1373-1385; bincode framing through the library's sink / source) ------------------------
-// flat layout (NNProof::serialize) <-> { comm_W_shared: Option, step_instances: Vec<SplitR1CSInstance>, core_instance, eval_arg, U_verifier:
-// SplitMultiRoundR1CSInstance, nifs: NovaNIFS { comm_T }, random_U: RelaxedR1CSInstance { comm_W, comm_E, X, u }, relaxed_snark }. The instances carry
-// comm_W_shared = None (:2069-2078) and no challenges.
-struct WireSinkGuard {
-  sp_wire* w = nullptr;
-  ~WireSinkGuard() { sp_wire_free(w); }
-};
-static std::vector<uint8_t> nn_proof_to_bytes(const NNZkKey& pk, const uint64_t* words, size_t nwords) {
-  if (nwords != proof_words(pk)) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "nn_proof_to_bytes: the word count does not match the key");
-  const sp_dims& d = pk.dims;
-  const vcirc::Shape& vs = pk.vc;
-  const size_t CW = DEFAULT_COMMITMENT_WIDTH, rows_sh = d.num_shared_unpadded ? d.num_shared / CW : 0, rows_pre = d.num_precommitted_unpadded ? d.num_precommitted / CW : 0,
-               rows_rest = d.num_rest / CW, VW = vs.width;
-  WireSinkGuard g;
-  ck(sp_wire_new(0, &g.w), "wire sink");
-  sp_wire* w = g.w;
-  const uint64_t* p = words;
-  auto u64v = [&](uint64_t v) { ck(sp_wire_u64s(w, &v, 1, 0), "wire"); };
-  auto commitment = [&](size_t rows) {
-    ck(sp_wire_points(w, p, rows, 1), "wire");
-    p += 8 * rows;
-  };
-  auto option_commitment = [&](size_t rows) {
-    ck(sp_wire_u8(w, rows ? 1 : 0), "wire");
-    if (rows) commitment(rows);
-  };
-  auto scalars = [&](size_t n, int with_len) {
-    ck(sp_wire_scalars(w, p, n, with_len), "wire");
-    p += 4 * n;
-  };
-  auto instance = [&](size_t npub, size_t my_pre, size_t my_rest) {
-    ck(sp_wire_u8(w, 0), "wire");
-    option_commitment(my_pre);
-    commitment(my_rest);
-    scalars(npub, 1);
-    u64v(0);  // challenges: an empty Vec
-  };
-  // the core circuit may split the same rows into precommitted | rest differently (nn_setup)
-  const sp_dims& dc = pk.dims_core;
-  const size_t rows_pre_c = dc.num_precommitted_unpadded ? dc.num_precommitted / CW : 0, rows_rest_c = dc.num_rest / CW;
-  auto sumcheck = [&](size_t rounds, size_t per) {
-    u64v(rounds);
-    for (size_t i = 0; i < rounds; ++i) scalars(per, 1);
-  };
-  option_commitment(rows_sh);
-  u64v(pk.num_steps);
-  for (size_t i = 0; i < pk.num_steps; ++i) instance(d.num_public, rows_pre, rows_rest);
-  instance(pk.dims_core.num_public, rows_pre_c, rows_rest_c);
-  ck(sp_wire_points(w, p, 2, 0), "wire");  // ipa.delta, ipa.beta
-  p += 16;
-  scalars(CW, 1);
-  scalars(2, 0);
-  u64v(vs.num_rounds);  // U_verifier.comm_w_per_round
-  for (size_t r = 0; r < vs.num_rounds; ++r) commitment(vs.vars_padded[r] / VW);
-  scalars(vs.num_public, 1);
-  u64v(vs.num_rounds);  // challenges_per_round
-  for (size_t r = 0; r < vs.num_rounds; ++r) scalars(vs.chals_per_round[r], 1);
-  commitment(vs.num_cons / VW);    // nifs.comm_T
-  commitment(vs.total_vars / VW);  // random_U.comm_W
-  commitment(vs.num_cons / VW);    // random_U.comm_E
-  const uint64_t* u = p;           // flat: u, then X; on the wire X, then u (src/r1cs/mod.rs:213-218)
-  p += 4;
-  scalars(vs.num_io(), 1);
-  ck(sp_wire_scalars(w, u, 1, 0), "wire");
-  sumcheck(log2_ceil(vs.num_cons), 3);
-  scalars(3, 0);
-  sumcheck(log2_ceil(next_pow2(vs.total_vars)) + 1, 2);
-  scalars(VW, 1);
-  scalars(1, 0);
-  scalars(VW, 1);
-  scalars(1, 0);
-  if ((size_t)(p - words) != nwords) throw Error(SP_ERR_INTERNAL, "nn_proof_to_bytes: layout walk out of step");
-  std::vector<uint8_t> out(sp_wire_len(w));
-  ck(sp_wire_bytes(w, out.data(), out.size()), "wire bytes");
-  return out;
-}
-// the inverse; every length prefix must be the one the key's shape dictates (the flat layout has no room for anything else)
-static std::vector<uint64_t> nn_proof_from_bytes(const NNZkKey& pk, const uint8_t* bytes, size_t n) {
-  const sp_dims& d = pk.dims;
-  const vcirc::Shape& vs = pk.vc;
-  const size_t CW = DEFAULT_COMMITMENT_WIDTH, rows_sh = d.num_shared_unpadded ? d.num_shared / CW : 0, rows_pre = d.num_precommitted_unpadded ? d.num_precommitted / CW : 0,
-               rows_rest = d.num_rest / CW, VW = vs.width;
-  struct Src {
-    sp_unwire* r = nullptr;
-    ~Src() { sp_unwire_free(r); }
-  } src;
-  ck(sp_unwire_new(bytes, n, &src.r), "wire source");
-  sp_unwire* r = src.r;
-  std::vector<uint64_t> out;
-  out.reserve(proof_words(pk));
-  auto expect_len = [&](size_t want, size_t elem) {
-    size_t got;
-    ck(sp_unwire_len(r, elem, &got), "wire length");
-    if (got != want) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "wire: a length prefix does not match the key's shape");
-  };
-  auto points = [&](size_t cnt) {
-    out.resize(out.size() + 8 * cnt);
-    ck(sp_unwire_points(r, cnt, out.data() + out.size() - 8 * cnt), "wire points");
-  };
-  auto scalars = [&](size_t cnt) {
-    out.resize(out.size() + 4 * cnt);
-    ck(sp_unwire_scalars(r, cnt, out.data() + out.size() - 4 * cnt), "wire scalars");
-  };
-  auto tag = [&](uint8_t want) {
-    uint8_t t;
-    ck(sp_unwire_u8(r, &t), "wire tag");
-    if (t != want) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "wire: an Option tag does not match the key's shape");
-  };
-  auto commitment = [&](size_t rows) {
-    expect_len(rows, 96);
-    points(rows);
-  };
-  auto option_commitment = [&](size_t rows) {
-    tag(rows ? 1 : 0);
-    if (rows) commitment(rows);
-  };
-  auto vec_scalars = [&](size_t cnt) {
-    expect_len(cnt, 32);
-    scalars(cnt);
-  };
-  auto instance = [&](size_t npub, size_t my_pre, size_t my_rest) {
-    tag(0);
-    option_commitment(my_pre);
-    commitment(my_rest);
-    vec_scalars(npub);
-    expect_len(0, 32);
-  };
-  const sp_dims& dc = pk.dims_core;
-  const size_t rows_pre_c = dc.num_precommitted_unpadded ? dc.num_precommitted / CW : 0, rows_rest_c = dc.num_rest / CW;
-  auto sumcheck = [&](size_t rounds, size_t per) {
-    expect_len(rounds, 8 + 32 * per);
-    for (size_t i = 0; i < rounds; ++i) vec_scalars(per);
-  };
-  option_commitment(rows_sh);
-  expect_len(pk.num_steps, 1 + 1 + 8 + 8 + 8);
-  for (size_t i = 0; i < pk.num_steps; ++i) instance(d.num_public, rows_pre, rows_rest);
-  instance(pk.dims_core.num_public, rows_pre_c, rows_rest_c);
-  points(2);
-  vec_scalars(CW);
-  scalars(2);
-  expect_len(vs.num_rounds, 8);
-  for (size_t k = 0; k < vs.num_rounds; ++k) commitment(vs.vars_padded[k] / VW);
-  vec_scalars(vs.num_public);
-  expect_len(vs.num_rounds, 8);
-  for (size_t k = 0; k < vs.num_rounds; ++k) vec_scalars(vs.chals_per_round[k]);
-  commitment(vs.num_cons / VW);
-  commitment(vs.total_vars / VW);
-  commitment(vs.num_cons / VW);
-  const size_t u_at = out.size();
-  out.resize(u_at + 4);  // flat: u in front of X
-  vec_scalars(vs.num_io());
-  ck(sp_unwire_scalars(r, 1, out.data() + u_at), "wire scalars");
-  sumcheck(log2_ceil(vs.num_cons), 3);
-  scalars(3);
-  sumcheck(log2_ceil(next_pow2(vs.total_vars)) + 1, 2);
-  vec_scalars(VW);
-  scalars(1);
-  vec_scalars(VW);
-  scalars(1);
-  ck(sp_unwire_done(r), "wire end");
-  if (out.size() != proof_words(pk)) throw Error(SP_ERR_INTERNAL, "nn_proof_from_bytes: layout walk out of step");
-  return out;
-}
 
 // ---- NeutronNovaZkSNARK::verify (src/neutronnova_zk.rs:2096-2343) — SURVEY 8(f) rank 3 for caller #2 -----------------------------------------------
 // What scales with the step circuits runs on the device through the same ABI: the fold of the step instances' commitments (one shared-weights MSM per
@@ -1419,10 +1216,10 @@ static int nn_verify(const NNZkKey& pk, const uint64_t* words, size_t nwords) {
   const sp_dims& d = pk.dims;
   const vcirc::Shape& vs = pk.vc;
   const size_t CW = DEFAULT_COMMITMENT_WIDTH, n = pk.num_steps, nv = pk.num_vars, N = d.num_cons, dpub = d.num_public, cpub = pk.dims_core.num_public;
-  const size_t rows_sh = d.num_shared_unpadded ? d.num_shared / CW : 0, rows_pre = d.num_precommitted_unpadded ? d.num_precommitted / CW : 0, rows_rest = d.num_rest / CW;
-  const size_t rows = rows_sh + rows_pre + rows_rest;
+  const NNLayout& lay = pk.layout;
+  const size_t rows_sh = lay.rows_sh, rows = lay.rows();
   const size_t vnv = vs.total_vars, vcons = vs.num_cons, vio = vs.num_io(), vlx = log2_ceil(vcons), vnvp = next_pow2(vnv), vly = log2_ceil(vnvp) + 1, VW = vs.width;
-  if (n == 0 || nwords != proof_words(pk)) return 1;
+  if (n == 0 || nwords != lay.words()) return 1;
   ck(sp_ctx_bind_thread(ctx), "device");
   static const bool laps = [] {
     const char* e = getenv("SPARTAN_HOST_LAPS");
@@ -1437,80 +1234,25 @@ static int nn_verify(const NNZkKey& pk, const uint64_t* words, size_t nwords) {
     t_lap = t;
   };
   // ---- the proof in its canonical layout; every coordinate and scalar of an untrusted proof must be a canonical residue and every point on the curve
-  const fe_t* w = reinterpret_cast<const fe_t*>(words);
-  size_t o = 0;
-  bool well_formed = true;
-  auto pts = [&](size_t cnt) {
-    const aff_t* p = reinterpret_cast<const aff_t*>(w + o);
-    for (size_t i = 0; i < cnt; ++i)
-      if (!limbs_canonical<B>(p[i].x) || !limbs_canonical<B>(p[i].y) || !aff_on_curve(p[i])) well_formed = false;
-    o += 2 * cnt;
-    return p;
-  };
-  auto fes = [&](size_t cnt) {
-    const fe_t* p = w + o;
-    for (size_t i = 0; i < cnt; ++i)
-      if (!limbs_canonical<S>(p[i])) well_formed = false;
-    o += cnt;
-    return p;
-  };
-  struct Inst {
-    const aff_t *pre, *rest;
-    const fe_t* pub;
-  };
-  const aff_t* comm_shared = pts(rows_sh);
-  std::vector<Inst> steps(n);
-  for (auto& u : steps) {
-    u.pre = pts(rows_pre);
-    u.rest = pts(rows_rest);
-    u.pub = fes(dpub);
-  }
-  Inst core;
-  core.pre = pts(rows_pre);
-  core.rest = pts(rows_rest);
-  core.pub = fes(cpub);
-  const aff_t delta = *pts(1), beta = *pts(1);
-  const fe_t* z_vec = fes(CW);
-  const fe_t z_delta = *fes(1), z_beta = *fes(1);
-  std::vector<const aff_t*> vcomm(vs.num_rounds);
-  for (size_t r = 0; r < vs.num_rounds; ++r) vcomm[r] = pts(vs.vars_padded[r] / VW);
-  const fe_t* vpub = fes(vs.num_public);
-  std::vector<const fe_t*> vchal(vs.num_rounds);
-  for (size_t r = 0; r < vs.num_rounds; ++r) vchal[r] = fes(vs.chals_per_round[r]);
-  const aff_t* comm_T = pts(vcons / VW);
-  const aff_t* rnd_comm_W = pts(vnv / VW);
-  const aff_t* rnd_comm_E = pts(vcons / VW);
-  const fe_t rnd_u = *fes(1);
-  const fe_t* rnd_X = fes(vio);
-  const fe_t* v_outer = fes(3 * vlx);
-  const fe_t* v_claims = fes(3);
-  const fe_t* v_inner = fes(2 * vly);
-  const fe_t* v_W = fes(VW);
-  const fe_t blind_vW = *fes(1);
-  const fe_t* v_E = fes(VW);
-  const fe_t blind_vE = *fes(1);
-  if (4 * o != nwords) throw Error(SP_ERR_INTERNAL, "nn_verify: layout / proof_words disagree");
-  if (!well_formed) return 1;
-
+  if (!well_formed(lay, words)) return 1;
+  const NNProofView pv = lay.view(words);
+  const aff_t *comm_shared = pv.comm_shared, *comm_T = pv.comm_T, *rnd_comm_W = pv.rnd_comm_W, *rnd_comm_E = pv.rnd_comm_E;
+  const fe_t *z_vec = pv.z_vec, *vpub = pv.vpub, *rnd_X = pv.rnd_X, *v_outer = pv.v_outer, *v_claims = pv.v_claims, *v_inner = pv.v_inner, *v_W = pv.v_W, *v_E = pv.v_E;
+  const aff_t delta = *pv.delta, beta = *pv.beta;
+  const fe_t z_delta = *pv.z_delta, z_beta = *pv.z_beta, rnd_u = *pv.rnd_u, blind_vW = *pv.blind_vW, blind_vE = *pv.blind_vE;
   lap("parse + encoding checks");
   // <z_vec, ck> (ipa.rs:196-203) depends on nothing but the proof: its device part runs under everything that follows
-  struct ZJob {
-    sp_ctx* ctx;
-    const sp_ck* key;
-    sp_msm_job* job = nullptr;
-    ~ZJob() {
-      uint64_t sink[8];
-      if (job) sp_msm_ck_finish(ctx, key, job, nullptr, sink);  // an early return still owns the job
-    }
-  } zjob{ctx, pk.ck};
+  ZJob zjob;
+  zjob.ctx = ctx;
+  zjob.key = pk.ck;
   ck(sp_msm_ck_begin(ctx, pk.ck, u64p(z_vec), CW, &zjob.job), "<z, ck> (begin)");
 
   // regular instances: comm_W = shared | precommitted | rest rows, X = the public values (src/r1cs/mod.rs:1723-1760)
-  auto regular = [&](const Inst& u) {
+  auto regular = [&](const NNProofView::Inst& u, size_t my_pre, size_t my_rest) {
     std::vector<aff_t> c(rows);
     std::copy(comm_shared, comm_shared + rows_sh, c.begin());
-    std::copy(u.pre, u.pre + rows_pre, c.begin() + rows_sh);
-    std::copy(u.rest, u.rest + rows_rest, c.begin() + rows_sh + rows_pre);
+    std::copy(u.pre, u.pre + my_pre, c.begin() + rows_sh);
+    std::copy(u.rest, u.rest + my_rest, c.begin() + rows_sh + my_pre);
     return c;
   };
   size_t np = 2;
@@ -1519,14 +1261,14 @@ static int nn_verify(const NNZkKey& pk, const uint64_t* words, size_t nwords) {
   if (((size_t)1 << nb) != np) throw Error(SP_ERR_INTERNAL, "nn_verify: a single step instance is not driven by this layer");
   auto inst = [&](size_t i) { return i < n ? i : 0; };  // padding clones instance 0 (:549-552)
   std::vector<std::vector<aff_t>> Ucomm(n);
-  for (size_t i = 0; i < n; ++i) Ucomm[i] = regular(steps[i]);
-  const std::vector<aff_t> core_comm = regular(core);
-  const std::vector<fe_t> core_X(core.pub, core.pub + cpub);
+  for (size_t i = 0; i < n; ++i) Ucomm[i] = regular(pv.steps[i], lay.rows_pre, lay.rows_rest);
+  const std::vector<aff_t> core_comm = regular(pv.core, lay.rows_pre_c, lay.rows_rest_c);
+  const std::vector<fe_t> core_X(pv.core.pub, pv.core.pub + cpub);
   // the verifier-circuit instance in its regular form: comm_W = the rounds' rows, X = challenges | public values; the challenges are checked against the
   // transcript below, what is computed from them before that is only used after the check
-  const std::vector<aff_t> Uv_comm(vcomm[0], vcomm[0] + vnv / VW);  // the rounds are consecutive in the layout
+  const std::vector<aff_t> Uv_comm(pv.vcomm[0], pv.vcomm[0] + vnv / VW);  // the rounds are consecutive in the layout
   std::vector<fe_t> Uv_X;
-  for (size_t r = 0; r < vs.num_rounds; ++r) Uv_X.insert(Uv_X.end(), vchal[r], vchal[r] + vs.chals_per_round[r]);
+  for (size_t r = 0; r < vs.num_rounds; ++r) Uv_X.insert(Uv_X.end(), pv.vchal[r], pv.vchal[r] + vs.chals_per_round[r]);
   Uv_X.insert(Uv_X.end(), vpub, vpub + vs.num_public);
   const size_t num_chal = nb + nx + 1 + ny;
   if (vs.total_challenges != num_chal || vs.num_public != 6) return 2;
@@ -1537,7 +1279,7 @@ static int nn_verify(const NNZkKey& pk, const uint64_t* words, size_t nwords) {
   ck(sp_weights_from_r(u64p(r_b), nb, np, u64p(wts.data())), "weights_from_r");
   std::vector<fe_t> Xf(dpub, fe_zero());
   for (size_t i = 0; i < np; ++i)
-    for (size_t j = 0; j < dpub; ++j) Xf[j] = fe_add<S>(Xf[j], fe_mul<S>(wts[i], steps[inst(i)].pub[j]));
+    for (size_t j = 0; j < dpub; ++j) Xf[j] = fe_add<S>(Xf[j], fe_mul<S>(wts[i], pv.steps[inst(i)].pub[j]));
   std::vector<aff_t> folded_comm(rows), fold_bases(rows * np);
   for (size_t rr = 0; rr < rows; ++rr)
     for (size_t i = 0; i < np; ++i) fold_bases[rr * np + i] = Ucomm[inst(i)][rr];
@@ -1582,7 +1324,7 @@ static int nn_verify(const NNZkKey& pk, const uint64_t* words, size_t nwords) {
   Tr tr(ctx, "neutronnova_prove");
   tr.absorb("vk", pk.vk_digest, 32);
   absorb_instance(tr, "core_instance", core_comm, core_X);
-  for (size_t i = 0; i < np; ++i) absorb_instance(tr, "U", Ucomm[inst(i)], std::vector<fe_t>(steps[inst(i)].pub, steps[inst(i)].pub + dpub));
+  for (size_t i = 0; i < np; ++i) absorb_instance(tr, "U", Ucomm[inst(i)], std::vector<fe_t>(pv.steps[inst(i)].pub, pv.steps[inst(i)].pub + dpub));
   {
     uint8_t zero_be[32] = {0};  // T = 0 (:556-557)
     tr.absorb("T", zero_be, 32);
@@ -1593,10 +1335,10 @@ static int nn_verify(const NNZkKey& pk, const uint64_t* words, size_t nwords) {
   lap("instances absorbed");
   // U_verifier.validate (src/r1cs/mod.rs:1808-1834): the per-round commitments reproduce the challenges the instance carries
   for (size_t round = 0; round < vs.num_rounds; ++round) {
-    const std::vector<uint8_t> b = commitment_bytes(vcomm[round], vs.vars_padded[round] / VW);
+    const std::vector<uint8_t> b = commitment_bytes(pv.vcomm[round], vs.vars_padded[round] / VW);
     tr.absorb("comm_w_round", b.data(), b.size());
     for (size_t i = 0; i < vs.chals_per_round[round]; ++i)
-      if (!fe_eq(tr.squeeze("challenge"), vchal[round][i])) return 2;
+      if (!fe_eq(tr.squeeze("challenge"), pv.vchal[round][i])) return 2;
   }
   lap("vc instance replayed");
   // NovaNIFS::verify (src/nifs.rs:65-77): the random relaxed instance folded with the verifier-circuit instance
@@ -1631,14 +1373,14 @@ static int nn_verify(const NNZkKey& pk, const uint64_t* words, size_t nwords) {
       if (nvr == 0) {
         comm_LZ = comm[0];
       } else {
-        const std::vector<fe_t> L = eq_evals(point, nvr);
+        const std::vector<fe_t> L = eq_evals_host(point, nvr);
         if (comm.size() > L.size()) return false;
         ck(sp_msm(ctx, u64p(L.data()), u64p(&comm[0].x), comm.size(), u64p(&comm_LZ.x)), "direct opening: <L, rows>");
       }
       aff_t expected;
       ck(sp_hyrax_commit_small(ctx, pk.vc_ck, u64p(v), VW, u64p(&cb), u64p(&expected.x)), "direct opening: <v, ck> + cb h");
       if (!fe_eq(comm_LZ.x, expected.x) || !fe_eq(comm_LZ.y, expected.y)) return false;
-      const std::vector<fe_t> R = eq_evals(point + nvr, npoint - nvr);
+      const std::vector<fe_t> R = eq_evals_host(point + nvr, npoint - nvr);
       fe_t e = fe_zero();
       for (size_t i = 0; i < VW; ++i) e = fe_add<S>(e, fe_mul<S>(v[i], R[i]));
       *eval = e;
@@ -1661,7 +1403,7 @@ static int nn_verify(const NNZkKey& pk, const uint64_t* words, size_t nwords) {
     const fe_t claim_inner = fe_add<S>(fe_add<S>(v_claims[0], fe_mul<S>(vr, v_claims[1])), fe_mul<S>(vr2, fe_sub<S>(v_claims[2], eval_E)));
     if (!sumcheck_verify(tr, claim_inner, vly, 2, v_inner, &claim_inner_final, &vry)) return 4;
     if (!verify_direct(fU_W, v_W, blind_vW, vry.data() + 1, vly - 1, &eval_W)) return 4;
-    const std::vector<fe_t> Tx = eq_evals(vrx.data(), vlx), Ty = eq_evals(vry.data(), vly);
+    const std::vector<fe_t> Tx = eq_evals_host(vrx.data(), vlx), Ty = eq_evals_host(vry.data(), vly);
     fe_t eval_Z = fe_add<S>(fe_mul<S>(fe_sub<S>(one, vry[0]), eval_W), fe_mul<S>(fU_u, Ty[vnv]));
     for (size_t j = 0; j < vio; ++j) eval_Z = fe_add<S>(eval_Z, fe_mul<S>(fU_X[j], Ty[vnv + 1 + j]));
     fe_t em[3];  // evaluate_with_tables on the verifier-circuit matrices (spartan_relaxed.rs:44-67)
@@ -1701,7 +1443,7 @@ static int nn_verify(const NNZkKey& pk, const uint64_t* words, size_t nwords) {
     }
     fe_t eq_rho = one;
     for (size_t i = 0; i < nb; ++i) eq_rho = fe_mul<S>(eq_rho, fe_add<S>(fe_mul<S>(rhos[i], r_b[i]), fe_mul<S>(fe_sub<S>(one, rhos[i]), fe_sub<S>(one, r_b[i]))));
-    if (!fe_eq(pub[0], tau_at_rx) || !fe_eq(pub[1], eval_X(Xf.data(), dpub)) || !fe_eq(pub[2], eval_X(core.pub, cpub)) || !fe_eq(pub[3], eq_rho) || !fe_eq(pub[4], q_step) ||
+    if (!fe_eq(pub[0], tau_at_rx) || !fe_eq(pub[1], eval_X(Xf.data(), dpub)) || !fe_eq(pub[2], eval_X(pv.core.pub, cpub)) || !fe_eq(pub[3], eq_rho) || !fe_eq(pub[4], q_step) ||
         !fe_eq(pub[5], q_core))
       return 5;
   }
@@ -1717,7 +1459,7 @@ static int nn_verify(const NNZkKey& pk, const uint64_t* words, size_t nwords) {
     fold_commitments(ctx);
   ck(sp_fold_commitments2(ctx, u64p(&folded_comm[0].x), u64p(&core_comm[0].x), rows, u64p(&c_eval), u64p(&comm[0].x)), "fold_commitments");
   aff_t comm_eval;
-  ck(sp_fold_commitments2(ctx, u64p(&vcomm[commit_round][0].x), u64p(&vcomm[commit_round + 1][0].x), 1, u64p(&c_eval), u64p(&comm_eval.x)), "fold eval commitments");
+  ck(sp_fold_commitments2(ctx, u64p(&pv.vcomm[commit_round][0].x), u64p(&pv.vcomm[commit_round + 1][0].x), 1, u64p(&c_eval), u64p(&comm_eval.x)), "fold eval commitments");
   {
     const std::vector<uint8_t> b = commitment_bytes(comm.data(), rows);
     tr.absorb("poly_com", b.data(), b.size());
@@ -1728,10 +1470,10 @@ static int nn_verify(const NNZkKey& pk, const uint64_t* words, size_t nwords) {
   std::vector<fe_t> R;
   if (nvr == 0) {
     comm_LZ = comm[0];
-    R = eq_evals(point, npoint);
+    R = eq_evals_host(point, npoint);
   } else {
-    const std::vector<fe_t> L = eq_evals(point, nvr);
-    R = eq_evals(point + nvr, npoint - nvr);
+    const std::vector<fe_t> L = eq_evals_host(point, nvr);
+    R = eq_evals_host(point + nvr, npoint - nvr);
     if (rows < L.size()) return 6;
     ck(sp_msm(ctx, u64p(L.data()), u64p(&comm[0].x), L.size(), u64p(&comm_LZ.x)), "comm_LZ");
   }
@@ -1874,7 +1616,7 @@ void nnz_pk_info(void* pk_, uint64_t out[8], uint8_t digest[32]) {
   memcpy(out, v, sizeof v);
   memcpy(digest, pk->vk_digest, 32);
 }
-size_t nnz_proof_words(void* pk_) { return proof_words(*(NNZkKey*)pk_); }
+size_t nnz_proof_words(void* pk_) { return ((NNZkKey*)pk_)->layout.words(); }
 // prep_prove with the step / core witnesses generated on the device (see nn_prep_prove_sha256): blocks = n x 64 bytes
 int nnz_prep_prove_sha256(void* pk, const sp_sha256_plan* plan, const uint8_t* blocks, size_t n, int is_small, const uint8_t* tape, size_t tape_blocks, size_t* tape_used,
                           void** out_ps) {
@@ -1949,7 +1691,7 @@ int nnz_prove_reference_order(void* pk, void* ps, const uint8_t* tape, size_t ta
 // NeutronNovaZkSNARK as bincode bytes (the reference's serde framing; include/spartan_hip.h "wire formats"). `_to_bytes`: out may be NULL to learn *len.
 int nnz_proof_to_bytes(void* pk, const uint64_t* words, size_t nwords, uint8_t* out, size_t cap, size_t* len) {
   try {
-    std::vector<uint8_t> b = nn_proof_to_bytes(*(NNZkKey*)pk, words, nwords);
+    std::vector<uint8_t> b = ((NNZkKey*)pk)->layout.to_bytes(words, nwords);
     *len = b.size();
     if (out) {
       if (cap < b.size()) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "byte buffer too small");
@@ -1962,7 +1704,7 @@ int nnz_proof_to_bytes(void* pk, const uint64_t* words, size_t nwords, uint8_t* 
 }
 int nnz_proof_from_bytes(void* pk, const uint8_t* bytes, size_t n, uint64_t* out_words, size_t cap_words) {
   try {
-    std::vector<uint64_t> w = nn_proof_from_bytes(*(NNZkKey*)pk, bytes, n);
+    std::vector<uint64_t> w = ((NNZkKey*)pk)->layout.from_bytes(bytes, n);
     if (cap_words < w.size()) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "word buffer too small");
     memcpy(out_words, w.data(), 8 * w.size());
     return 0;
@@ -1975,7 +1717,7 @@ int nnz_verify_bytes(void* pk, const uint8_t* bytes, size_t n) {
   try {
     std::vector<uint64_t> w;
     try {
-      w = nn_proof_from_bytes(*(NNZkKey*)pk, bytes, n);
+      w = ((NNZkKey*)pk)->layout.from_bytes(bytes, n);
     } catch (const Error& e) {
       if (e.code != SP_ERR_INVALID_INPUT_LENGTH) throw;
       ss_set_error(e.what());

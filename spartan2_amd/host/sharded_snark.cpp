@@ -22,7 +22,7 @@
 #include <mutex>
 
 #include "comm.hpp"
-#include "snark_common.hpp"
+#include "proof_layout.hpp"
 
 namespace spartan2 {
 
@@ -282,7 +282,7 @@ static void gather_slices(sp_ctx* ctx, Comm& comm, ShardedPrep& ps, sp_table* co
   ck(sp_ctx_synchronize(ctx), "synchronize");  // gS is reused by the next table / call
 }
 
-SpartanProofBuf sharded_prove(const ShardedKey& pk, ShardedPrep& ps, const uint64_t* publics_u64, size_t npub, Tape& tape, double phase_ms[8]) {
+ProofBuf sharded_prove(const ShardedKey& pk, ShardedPrep& ps, const uint64_t* publics_u64, size_t npub, Tape& tape, double phase_ms[8]) {
   const sp_dims& d = pk.dims;
   sp_ctx* ctx = pk.ctx;
   Comm& comm = *pk.comm;
@@ -556,7 +556,7 @@ SpartanProofBuf sharded_prove(const ShardedKey& pk, ShardedPrep& ps, const uint6
   const double t_mv = now_ms();
   lap("helper_start_and_tau");
 
-  SpartanProofBuf proof;
+  ProofBuf proof;
   for (const aff_t& a : comm_W) proof.pp(a);
   for (const fe_t& f : publics) proof.pf(f);
   // outer sum-check on slices: ell - k local rounds with one exchange each, then k rounds on the gathered 2^k-element tables
@@ -946,6 +946,7 @@ int ssd_setup(sp_ctx* ctx, void* comm, size_t num_cons, size_t num_shared, size_
   }
 }
 void ssd_pk_free(void* pk) { delete (ShardedKey*)pk; }
+size_t ssd_proof_words(void* pk_) { return SpartanLayout(((ShardedKey*)pk_)->dims, ((ShardedKey*)pk_)->num_vars).words(); }
 void ssd_pk_info(void* pk_, uint64_t dims_out[10]) { memcpy(dims_out, &((ShardedKey*)pk_)->dims, sizeof(sp_dims)); }
 int ssd_prep_prove(void* pk, const uint64_t* witness_u64, size_t n, int is_small, const uint8_t* tape, size_t tape_blocks, size_t* tape_used, void** out_ps) {
   try {
@@ -962,7 +963,7 @@ int ssd_prove(void* pk, void* ps, const uint64_t* publics_u64, size_t npub, cons
               size_t out_cap, double* phase_ms /* 8 */) {
   try {
     Tape t{tape, tape_blocks};
-    SpartanProofBuf pf = sharded_prove(*(ShardedKey*)pk, *(ShardedPrep*)ps, publics_u64, npub, t, phase_ms);
+    ProofBuf pf = sharded_prove(*(ShardedKey*)pk, *(ShardedPrep*)ps, publics_u64, npub, t, phase_ms);
     if (pf.words.size() > out_cap) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "proof buffer too small");
     memcpy(out_words, pf.words.data(), pf.words.size() * 8);
     if (tape_used) *tape_used = t.pos;

@@ -215,12 +215,29 @@ inline bool limbs_canonical(const fe_t& v) {
 }
 
 
-struct SpartanProofBuf {  // SpartanSNARK (src/spartan.rs:130-138) in the canonical flat layout of DESIGN.md
+struct ProofBuf {  // a proof in the canonical flat layout of DESIGN.md section 4, appended field by field
   std::vector<uint64_t> words;
   void pf(const fe_t& f) { words.insert(words.end(), u64p(&f), u64p(&f) + 4); }
   void pp(const aff_t& a) {
     pf(a.x);
     pf(a.y);
+  }
+  void pc(const std::vector<aff_t>& c) {
+    for (const aff_t& a : c) pp(a);
+  }
+};
+
+// <z_vec, ck> of the IPA check (ipa.rs:196-203) depends on nothing but the proof: a verifier starts its device part before the transcript work
+struct ZJob {
+  sp_ctx* ctx = nullptr;
+  const sp_ck* key = nullptr;
+  sp_msm_job* job = nullptr;
+  ZJob() = default;
+  ZJob(const ZJob&) = delete;
+  ZJob& operator=(const ZJob&) = delete;
+  ~ZJob() {
+    uint64_t sink[8];
+    if (job) sp_msm_ck_finish(ctx, key, job, nullptr, sink);  // an early return still owns the job
   }
 };
 

@@ -15,7 +15,7 @@
 #include <future>
 #include <memory>
 
-#include "snark_common.hpp"
+#include "proof_layout.hpp"
 
 // What ss_verify_batch / ss_verify_bytes_batch report beside the codes (C layout: four 64-bit words; host.py VerifyBatchInfo mirrors it). The ss_* surface
 // of this library has no header of its own: its types are declared here, at global scope, as a C caller would repeat them.
@@ -36,6 +36,7 @@ struct SpartanProverKey {  // src/spartan.rs:30-58
   sp_shape* S = nullptr;
   sp_ck *ck = nullptr, *ck_s = nullptr;
   sp_dims dims;
+  SpartanLayout layout;  // of a proof under this key (proof_layout.hpp)
   size_t num_vars = 0, num_extra = 0, num_cols = 0;
   uint8_t vk_digest[32];
   std::vector<aff_t> gens, gens_s;
@@ -152,6 +153,7 @@ SpartanProverKey* setup(sp_ctx* ctx, const R1CSIntView& R) {
     PaddedShape P = pad_shape(R);
     pk->dims = P.dims;
     pk->num_vars = P.num_vars();
+    pk->layout = SpartanLayout(P.dims, pk->num_vars);
     pk->num_extra = 1 + P.dims.num_public + P.dims.num_challenges;
     pk->num_cols = P.num_cols();
     sp_csr cs[3];
@@ -303,9 +305,9 @@ SpartanPrepSNARK* prep_prove_sha256(const SpartanProverKey& pk, const sp_sha256_
 // `synth`: circuit.synthesize(.., Some(&challenges)) for circuits with verifier challenges (bellpepper/r1cs.rs:443-461): receives the challenges and
 // writes the num_rest_unpadded values of the rest segment (Montgomery limbs); non-zero return = SynthesisError
 typedef int (*ss_rest_hook)(void* user, const uint64_t* challenges, size_t num_challenges, uint64_t* out_rest);
-SpartanProofBuf prove_reference_order(const SpartanProverKey& pk, SpartanPrepSNARK& ps, const uint64_t* publics_u64, size_t npub, Tape& tape, PhaseTimes* pt, ss_rest_hook synth,
+ProofBuf prove_reference_order(const SpartanProverKey& pk, SpartanPrepSNARK& ps, const uint64_t* publics_u64, size_t npub, Tape& tape, PhaseTimes* pt, ss_rest_hook synth,
                                       void* synth_user);
-SpartanProofBuf prove(const SpartanProverKey& pk, SpartanPrepSNARK& ps, const uint64_t* publics_u64, size_t npub, Tape& tape, PhaseTimes* pt, ss_rest_hook synth = nullptr,
+ProofBuf prove(const SpartanProverKey& pk, SpartanPrepSNARK& ps, const uint64_t* publics_u64, size_t npub, Tape& tape, PhaseTimes* pt, ss_rest_hook synth = nullptr,
                       void* synth_user = nullptr) {
   if (ps.flags & FLAG_REFERENCE_ORDER) return prove_reference_order(pk, ps, publics_u64, npub, tape, pt, synth, synth_user);
   const sp_dims& d = pk.dims;
@@ -718,7 +720,7 @@ SpartanProofBuf prove(const SpartanProverKey& pk, SpartanPrepSNARK& ps, const ui
 
   const double t_mv = now_ms();
 
-  SpartanProofBuf proof;
+  ProofBuf proof;
   for (const aff_t& a : comm_W) proof.pp(a);
   for (const fe_t& f : publics) proof.pf(f);
   for (const fe_t& f : challenges) proof.pf(f);  // SplitR1CSInstance carries them (src/r1cs/mod.rs:1423-1437)
@@ -1066,7 +1068,7 @@ SpartanProofBuf prove(const SpartanProverKey& pk, SpartanPrepSNARK& ps, const ui
 // committed are used (the shim keeps them in its PrepSNARK and names them when it announces the opening). Whatever overlap there is
 // happens BELOW the ABI (the round loops' launch-ahead and resident tails, sp_hyrax_prove's two walks beside its hashing). This is the time an unchanged
 // spartan.rs gets from a shim that binds include/spartan_hip.h; the proof is the same bytes as prove()'s.
-SpartanProofBuf prove_reference_order(const SpartanProverKey& pk, SpartanPrepSNARK& ps, const uint64_t* publics_u64, size_t npub, Tape& tape, PhaseTimes* pt, ss_rest_hook synth,
+ProofBuf prove_reference_order(const SpartanProverKey& pk, SpartanPrepSNARK& ps, const uint64_t* publics_u64, size_t npub, Tape& tape, PhaseTimes* pt, ss_rest_hook synth,
                                       void* synth_user) {
   const sp_dims& d = pk.dims;
   sp_ctx* ctx = pk.ctx;
@@ -1162,7 +1164,7 @@ SpartanProofBuf prove_reference_order(const SpartanProverKey& pk, SpartanPrepSNA
   ck(sp_multiply_vec_incremental(ctx, pk.S, ps.z, ps.caz, ps.cbz, ps.ccz, ps.az, ps.bz, ps.cz), "multiply_vec_incremental");
   lap("multiply_vec_incremental");
   const double t_mv = now_ms();
-  SpartanProofBuf proof;
+  ProofBuf proof;
   for (const aff_t& a : comm_W) proof.pp(a);
   for (const fe_t& f : publics) proof.pf(f);
   for (const fe_t& f : challenges) proof.pf(f);
@@ -1288,20 +1290,6 @@ bool is_sat(const SpartanProverKey& pk, SpartanPrepSNARK& ps, const uint64_t* pu
 //   (c) opening_prepare_host, opening_comm_LZ, opening_challenge  the opening up to the IPA's challenge r: R and <z_vec, R> (can fail check 6), comm_LZ, comm_eval_W
 //       opening_check    the two group equations of InnerProductArgumentLinear::verify for ONE proof: check 6
 
-// <z_vec, ck> (ipa.rs:196-203) depends on nothing but the proof: verify() starts its device part before the transcript work
-struct ZJob {
-  sp_ctx* ctx = nullptr;
-  const sp_ck* key = nullptr;
-  sp_msm_job* job = nullptr;
-  ZJob() = default;
-  ZJob(const ZJob&) = delete;
-  ZJob& operator=(const ZJob&) = delete;
-  ~ZJob() {
-    uint64_t sink[8];
-    if (job) sp_msm_ck_finish(ctx, key, job, nullptr, sink);  // an early return still owns the job
-  }
-};
-
 struct VerifyState {  // one proof between the steps
   // views into the caller's words
   const aff_t* comm_W = nullptr;
@@ -1324,52 +1312,21 @@ struct VerifyState {  // one proof between the steps
 static int verify_step_a(const SpartanProverKey& pk, const uint64_t* words, size_t nwords, bool start_z, VerifyState& st) {
   sp_ctx* ctx = pk.ctx;
   const sp_dims& d = pk.dims;
-
-  const size_t W_ = DEFAULT_COMMITMENT_WIDTH, N = d.num_cons, M = pk.num_vars;
-  const size_t rows_sh = d.num_shared_unpadded ? (d.num_shared + W_ - 1) / W_ : 0, rows_pre = d.num_precommitted_unpadded ? (d.num_precommitted + W_ - 1) / W_ : 0;
-  const size_t rows_rest = (d.num_rest + W_ - 1) / W_, rows = rows_sh + rows_pre + rows_rest;
-  const size_t lx = log2_ceil(N), ly = log2_ceil(M) + 1, nz = M < W_ ? M : W_;
-  if (nwords != 8 * rows + 4 * (d.num_public + d.num_challenges) + 12 * lx + 12 + 8 * ly + 8 + 16 + 4 * nz + 8) return 1;
-  const fe_t* w = reinterpret_cast<const fe_t*>(words);
-  const aff_t* comm_W = reinterpret_cast<const aff_t*>(w);
-  w += 2 * rows;
-  const fe_t* publics = w;
-  w += d.num_public;
-  const fe_t* challenges = w;
-  w += d.num_challenges;
-  const fe_t* outer = w;
-  w += 3 * lx;
-  const fe_t* claims = w;
-  w += 3;
-  const fe_t* inner = w;
-  w += 2 * ly;
-  const fe_t eval_W = w[0], blind_eval_W = w[1];
-  w += 2;
-  const aff_t delta = *reinterpret_cast<const aff_t*>(w), beta = *reinterpret_cast<const aff_t*>(w + 2);
-  w += 4;
-  const fe_t* z_vec = w;
-  w += nz;
-  const fe_t z_delta = w[0], z_beta = w[1];
-  {
-    const fe_t* all = reinterpret_cast<const fe_t*>(words);
-    const size_t n_el = nwords / 4, p0 = 2 * rows, p1 = p0 + d.num_public + d.num_challenges + 3 * lx + 3 + 2 * ly + 2;  // [0, p0): comm_W coordinates; [p1, p1 + 4): delta, beta
-    for (size_t i = 0; i < n_el; ++i) {
-      const bool coord = i < p0 || (i >= p1 && i < p1 + 4);
-      if (!(coord ? limbs_canonical<B>(all[i]) : limbs_canonical<S>(all[i]))) return 1;
-    }
-  }
-  for (size_t i = 0; i < rows; ++i)
-    if (!aff_on_curve(comm_W[i])) return 1;
-  if (!aff_on_curve(delta) || !aff_on_curve(beta)) return 1;
+  const SpartanLayout& lay = pk.layout;
+  const size_t rows_sh = lay.rows_shared, rows_pre = lay.rows_precommitted, rows_rest = lay.rows_rest, rows = lay.rows(), lx = lay.rounds_x, ly = lay.rounds_y, nz = lay.z_len;
+  if (nwords != lay.words() || !well_formed(lay, words)) return 1;
+  const SpartanProofView pv = lay.view(words);
+  const aff_t* comm_W = pv.comm_W;
+  const fe_t *publics = pv.publics, *challenges = pv.challenges, *outer = pv.outer, *claims = pv.claims, *inner = pv.inner, *z_vec = pv.z_vec;
   st.comm_W = comm_W;
   st.publics = publics;
   st.z_vec = z_vec;
-  st.eval_W = eval_W;
-  st.blind_eval_W = blind_eval_W;
-  st.z_delta = z_delta;
-  st.z_beta = z_beta;
-  st.delta = delta;
-  st.beta = beta;
+  st.eval_W = *pv.eval_W;
+  st.blind_eval_W = *pv.blind_eval_W;
+  st.z_delta = *pv.z_delta;
+  st.z_beta = *pv.z_beta;
+  st.delta = *pv.delta;
+  st.beta = *pv.beta;
   st.rows = rows;
   st.lx = lx;
   st.ly = ly;
@@ -1410,7 +1367,7 @@ static int verify_step_a(const SpartanProverKey& pk, const uint64_t* words, size
   X[0] = one;
   std::copy(publics, publics + d.num_public + d.num_challenges, X.begin() + 1);  // challenges follow the public values in the buffer and in X
   const fe_t eval_X = sparse_poly_evaluate(ly - 1, X, r_y.data() + 1);
-  st.eval_Z = fe_add<S>(fe_mul<S>(fe_sub<S>(one, r_y[0]), eval_W), fe_mul<S>(r_y[0], eval_X));
+  st.eval_Z = fe_add<S>(fe_mul<S>(fe_sub<S>(one, r_y[0]), st.eval_W), fe_mul<S>(r_y[0], eval_X));
   st.r = r;
   st.r2 = r2;
   return 0;
@@ -1872,25 +1829,11 @@ int ss_verify_batch(void* pk, const uint64_t* const* words, const size_t* nwords
     return catch_all();
   }
 }
-// SpartanSNARK's shape-dependent lengths (what the bincode length prefixes of a proof for this key must say)
-static sp_spartan_layout proof_layout(const SpartanProverKey& pk) {
-  const sp_dims& d = pk.dims;
-  sp_spartan_layout L;
-  L.rows_shared = d.num_shared_unpadded ? (d.num_shared + 2047) / 2048 : 0;
-  L.rows_precommitted = d.num_precommitted_unpadded ? (d.num_precommitted + 2047) / 2048 : 0;
-  L.rows_rest = (d.num_rest + 2047) / 2048;
-  L.num_public = d.num_public;
-  L.num_challenges = d.num_challenges;
-  L.rounds_x = log2_ceil(d.num_cons);
-  L.rounds_y = log2_ceil(pk.num_vars) + 1;
-  L.z_len = pk.num_vars < 2048 ? pk.num_vars : 2048;
-  return L;
-}
-void ss_proof_layout(void* pk, sp_spartan_layout* out) { *out = proof_layout(*(SpartanProverKey*)pk); }
+void ss_proof_layout(void* pk, sp_spartan_layout* out) { *out = ((SpartanProverKey*)pk)->layout.wire(); }
 // the proof as bincode bytes of SpartanSNARK (src/spartan.rs:125-137); out may be NULL to learn *len
 int ss_proof_to_bytes(void* pk, const uint64_t* words, size_t nwords, uint8_t* out, size_t cap, size_t* len) {
   try {
-    const sp_spartan_layout L = proof_layout(*(SpartanProverKey*)pk);
+    const sp_spartan_layout L = ((SpartanProverKey*)pk)->layout.wire();
     ck(sp_proof_serialize(&L, words, nwords, out, cap, len), "proof_serialize");
     return 0;
   } catch (...) {
@@ -1905,7 +1848,7 @@ int ss_verify_bytes(void* pk_, const uint8_t* bytes, size_t n, uint64_t* out_pub
     sp_spartan_layout L;
     size_t nwords = 0;
     if (sp_proof_deserialize(bytes, n, &L, nullptr, 0, &nwords) != SP_OK) return 1;
-    const sp_spartan_layout want = proof_layout(*pk);
+    const sp_spartan_layout want = pk->layout.wire();
     if (memcmp(&L, &want, sizeof L) != 0) return 1;
     std::vector<uint64_t> words(nwords);
     ck(sp_proof_deserialize(bytes, n, &L, words.data(), words.size(), &nwords), "proof_deserialize");
@@ -1919,7 +1862,7 @@ int ss_verify_bytes_batch(void* pk_, const uint8_t* const* bytes, const size_t* 
                           ss_verify_batch_info* info) {
   try {
     auto* pk = (SpartanProverKey*)pk_;
-    const sp_spartan_layout want = proof_layout(*pk);
+    const sp_spartan_layout want = pk->layout.wire();
     std::vector<std::vector<uint64_t>> store(count);
     std::vector<const uint64_t*> words(count);
     std::vector<size_t> nwords(count);
@@ -1939,13 +1882,7 @@ int ss_verify_bytes_batch(void* pk_, const uint8_t* const* bytes, const size_t* 
     return catch_all();
   }
 }
-size_t ss_proof_words(void* pk_) {
-  auto* pk = (SpartanProverKey*)pk_;
-  const sp_dims& d = pk->dims;
-  size_t rows = (d.num_shared_unpadded ? (d.num_shared + 2047) / 2048 : 0) + (d.num_precommitted_unpadded ? (d.num_precommitted + 2047) / 2048 : 0) + (d.num_rest + 2047) / 2048;
-  size_t lx = log2_ceil(d.num_cons), ly = log2_ceil(pk->num_vars) + 1, nz = pk->num_vars < 2048 ? pk->num_vars : 2048;
-  return 8 * rows + 4 * (d.num_public + d.num_challenges) + 12 * lx + 12 + 8 * ly + 8 + 16 + 4 * nz + 8;
-}
+size_t ss_proof_words(void* pk) { return ((SpartanProverKey*)pk)->layout.words(); }
 // prove() — writes the proof in the canonical layout; phase_ms[7]: witness_commit, matrix_vector_multiply, outer_sumcheck,
 // prepare_poly_ABC, inner_sumcheck, pcs_prove, total (the reference's span names, src/spartan.rs:267-437)
 int ss_prove_hook(void* pk, void* ps, const uint64_t* publics_u64, size_t npub, const uint8_t* tape, size_t tape_blocks, size_t* tape_used, uint64_t* out_words,
@@ -1960,7 +1897,7 @@ int ss_prove_hook(void* pk, void* ps, const uint64_t* publics_u64, size_t npub, 
   try {
     Tape t{tape, tape_blocks};
     PhaseTimes pt;
-    SpartanProofBuf pf = prove(*(SpartanProverKey*)pk, *(SpartanPrepSNARK*)ps, publics_u64, npub, t, &pt, synth, synth_user);
+    ProofBuf pf = prove(*(SpartanProverKey*)pk, *(SpartanPrepSNARK*)ps, publics_u64, npub, t, &pt, synth, synth_user);
     if (pf.words.size() > out_cap) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "proof buffer too small");
     memcpy(out_words, pf.words.data(), pf.words.size() * 8);
     if (tape_used) *tape_used = t.pos;
@@ -2061,7 +1998,7 @@ int ss_prove_multiplexed(void** pks, void** pss, size_t n_ctx, const uint64_t* p
       fibers[i].body = [=] {
         for (size_t k = 0; k < proofs_each; ++k) {
           Tape t{tape, tape_blocks};
-          SpartanProofBuf pf = prove(*pk, *ps, publics_u64, npub, t, nullptr, nullptr, nullptr);
+          ProofBuf pf = prove(*pk, *ps, publics_u64, npub, t, nullptr, nullptr, nullptr);
           if (pf.words.size() > words_cap) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "proof buffer too small");
           if (k + 1 == proofs_each) memcpy(dst, pf.words.data(), pf.words.size() * 8);
         }

@@ -212,6 +212,20 @@ int sp_sumcheck_cubic3_host(sp_ctx* ctx, const uint64_t claim[4], const uint64_t
                             uint64_t* out_cpolys, uint64_t* out_r, uint64_t out_final[12]);
 int sp_sumcheck_quad_host(sp_ctx* ctx, const uint64_t claim[4], size_t rounds, uint64_t* A, uint64_t* B, sp_transcript* tr, uint64_t* out_cpolys, uint64_t* out_r,
                           uint64_t out_final[8]);
+/* Many sum-checks of one length in lockstep: `count` independent instances of the two device provers over `count` distinct table sets of equal length,
+ * each with its own claim, its own transcript and (cubic) its own taus. One launch computes round i of every instance, the library finishes `count`
+ * round polynomials, absorbs each into its own transcript and hands the `count` challenges to the next launch: one host <-> device round trip per
+ * round for all instances instead of one per instance. For every k the compressed polynomials, the challenges, the final claims, the state of tr[k]
+ * afterwards and element 0 of each bound table are exactly what sp_sumcheck_cubic3 / sp_sumcheck_quad produce on instance k alone; the quadratic form
+ * honours every table's (lo_eff, hi_eff) (sp_table_set_len). Arrays are instance-major: claims count x 4 words, taus count x ell x 4, out_cpolys
+ * count x ell x 12 (cubic) / count x rounds x 8 (quadratic), out_r count x rounds x 4, out_final count x 12 / count x 8.
+ * Refused with SP_ERR_INVALID_INPUT_LENGTH before anything is launched or changed: count == 0 or count > SP_LOCKSTEP_MAX, a null argument (array
+ * entries included), tables of differing length, a length that is not 2^ell / 2^rounds, the same table or the same transcript appearing twice. */
+#define SP_LOCKSTEP_MAX 64
+int sp_sumcheck_cubic3_lockstep(sp_ctx* ctx, size_t count, const uint64_t* claims, const uint64_t* taus, size_t ell, sp_table* const* A, sp_table* const* B,
+                                sp_table* const* C, sp_transcript* const* tr, uint64_t* out_cpolys, uint64_t* out_r, uint64_t* out_final);
+int sp_sumcheck_quad_lockstep(sp_ctx* ctx, size_t count, const uint64_t* claims, size_t rounds, sp_table* const* A, sp_table* const* B, sp_transcript* const* tr,
+                              uint64_t* out_cpolys, uint64_t* out_r, uint64_t* out_final);
 /* EqSumCheckInstance::evaluation_points_zero_check_round0 (src/sumcheck.rs:1163-1271; the round-0 shortcut of the *_zk cubic provers, :595): on a
  * zero-check (claim 0, A o B = C on the hypercube) t(0) vanishes, so only t_inf = sum E(x) (A1 - A0)(B1 - B0) is computed (C is not read) and the
  * evaluations (s(0), s(2), s(3)) of the round polynomial are derived from it (derive_from_claim :1276-1324, or the tau = 0 fallback :1244-1268).

@@ -11,6 +11,7 @@
 #include "core.hpp"
 #include "walk_pool.hpp"
 #include "kernels_poly.hpp"
+#include "sumcheck_round.hpp"
 
 namespace sp {
 static thread_local std::string g_err;
@@ -687,6 +688,8 @@ static int wait_slot(sp_ctx* c, const fe_t* slot, unsigned want, int nvals, fe_t
     sp::relax();
   }
 }
+// the same wait for the other translation units of the library (core.hpp): the round loops here keep calling the static form
+int sp::wait_result_slot(sp_ctx* c, const fe_t* slot, unsigned want, int nvals, fe_t* v, long* spins) { return wait_slot(c, slot, want, nvals, v, false, spins); }
 // the result of a two-round trip of the resident tail (kernels_poly.hpp TAIL_WIDE_VALS): nvals sums, three per result slot from slot 0 on
 static int wait_wide(sp_ctx* c, unsigned want, int nvals, fe_t* v) {
   long spins = 0;
@@ -1152,15 +1155,12 @@ static int tail_check(sp_ctx* c) {
 }
 
 // ---- host-side O(1) glue: UniPoly (src/polys/univariate.rs) ----------------------------------------------------------
+// (UniPoly, two_inv, poly_eval, absorb_poly and the round polynomials of the host-table provers: sumcheck_round.hpp)
+using sp::UniPoly;
+using sp::two_inv;
+using sp::poly_eval;
+using sp::absorb_poly;
 namespace {
-struct UniPoly {
-  fe_t c[4];
-  int n;
-};
-fe_t two_inv() {
-  static fe_t v = fe_inv_vartime<S>(fe_from_u64<S>(2));
-  return v;
-}
 fe_t six_inv() {
   static fe_t v = fe_inv_vartime<S>(fe_from_u64<S>(6));
   return v;
@@ -1191,24 +1191,6 @@ UniPoly from_evals_deg3(const fe_t e[4]) {  // univariate.rs:102-118
   p.c[2] = b;
   p.c[3] = a;
   return p;
-}
-fe_t poly_eval(const UniPoly& p, const fe_t& r) {  // univariate.rs:136-144
-  fe_t ev = p.c[0], pw = r;
-  for (int i = 1; i < p.n; ++i) {
-    ev = fe_add<S>(ev, fe_mul<S>(pw, p.c[i]));
-    pw = fe_mul<S>(pw, r);
-  }
-  return ev;
-}
-// absorb(b"p", &poly): compressed coefficients, to_repr LE each (univariate.rs:182-190)
-void absorb_poly(sp::Transcript& t, const UniPoly& p) {
-  uint8_t buf[32 * 3];
-  int k = 0;
-  sp::fe_to_le_bytes<S>(p.c[0], buf);
-  k = 1;
-  for (int i = 2; i < p.n; ++i) sp::fe_to_le_bytes<S>(p.c[i], buf + 32 * k++);
-  const uint8_t lbl[1] = {'p'};
-  t.absorb(lbl, 1, buf, 32 * k);
 }
 }  // namespace
 
@@ -2415,28 +2397,14 @@ int sp_sumcheck_cubic3_host(sp_ctx* c, const uint64_t claim_[4], const uint64_t*
   const fe_t one = fe_one<S>();
   const uint8_t lbl_c[1] = {'c'};
   // 1 / tau_k by one inversion; zeros stay zero (those rounds take the three-sum form), as in cubic_impl
-  std::vector<fe_t> inv_tau(ell, fe_zero());
-  {
-    std::vector<fe_t> pref(ell);
-    fe_t run = one;
-    for (size_t i = 0; i < ell; ++i) {
-      pref[i] = run;
-      if (!fe_is_zero(taus[i])) run = fe_mul<S>(run, taus[i]);
-    }
-    fe_t inv = fe_inv_vartime<S>(run);
-    for (size_t i = ell; i-- > 0;) {
-      if (fe_is_zero(taus[i])) continue;
-      inv_tau[i] = fe_mul<S>(inv, pref[i]);
-      inv = fe_mul<S>(inv, taus[i]);
-    }
-  }
+  std::vector<fe_t> inv_tau(ell);
+  sp::batch_inv_taus(taus.data(), ell, inv_tau.data());
   HostEqLevels heq;
   heq.build(taus.data(), ell, N / 2 ? N / 2 : 1);
   fe_t claim = load_fe(claim_), p = one;
   for (size_t rnd = 1; rnd <= ell; ++rnd) {
     const size_t n = N >> (rnd - 1), hn = n / 2;
     const fe_t tau = taus[rnd - 1];
-    const fe_t eq0 = fe_sub<S>(one, tau), slope = fe_sub<S>(tau, eq0), eqm1 = fe_sub<S>(eq0, slope);
     const fe_t* E = heq.level(rnd);
     if (!E) return fail(SP_ERR_INTERNAL, "prove_cubic_with_three_inputs (host tables): eq weights");
     fe_t sums[3];
@@ -2454,28 +2422,7 @@ int sp_sumcheck_cubic3_host(sp_ctx* c, const uint64_t claim_[4], const uint64_t*
       for (unsigned pp = 0; pp < np; ++pp)
         for (int k = 0; k < 3; ++k) sums[k] = fe_add<S>(sums[k], q.out[pp][k]);
     }
-    const fe_t t0 = sums[0], tinf = sums[1];
-    const fe_t l_1_p = fe_mul<S>(fe_add<S>(eq0, slope), p);
-    fe_t s_0, s_1, s_leading, s_m1;
-    if (!fe_is_zero(l_1_p)) {  // derive_from_claim (src/sumcheck.rs:1276-1324), the division by l(1) p = tau p through 1 / tau
-      s_0 = fe_mul<S>(fe_mul<S>(eq0, p), t0);
-      s_1 = fe_sub<S>(claim, s_0);
-      s_leading = fe_mul<S>(fe_mul<S>(slope, p), tinf);
-      const fe_t two_sum = fe_add<S>(fe_dbl<S>(tinf), fe_dbl<S>(t0));
-      s_m1 = fe_mul<S>(eqm1, fe_sub<S>(fe_mul<S>(p, two_sum), fe_mul<S>(s_1, inv_tau[rnd - 1])));
-    } else {  // fallback_three_inputs (:1327-1396)
-      s_0 = fe_mul<S>(fe_mul<S>(eq0, p), t0);
-      s_1 = fe_sub<S>(claim, s_0);
-      s_leading = fe_mul<S>(fe_mul<S>(slope, p), tinf);
-      s_m1 = fe_mul<S>(fe_mul<S>(eqm1, p), sums[2]);
-    }
-    const fe_t halfc = two_inv();
-    UniPoly poly;
-    poly.n = 4;
-    poly.c[0] = s_0;
-    poly.c[1] = fe_sub<S>(fe_mul<S>(fe_sub<S>(s_1, s_m1), halfc), s_leading);
-    poly.c[2] = fe_sub<S>(fe_mul<S>(fe_add<S>(s_1, s_m1), halfc), s_0);
-    poly.c[3] = s_leading;
+    const UniPoly poly = sp::cubic3_round_poly(claim, p, tau, inv_tau[rnd - 1], sums);
     absorb_poly(tr->t, poly);
     fe_t r_i;
     if (!tr->t.squeeze<S>(lbl_c, 1, &r_i)) return fail(SP_ERR_INTERNAL_TRANSCRIPT, "transcript round counter overflow");
@@ -2486,7 +2433,7 @@ int sp_sumcheck_cubic3_host(sp_ctx* c, const uint64_t claim_[4], const uint64_t*
     store_fe(out_cpolys + 12 * ri + 8, poly.c[3]);
     claim = poly_eval(poly, r_i);
     for (fe_t* T : {ha, hb, hc}) host_bind_tables(T, 0, 1, n, r_i);
-    p = fe_mul<S>(p, fe_add<S>(fe_sub<S>(fe_sub<S>(one, tau), r_i), fe_dbl<S>(fe_mul<S>(r_i, tau))));
+    p = sp::cubic3_next_p(p, tau, r_i);
   }
   store_fe(out_final, ha[0]);
   store_fe(out_final + 4, hb[0]);
@@ -2508,12 +2455,7 @@ int sp_sumcheck_quad_host(sp_ctx* c, const uint64_t claim_[4], size_t rounds, ui
     const size_t n = N >> round, half = n / 2;
     fe_t sums[2];
     host_quad_eval(ha, hb, half, sums);
-    // BDDT: eval_2 = 2 claim - 3 eval_0 + 2 t_inf and its interpolation (src/sumcheck.rs:211-215, univariate.rs:84-93): c0 = eval_0, c2 = t_inf, c1 = claim - 2 eval_0 - t_inf
-    UniPoly poly;
-    poly.n = 3;
-    poly.c[0] = sums[0];
-    poly.c[1] = fe_sub<S>(fe_sub<S>(claim, fe_dbl<S>(sums[0])), sums[1]);
-    poly.c[2] = sums[1];
+    const UniPoly poly = sp::quad_round_poly(claim, sums);
     absorb_poly(tr->t, poly);
     fe_t r_i;
     if (!tr->t.squeeze<S>(lbl_c, 1, &r_i)) return fail(SP_ERR_INTERNAL_TRANSCRIPT, "transcript round counter overflow");

@@ -248,6 +248,7 @@ struct sp_ctx {
          WS_ROWMAT_PART, WS_ROWMAT_OUT, WS_COMMIT_CANON, WS_COMMIT_FLAGS, WS_COMMIT_ROWS, WS_BASES_TMP, WS_MSM_FOLDED, WS_MSM_DIGITS, WS_NARROW_SCALARS, WS_NARROW_OUT, WS_NARROW_BLINDS, WS_POLYABC_PARTIALS, WS_POLYABC_TICKETS, WS_MSM_TASKS, WS_MSM_PARTIAL,
          WS_SAT_PRODUCTS, WS_SAT_BITMAP, WS_SAT_SUMMARY,  // sp_shape_is_sat / sp_r1cs_residual: Az | Bz | Cz, failure bitmaps, (count, first) pairs
          WS_MATEVAL_PARTIALS, WS_MATEVAL_TICKETS, WS_MATEVAL_OUT,  // sp_shape_matrix_evals_batched: block sums, arrival counters, the 3 results per pair
+         WS_LOCKSTEP_EQ, WS_LOCKSTEP_PARTIALS, WS_LOCKSTEP_PARAMS,  // the lockstep sum-checks: eq pyramids per instance, block partials, taus / (lo_eff, hi_eff) per round
          WS_PER_LANE,
          WS_SLOTS = 2 * WS_PER_LANE };  // lane 1 = the auxiliary stream used by asynchronous MSM jobs
   void* ws_ptr[WS_SLOTS] = {};
@@ -306,6 +307,12 @@ struct sp_ctx {
   }
   void drain_stats();
 };
+
+// capi_core.hip: the bounded wait for one self-validating result slot of the mapped pinned buffer (kernels_poly.hpp slot_store_tag), as the round loops
+// use it for a plain launch - polls the slot's sequence word, gives a launch that does not deliver a stream synchronise and fails instead of hanging
+namespace sp {
+int wait_result_slot(sp_ctx* c, const fe_t* slot, unsigned want, int nvals, fe_t* v, long* spins);
+}
 
 struct sp_table {
   sp_ctx* ctx = nullptr;

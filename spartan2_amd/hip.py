@@ -335,6 +335,50 @@ def sumcheck_quad(ctx, claim, rounds, A: Table, B: Table, tr: Transcript):
     return polys, r, fin
 
 
+LOCKSTEP_MAX = 64  # SP_LOCKSTEP_MAX
+
+
+def _lockstep_lib():
+    L = lib()
+    vpp, sz = ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t
+    L.sp_sumcheck_cubic3_lockstep.argtypes = [ctypes.c_void_p, sz, c_u64p, c_u64p, sz, vpp, vpp, vpp, vpp, c_u64p, c_u64p, c_u64p]
+    L.sp_sumcheck_cubic3_lockstep.restype = ctypes.c_int
+    L.sp_sumcheck_quad_lockstep.argtypes = [ctypes.c_void_p, sz, c_u64p, sz, vpp, vpp, vpp, c_u64p, c_u64p, c_u64p]
+    L.sp_sumcheck_quad_lockstep.restype = ctypes.c_int
+    return L
+
+
+def _handles(objs):
+    """array of handles for a `sp_table* const*` / `sp_transcript* const*` argument (None entries stay NULL)"""
+    return (ctypes.c_void_p * max(len(objs), 1))(*[None if o is None else o.h for o in objs])
+
+
+def sumcheck_cubic3_lockstep(ctx, claims, taus, As, Bs, Cs, trs):
+    """sp_sumcheck_cubic3_lockstep: len(trs) instances of sumcheck_cubic3 over tables of one length, one launch per round for all of them.
+    claims (K, 4), taus (K, ell, 4) -> polys (K, ell, 3, 4), r (K, ell, 4), final claims (K, 3, 4)."""
+    K = len(trs)
+    taus = np.ascontiguousarray(taus, dtype=np.uint64).reshape(max(K, 1), -1, 4)
+    ell = taus.shape[1]
+    claims = np.ascontiguousarray(claims, dtype=np.uint64).reshape(-1, 4)
+    polys = np.zeros((max(K, 1), ell, 3, 4), dtype=np.uint64)
+    r = np.zeros((max(K, 1), ell, 4), dtype=np.uint64)
+    fin = np.zeros((max(K, 1), 3, 4), dtype=np.uint64)
+    check(_lockstep_lib().sp_sumcheck_cubic3_lockstep(ctx.h, K, p64(claims), p64(taus), ell, _handles(As), _handles(Bs), _handles(Cs), _handles(trs), p64(polys), p64(r),
+                                                      p64(fin)))
+    return polys, r, fin
+
+
+def sumcheck_quad_lockstep(ctx, claims, rounds, As, Bs, trs):
+    """sp_sumcheck_quad_lockstep: len(trs) instances of sumcheck_quad -> polys (K, rounds, 2, 4), r (K, rounds, 4), final claims (K, 2, 4)."""
+    K = len(trs)
+    claims = np.ascontiguousarray(claims, dtype=np.uint64).reshape(-1, 4)
+    polys = np.zeros((max(K, 1), rounds, 2, 4), dtype=np.uint64)
+    r = np.zeros((max(K, 1), rounds, 4), dtype=np.uint64)
+    fin = np.zeros((max(K, 1), 2, 4), dtype=np.uint64)
+    check(_lockstep_lib().sp_sumcheck_quad_lockstep(ctx.h, K, p64(claims), rounds, _handles(As), _handles(Bs), _handles(trs), p64(polys), p64(r), p64(fin)))
+    return polys, r, fin
+
+
 def table_dot(ctx, a: Table, b: Table, n: int):
     out = np.zeros(4, dtype=np.uint64)
     check(lib().sp_table_dot(ctx.h, a.h, b.h, ctypes.c_size_t(n), p64(out)))

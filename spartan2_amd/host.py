@@ -117,6 +117,7 @@ class SpartanSNARK:
         self.dims = {k: int(v) for k, v in zip(DIM_NAMES, d)}
         self.vk_digest = dig
         self.ps = None
+        self.batch = []  # prep_prove_batch's states: [(prep state, its public values)]
         self.publics = np.ascontiguousarray(inst.publics, dtype=np.uint64)  # the public values prove() states: the instance's, or prep_prove_sha256's
         self._sha_plan = None
         si = (ctypes.c_uint64 * 8)()
@@ -130,8 +131,7 @@ class SpartanSNARK:
         ps = ctypes.c_void_p()
         _check(lib().ss_prep_prove(self.pk, hip.p64(w), ctypes.c_size_t(len(w)), int(is_small), hip.p8(tape), ctypes.c_size_t(tape.shape[0]), ctypes.byref(used),
                                    ctypes.byref(ps)))
-        if self.ps:
-            lib().ss_prep_free(self.ps)
+        self._free_ps()
         self.ps = ps
         self.publics = np.ascontiguousarray(self.inst.publics, dtype=np.uint64)
         return used.value
@@ -151,11 +151,84 @@ class SpartanSNARK:
         buf = np.frombuffer(msg, dtype=np.uint8).copy()
         _check(lib().ss_prep_prove_sha256(self.pk, self._sha_plan.h, hip.p8(buf), ctypes.c_size_t(len(msg)), int(is_small), hip.p8(tape), ctypes.c_size_t(tape.shape[0]),
                                           ctypes.byref(used), ctypes.byref(ps), hip.p64(pub)))
-        if self.ps:
-            lib().ss_prep_free(self.ps)
+        self._free_ps()
         self.ps = ps
         self.publics = pub
         return used.value
+
+    def _free_ps(self):
+        """drops self.ps; a state of self.batch that a caller assigned to self.ps (to prove it alone) stays with the batch"""
+        if self.ps and not any(self.ps is b or self.ps.value == b.value for b, _ in self.batch):
+            lib().ss_prep_free(self.ps)
+        self.ps = None
+
+    def _free_batch(self):
+        for ps, _ in self.batch:
+            if self.ps is not None and (self.ps is ps or self.ps.value == ps.value):
+                self.ps = None
+            lib().ss_prep_free(ps)
+        self.batch = []
+
+    def prep_prove_batch(self, tapes, witnesses=None, msgs=None, is_small=True):
+        """K prep states on this one key for prove_batch, kept in self.batch with their public values (self.ps is left alone): from `msgs` (K messages
+        of the key's length, through ss_prep_prove_sha256 as prep_prove_sha256), from `witnesses` (K instances of this key's circuit - objects with
+        .witness and .publics - through ss_prep_prove), or K = len(tapes) states of the key's own instance. Returns the blocks used of each tape."""
+        K = len(tapes)
+        if msgs is not None and witnesses is not None:
+            raise ValueError("prep_prove_batch: msgs or witnesses, not both")
+        for name, v in (("msgs", msgs), ("witnesses", witnesses)):
+            if v is not None and len(v) != K:
+                raise ValueError(f"prep_prove_batch: {len(v)} {name} for {K} tapes")
+        self._free_batch()
+        used_all = []
+        for k in range(K):
+            tape = tapes[k]
+            used = ctypes.c_size_t(0)
+            ps = ctypes.c_void_p()
+            if msgs is not None:
+                msg = bytes(msgs[k])
+                if self._sha_plan is None or self._sha_plan.msg_len != len(msg):
+                    from . import frontend
+
+                    self._sha_plan = hip.Sha256Plan(self.ctx, frontend.sha256_witness_plan(len(msg)))
+                pub = np.zeros(256, dtype=np.uint64)
+                buf = np.frombuffer(msg, dtype=np.uint8).copy()
+                _check(lib().ss_prep_prove_sha256(self.pk, self._sha_plan.h, hip.p8(buf), ctypes.c_size_t(len(msg)), int(is_small), hip.p8(tape),
+                                                  ctypes.c_size_t(tape.shape[0]), ctypes.byref(used), ctypes.byref(ps), hip.p64(pub)))
+            else:
+                src = self.inst if witnesses is None else witnesses[k]
+                w = np.ascontiguousarray(src.witness, dtype=np.uint64)
+                pub = np.ascontiguousarray(src.publics, dtype=np.uint64)
+                _check(lib().ss_prep_prove(self.pk, hip.p64(w), ctypes.c_size_t(len(w)), int(is_small), hip.p8(tape), ctypes.c_size_t(tape.shape[0]), ctypes.byref(used),
+                                           ctypes.byref(ps)))
+            self.batch.append((ps, pub))
+            used_all.append(used.value)
+        return used_all
+
+    def prove_batch(self, tapes, states=None):
+        """ss_prove_batch over self.batch (or `states`, a list of (prep state, publics) pairs): one tape per proof -> ([(proof words, blocks used)],
+        {phase: ms of the whole batch}). Proof k is word for word what prove() returns on state k with tape k; the outer and the inner sum-check of all
+        proofs run in lockstep (sp_sumcheck_cubic3_lockstep / sp_sumcheck_quad_lockstep), everything else per proof."""
+        states = self.batch if states is None else states
+        K = len(states)
+        if len(tapes) != K:
+            raise ValueError(f"prove_batch: {len(tapes)} tapes for {K} states")
+        n = lib().ss_proof_words(self.pk)
+        npub = self.dims["num_public"]
+        words = np.zeros((max(K, 1), n), dtype=np.uint64)
+        pubs = np.zeros((max(K, 1), max(npub, 1)), dtype=np.uint64)
+        for k, (_, pub) in enumerate(states):
+            pubs[k, : len(pub)] = pub
+        pubs = np.ascontiguousarray(pubs[:, :npub]) if npub else pubs
+        tapes = [np.ascontiguousarray(t, dtype=np.uint8) for t in tapes]
+        tptr = (hip.c_u8p * max(K, 1))(*[hip.p8(t) for t in tapes])
+        tblk = (ctypes.c_size_t * max(K, 1))(*[t.shape[0] for t in tapes])
+        pss = (ctypes.c_void_p * max(K, 1))(*[ps for ps, _ in states])
+        used = (ctypes.c_size_t * max(K, 1))()
+        ms = (ctypes.c_double * 7)()
+        _check(lib().ss_prove_batch(self.pk, pss, ctypes.c_size_t(K), hip.p64(pubs) if npub else None, ctypes.c_size_t(npub), tptr, tblk, used, hip.p64(words),
+                                    ctypes.c_size_t(n), ms))
+        return [(words[k].copy(), int(used[k])) for k in range(K)], dict(zip(PHASES, list(ms)))
 
     def prep_phases(self):
         """host wall-clock of the last prep_prove's phases, ms (ss_prep_phases)"""
@@ -319,6 +392,8 @@ class SpartanSNARK:
         return self._verify_batch(lib().ss_verify_bytes_batch, ptrs, [len(b) for b in blobs], bs, seed, info)
 
     def close(self):
+        if getattr(self, "batch", None):
+            self._free_batch()
         if self.ps:
             lib().ss_prep_free(self.ps)
             self.ps = None

@@ -104,6 +104,7 @@ struct SpartanPrepSNARK {  // src/spartan.rs:107-124
   size_t rows_shared = 0, rows_precommitted = 0;
   std::vector<uint8_t> comm_shared_bytes, comm_pre_bytes;  // transcript encodings (hyrax_pc.rs:714-729)
   bool is_small = true;
+  const struct SpartanProverKey* key = nullptr;  // the key prep_prove made this state for (prove_batch refuses states of another key)
   sp_transcript* tr_prefix = nullptr;  // FLAG_PREFIX_CACHE: transcript state after the per-instance prefix (see prove)
   std::vector<fe_t> tr_publics;
   sp_transcript* tr_fresh = nullptr;   // default: the prefix re-hashed for this prove by the second helper
@@ -185,6 +186,7 @@ static SpartanPrepSNARK* prep_prove_from(const SpartanProverKey& pk, bool is_sma
     sp_ctx* ctx = pk.ctx;
     const size_t M = pk.num_vars, N = d.num_cons;
     ps->is_small = is_small;
+    ps->key = &pk;
     const double t_begin = now_ms();
     double t_last = t_begin;
     auto phase = [&](int k) {
@@ -1234,6 +1236,225 @@ ProofBuf prove_reference_order(const SpartanProverKey& pk, SpartanPrepSNARK& ps,
   return proof;
 }
 
+// ---- prove_batch: many proofs of one key, the two sum-checks in lockstep -----------------------------------------------------------------------------
+// prove_reference_order restated over `count` prepared states of ONE key, on one thread, phase by phase: every statement of src/spartan.rs:226-466 is
+// run for proof 0 .. count - 1 before the next statement is begun, and the outer and the inner sum-check run as ONE lockstep sum-check each
+// (sp_sumcheck_cubic3_lockstep / sp_sumcheck_quad_lockstep: a launch per round for all proofs, one wait, `count` transcripts fed on this thread).
+// Everything else is the per-proof call prove_reference_order makes - the commitments, the matrix-vector product, poly_ABC and the opening are NOT
+// batched - and the opening is never announced ahead (the announcement is one slot per context). Proof k is word for word what
+// prove(pk, *ps[k], publics[k], tapes[k]) returns and consumes the same tape blocks; every state can be proved again afterwards, alone or in a batch.
+// pt (optional): the batch's wall-clock per phase, in prove's slots.
+static void prove_batch_chunk(const SpartanProverKey& pk, SpartanPrepSNARK* const* pss, size_t count, const uint64_t* publics_u64, size_t npub, Tape* tapes,
+                              ProofBuf* out, size_t first, double* ms) {
+  const sp_dims& d = pk.dims;
+  sp_ctx* ctx = pk.ctx;
+  const size_t M = pk.num_vars, N = d.num_cons, W_ = DEFAULT_COMMITMENT_WIDTH;
+  const size_t num_rounds_x = log2_ceil(N), num_rounds_y = log2_ceil(M) + 1;
+  struct Item {
+    SpartanPrepSNARK* ps = nullptr;
+    Tape* tape = nullptr;
+    std::unique_ptr<Tr> tr;
+    std::vector<fe_t> publics, r_W_rest, r_W;
+    std::vector<aff_t> comm_W;
+    fe_t claims_outer[3], claims_inner[2], r;
+    std::vector<fe_t> r_y;
+    ProofBuf proof;
+  };
+  std::vector<Item> items(count);
+  // every per-proof statement runs through here: an error names the proof it happened in
+  auto each = [&](auto&& fn) {
+    for (size_t k = 0; k < count; ++k) {
+      try {
+        fn(items[k], k);
+      } catch (const Error& e) {
+        throw Error(e.code, "prove_batch: proof " + std::to_string(first + k) + ": " + e.what());
+      }
+    }
+  };
+  double t_last = now_ms();
+  auto phase = [&](int slot) {
+    const double t = now_ms();
+    if (ms) ms[slot] += t - t_last;
+    t_last = t;
+  };
+  const size_t rows_rest = (d.num_rest + W_ - 1) / W_;
+  // :226-236 transcript, vk, public values; r1cs_instance_and_witness (src/bellpepper/r1cs.rs:411-540)
+  each([&](Item& it, size_t k) {
+    it.ps = pss[k];
+    it.tape = &tapes[k];
+    it.publics.resize(npub);
+    for (size_t i = 0; i < npub; ++i) it.publics[i] = fe_from_u64<S>(publics_u64[k * npub + i]);
+    it.tr.reset(new Tr(ctx, "SpartanSNARK"));
+    ck(sp_transcript_set_async(it.tr->t, 1), "transcript");
+    it.tr->absorb("vk", pk.vk_digest, 32);
+    it.tr->absorb_scalars("public_values", it.publics.data(), npub);
+    if (it.ps->rows_shared) it.tr->absorb("comm_W_shared", it.ps->comm_shared_bytes.data(), it.ps->comm_shared_bytes.size());
+    if (it.ps->rows_precommitted) it.tr->absorb("comm_W_precommitted", it.ps->comm_pre_bytes.data(), it.ps->comm_pre_bytes.size());
+  });
+  // PCS::blind (r1cs.rs:466)
+  each([&](Item& it, size_t) {
+    it.r_W_rest.resize(rows_rest);
+    for (auto& b : it.r_W_rest) b = it.tape->next();
+  });
+  // commit_zeros (:467-469) or the rest commitment, and its absorb; combine_blinds (r1cs.rs:515-524)
+  each([&](Item& it, size_t) {
+    SpartanPrepSNARK& ps = *it.ps;
+    const size_t rows_pre = ps.comm_W_fixed.size();
+    it.comm_W.resize(rows_pre + rows_rest);
+    std::copy(ps.comm_W_fixed.begin(), ps.comm_W_fixed.end(), it.comm_W.begin());
+    if (rows_rest && d.num_rest_unpadded == 0) ck(sp_fixed_base_mul_h(ctx, pk.ck, u64p(it.r_W_rest.data()), rows_rest, u64p(&it.comm_W[rows_pre].x)), "commit_zeros");
+    else if (rows_rest)
+      ck(sp_hyrax_commit(ctx, pk.ck, ps.W, d.num_shared + d.num_precommitted, d.num_rest, u64p(it.r_W_rest.data()), ps.is_small ? 1 : 0, u64p(&it.comm_W[rows_pre].x)),
+         "commit rest");
+    std::vector<uint8_t> b = commitment_bytes(it.comm_W.data() + rows_pre, rows_rest);
+    it.tr->absorb("comm_W_rest", b.data(), b.size());
+    it.r_W = ps.r_W_fixed;
+    it.r_W.insert(it.r_W.end(), it.r_W_rest.begin(), it.r_W_rest.end());
+  });
+  phase(0);
+  // :246-253 z = [W | 1 | public]
+  each([&](Item& it, size_t) {
+    SpartanPrepSNARK& ps = *it.ps;
+    ck(sp_table_set_len(ps.z, 2 * M, (size_t)-1, (size_t)-1), "z len");
+    ck(sp_table_copy(ctx, ps.z, 0, ps.W, 0, M), "z <- W");
+    ck(sp_table_zero(ctx, ps.z, M, M), "clear z high half");
+    std::vector<fe_t> tail(pk.num_extra);
+    tail[0] = fe_one<S>();
+    std::copy(it.publics.begin(), it.publics.end(), tail.begin() + 1);
+    // (the staged asynchronous write reuses a few pinned slots behind events; `tail` dies with this statement, so the plain write it is)
+    ck(sp_table_write(ctx, ps.z, M, u64p(tail.data()), tail.size()), "z tail");
+    ck(sp_table_set_len(ps.z, pk.num_cols, (size_t)-1, (size_t)-1), "z len");
+  });
+  // :262-264 tau
+  std::vector<fe_t> taus(count * num_rounds_x);
+  each([&](Item& it, size_t k) {
+    for (size_t i = 0; i < num_rounds_x; ++i) taus[k * num_rounds_x + i] = it.tr->squeeze("t");
+  });
+  // :267-283 multiply_vec_incremental_into
+  each([&](Item& it, size_t) {
+    SpartanPrepSNARK& ps = *it.ps;
+    ck(sp_multiply_vec_incremental(ctx, pk.S, ps.z, ps.caz, ps.cbz, ps.ccz, ps.az, ps.bz, ps.cz), "multiply_vec_incremental");
+  });
+  phase(1);
+  each([&](Item& it, size_t) {
+    for (const aff_t& a : it.comm_W) it.proof.pp(a);
+    for (const fe_t& f : it.publics) it.proof.pf(f);
+  });
+  // :291-310 outer sum-check, all proofs in lockstep
+  std::vector<sp_table*> tA(count), tB(count), tC(count);
+  std::vector<sp_transcript*> trs(count);
+  for (size_t k = 0; k < count; ++k) {
+    tA[k] = items[k].ps->az;
+    tB[k] = items[k].ps->bz;
+    tC[k] = items[k].ps->cz;
+    trs[k] = items[k].tr->t;
+  }
+  std::vector<fe_t> claims(count, fe_zero()), outer_polys(count * 3 * num_rounds_x), r_x(count * num_rounds_x), outer_final(count * 3);
+  ck(sp_sumcheck_cubic3_lockstep(ctx, count, u64p(claims.data()), u64p(taus.data()), num_rounds_x, tA.data(), tB.data(), tC.data(), trs.data(), u64p(outer_polys.data()),
+                                 u64p(r_x.data()), u64p(outer_final.data())),
+     "prove_batch: outer sum-check");
+  each([&](Item& it, size_t k) {
+    for (int i = 0; i < 3; ++i) it.claims_outer[i] = outer_final[3 * k + i];
+    it.tr->absorb_scalars("claims_outer", it.claims_outer, 3);
+    for (size_t i = 0; i < 3 * num_rounds_x; ++i) it.proof.pf(outer_polys[k * 3 * num_rounds_x + i]);
+    for (int i = 0; i < 3; ++i) it.proof.pf(it.claims_outer[i]);
+  });
+  phase(2);
+  // :311-322 r, evals_rx, bind_and_prepare_poly_ABC
+  each([&](Item& it, size_t k) {
+    SpartanPrepSNARK& ps = *it.ps;
+    it.r = it.tr->squeeze("r");
+    claims[k] = fe_add<S>(fe_add<S>(it.claims_outer[0], fe_mul<S>(it.r, it.claims_outer[1])), fe_mul<S>(fe_mul<S>(it.r, it.r), it.claims_outer[2]));
+    ck(sp_eq_table_into(ctx, u64p(&r_x[k * num_rounds_x]), num_rounds_x, ps.rx), "evals_rx");
+    ck(sp_poly_abc(ctx, pk.S, ps.rx, u64p(&it.r), 2 * M, ps.abc), "poly_ABC");
+  });
+  phase(3);
+  // :323-404 inner sum-check (manual round 0 == a generic round on (lo_eff, hi_eff) = (M, num_extra) tables), all proofs in lockstep
+  each([&](Item& it, size_t k) {
+    SpartanPrepSNARK& ps = *it.ps;
+    ck(sp_table_set_len(ps.abc, 2 * M, M, pk.num_extra), "abc len");
+    ck(sp_table_set_len(ps.z, 2 * M, M, pk.num_extra), "z len");
+    tA[k] = ps.abc;
+    tB[k] = ps.z;
+  });
+  std::vector<fe_t> inner_polys(count * 2 * num_rounds_y), r_y(count * num_rounds_y), inner_final(count * 2);
+  ck(sp_sumcheck_quad_lockstep(ctx, count, u64p(claims.data()), num_rounds_y, tA.data(), tB.data(), trs.data(), u64p(inner_polys.data()), u64p(r_y.data()),
+                               u64p(inner_final.data())),
+     "prove_batch: inner sum-check");
+  const size_t num_rows = (M + W_ - 1) / W_, cols = M / num_rows;
+  std::vector<fe_t> eval_W(count);
+  // :405-421 eval_W
+  each([&](Item& it, size_t k) {
+    for (size_t i = 0; i < 2 * num_rounds_y; ++i) it.proof.pf(inner_polys[k * 2 * num_rounds_y + i]);
+    it.r_y.assign(r_y.begin() + k * num_rounds_y, r_y.begin() + (k + 1) * num_rounds_y);
+    const fe_t eval_Z = inner_final[2 * k + 1];
+    std::vector<fe_t> X;
+    X.push_back(fe_one<S>());
+    X.insert(X.end(), it.publics.begin(), it.publics.end());
+    const fe_t eval_X = sparse_poly_evaluate(num_rounds_y - 1, X, it.r_y.data() + 1);
+    const fe_t denom = fe_sub<S>(fe_one<S>(), it.r_y[0]);
+    if (fe_is_zero(denom)) throw Error(SP_ERR_DIVISION_BY_ZERO, "DivisionByZero");
+    eval_W[k] = fe_mul<S>(fe_sub<S>(eval_Z, fe_mul<S>(it.r_y[0], eval_X)), fe_inv_vartime<S>(denom));
+  });
+  phase(4);
+  // :423-436 blind, commit to eval_W, PCS::prove - per proof, never announced ahead
+  each([&](Item& it, size_t k) {
+    SpartanPrepSNARK& ps = *it.ps;
+    Tape& tape = *it.tape;
+    const fe_t blind_eval_W = tape.next();
+    aff_t comm_eval_W;
+    ck(sp_hyrax_commit_small(ctx, pk.ck_s, u64p(&eval_W[k]), 1, u64p(&blind_eval_W), u64p(&comm_eval_W.x)), "commit eval_W");
+    it.proof.pf(eval_W[k]);
+    it.proof.pf(blind_eval_W);
+    if (tape.pos + cols + 2 > tape.blocks) throw Error(SP_ERR_INTERNAL, "random tape exhausted");
+    std::vector<uint64_t> arg(16 + 4 * cols + 8);
+    ck(sp_hyrax_prove(ctx, pk.ck, pk.ck_s, it.tr->t, u64p(&it.comm_W[0].x), it.comm_W.size(), ps.W, M, u64p(it.r_W.data()), u64p(it.r_y.data() + 1), num_rounds_y - 1,
+                      u64p(&comm_eval_W.x), u64p(&blind_eval_W), tape.bytes + 64 * tape.pos, tape.blocks - tape.pos, arg.data()),
+       "PCS::prove");
+    tape.skip(cols + 2);
+    it.proof.words.insert(it.proof.words.end(), arg.begin(), arg.end());
+    ps.queue_lz_tables(ctx);
+    out[k] = std::move(it.proof);
+  });
+  phase(5);
+}
+std::vector<ProofBuf> prove_batch(const SpartanProverKey& pk, SpartanPrepSNARK* const* pss, size_t count, const uint64_t* publics_u64, size_t npub, Tape* tapes,
+                                  PhaseTimes* pt) {
+  const sp_dims& d = pk.dims;
+  if (count == 0) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "prove_batch: no states");
+  if (!pss || !tapes || (npub && !publics_u64)) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "prove_batch: null argument");
+  if (npub != d.num_public) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "prove_batch: public_values length");
+  if (d.num_challenges > 0) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "prove_batch: circuits with verifier challenges are proved one at a time (prove)");
+  for (size_t k = 0; k < count; ++k) {
+    if (!pss[k]) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "prove_batch: null state, proof " + std::to_string(k));
+    if (pss[k]->key != &pk) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "prove_batch: proof " + std::to_string(k) + ": the state was prepared for another key");
+    for (size_t j = 0; j < k; ++j)
+      if (pss[j] == pss[k]) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "prove_batch: the same state twice, proofs " + std::to_string(j) + " and " + std::to_string(k));
+  }
+  const double t_start = now_ms();
+  std::vector<ProofBuf> out(count);
+  if (pt) std::fill(pt->ms, pt->ms + 8, 0.0);
+  if (count == 1) {
+    out[0] = prove(pk, *pss[0], publics_u64, npub, tapes[0], pt);
+    return out;
+  }
+  ck(sp_ctx_bind_thread(pk.ctx), "device");
+  for (size_t first = 0; first < count; first += SP_LOCKSTEP_MAX) {  // more than SP_LOCKSTEP_MAX states: chunk by chunk
+    const size_t n = std::min<size_t>(SP_LOCKSTEP_MAX, count - first);
+    if (n == 1) {
+      try {
+        out[first] = prove_reference_order(pk, *pss[first], publics_u64 + first * npub, npub, tapes[first], nullptr, nullptr, nullptr);
+      } catch (const Error& e) {
+        throw Error(e.code, "prove_batch: proof " + std::to_string(first) + ": " + e.what());
+      }
+      continue;
+    }
+    prove_batch_chunk(pk, pss + first, n, publics_u64 + first * npub, npub, tapes + first, out.data() + first, first, pt ? pt->ms : nullptr);
+  }
+  if (pt) pt->ms[6] = now_ms() - t_start;
+  return out;
+}
+
 // ---- R1CSShape::is_sat (src/r1cs/mod.rs:358-394) on a prepared state ----------------------------------------------------------------------------
 // z = [W | 1 | X] formed as prove forms it (src/spartan.rs:246-253) but in a table of its own, the row check on the device (sp_shape_is_sat), then
 // `res_comm` (:379): PCS::commit of the rows committed at prep_prove - shared, then precommitted - with the stored blinds and the state's is_small,
@@ -1914,6 +2135,28 @@ int ss_prove_hook(void* pk, void* ps, const uint64_t* publics_u64, size_t npub, 
       fprintf(stderr, "[slow prove] %.3f ms: witness %.3f mv %.3f outer %.3f abc %.3f inner %.3f pcs %.3f\n", pt.ms[6], pt.ms[0], pt.ms[1], pt.ms[2], pt.ms[3], pt.ms[4], pt.ms[5]);
       for (auto& l : pt.laps) fprintf(stderr, "[slow prove]   lap %-28s %.3f ms\n", l.first.c_str(), l.second);
     }
+    return 0;
+  } catch (...) {
+    return catch_all();
+  }
+}
+// prove_batch(): `count` states of one key (pss), publics count x npub words, one tape per proof (tapes[k]: tape_blocks[k] blocks of 64 bytes), out_words
+// count x out_cap_each words (proof k at k * out_cap_each, ss_proof_words(pk) words long), tape_used[k] = blocks proof k consumed; phase_ms[7]: the
+// batch's wall-clock per phase, in ss_prove's slots
+int ss_prove_batch(void* pk, void* const* pss, size_t count, const uint64_t* publics_u64, size_t npub, const uint8_t* const* tapes, const size_t* tape_blocks,
+                   size_t* tape_used, uint64_t* out_words, size_t out_cap_each, double* phase_ms) {
+  try {
+    if (!pk || !tapes || !tape_blocks || !out_words) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "prove_batch: null argument");
+    std::vector<Tape> ts;
+    for (size_t k = 0; k < count; ++k) ts.push_back(Tape{tapes[k], tape_blocks[k]});
+    PhaseTimes pt;
+    std::vector<ProofBuf> pf = prove_batch(*(SpartanProverKey*)pk, (SpartanPrepSNARK* const*)pss, count, publics_u64, npub, ts.data(), &pt);
+    for (size_t k = 0; k < count; ++k) {
+      if (pf[k].words.size() > out_cap_each) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "proof buffer too small");
+      memcpy(out_words + k * out_cap_each, pf[k].words.data(), pf[k].words.size() * 8);
+      if (tape_used) tape_used[k] = ts[k].pos;
+    }
+    if (phase_ms) memcpy(phase_ms, pt.ms, 7 * sizeof(double));
     return 0;
   } catch (...) {
     return catch_all();

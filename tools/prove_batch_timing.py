@@ -1,0 +1,152 @@
+"""What prove_batch buys, timed on the device's host at the config-2 shape (2048-byte messages, one key): K proofs as (a) K sequential `prove` calls
+(the headline driver), (b) K sequential reference-order proves (one thread, the reference's statement order: what prove_batch restates), (c) one
+`prove_batch` call. One process, the legs alternating; median (min .. max) of `runs` repetitions after `warmup`, host clock. Then the lockstep cubic
+kernels alone at 2^20-element tables, 16 instances, by the HIP events attached to their dispatches (sp_ctx_kernel_stats), beside the single-proof
+k_bind_eval_cubic_stream of the same run. Writes a Markdown report (profiles/prove_batch.md holds this output for this commit and its parent).
+--no-batch: legs (a) and (b) only - they need nothing of prove_batch, so this form also runs on the commit before it (the baseline column).
+usage: python tools/prove_batch_timing.py [--out FILE] [--runs 20] [--warmup 3] [--ks 1,4,16] [--no-batch] [--no-kernels]"""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from spartan2_amd import frontend, hip, host  # noqa: E402
+
+MSG_LEN = 2048
+
+
+def stat(ts):
+    return statistics.median(ts), min(ts), max(ts)
+
+
+def fmt(s):
+    return f"{s[0]:.3f} ({s[1]:.3f} .. {s[2]:.3f})"
+
+
+def kernels_alone(ctx, lines, count=16, ell=20):
+    """the lockstep cubic kernels at `count` instances of 2^ell elements, and the single-proof prover on one instance, by HIP events"""
+    n = 1 << ell
+    rng = np.random.default_rng(5)
+    data = rng.integers(0, 1 << 62, size=(n, 4), dtype=np.uint64)  # (canonical: the top limb stays below the modulus')
+    tabs = [[hip.Table.from_host(ctx, data) for _ in range(3)] for _ in range(count)]
+    taus = rng.integers(0, 1 << 62, size=(count, ell, 4), dtype=np.uint64)
+    claims = rng.integers(0, 1 << 62, size=(count, 4), dtype=np.uint64)
+
+    def lockstep():
+        for t3 in tabs:
+            for t in t3:
+                t.set_len(n)  # (bound down to one element by the run before: the contents no longer matter, the traffic is the same)
+        trs = [hip.Transcript(ctx, b"t") for _ in range(count)]
+        hip.sumcheck_cubic3_lockstep(ctx, claims, taus, [t[0] for t in tabs], [t[1] for t in tabs], [t[2] for t in tabs], trs)
+
+    def single():
+        for t in tabs[0]:
+            t.set_len(n)
+        hip.sumcheck_cubic3(ctx, claims[0], taus[0], *tabs[0], hip.Transcript(ctx, b"t"))
+
+    lockstep()
+    single()
+    ctx.reset_stats(True)
+    t0 = time.perf_counter()
+    lockstep()
+    t_lock = (time.perf_counter() - t0) * 1e3
+    t0 = time.perf_counter()
+    single()
+    t_single = (time.perf_counter() - t0) * 1e3
+    ctx.synchronize()
+    lines += ["", f"## The lockstep cubic kernels alone: {count} instances of 2^{ell} elements (HIP events on the dispatches, one sum-check each)", "",
+              f"host clock: lockstep sum-check of {count} instances {t_lock:.3f} ms ({t_lock / count:.3f} ms an instance); single-proof sp_sumcheck_cubic3 of one instance "
+              f"{t_single:.3f} ms", "", "| kernel class | launches | device ms | algorithmic bytes | GB/s algorithmic |", "|---|---|---|---|---|"]
+    for what in ("ls_eval_cubic", "ls_bind_eval_cubic", "ls_sum_partials", "eval_cubic", "bind_stream_cubic", "bind"):
+        ms, launches, nbytes = ctx.kernel_stats(what)
+        if launches:
+            lines.append(f"| {what} | {launches} | {ms:.4f} | {nbytes} | {nbytes / (ms * 1e-3) / 1e9 if ms > 0 else 0:.0f} |")
+    ctx.reset_stats(False)
+    for t3 in tabs:
+        for t in t3:
+            t.free()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "prove_batch.md"))
+    ap.add_argument("--runs", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--ks", default="1,4,16")
+    ap.add_argument("--no-batch", action="store_true", help="legs (a) and (b) only: runs on the commit before prove_batch too")
+    ap.add_argument("--no-kernels", action="store_true")
+    a = ap.parse_args()
+    ks = [int(k) for k in a.ks.split(",")]
+    kmax = max(ks)
+    ctx = hip.Context(0)
+    rng = np.random.default_rng(2)
+    sn = host.SpartanSNARK(ctx, frontend.sha256_circuit(bytes(MSG_LEN)))
+    # kmax prepared states of the one key, through the entry point every commit has: the state is taken out of the object after each prep_prove
+    states = []
+    for k in range(kmax):
+        sn.prep_prove_sha256(rng.bytes(MSG_LEN), np.random.default_rng(100 + k).integers(0, 256, size=(1024, 64), dtype=np.uint8))
+        states.append((sn.ps, sn.publics))
+        sn.ps = None
+    tapes = [np.random.default_rng(200 + k).integers(0, 256, size=(8192, 64), dtype=np.uint8) for k in range(kmax)]
+    d = sn.dims
+
+    def sequential(K, reference_order):
+        for k in range(K):
+            sn.ps, sn.publics = states[k]
+            sn.set_flags(reference_order=reference_order)
+            sn.prove(tapes[k])
+        sn.ps = None
+
+    def batch(K):
+        for k in range(K):  # (a batch of one is handed to prove: the headline driver)
+            sn.ps = states[k][0]
+            sn.set_flags(reference_order=False)
+        sn.ps = None
+        sn.prove_batch(tapes[:K], states=states[:K])
+
+    legs = [("a", lambda K: sequential(K, False)), ("b", lambda K: sequential(K, True))]
+    if not a.no_batch:
+        legs.append(("c", batch))
+    lines = [f"# prove_batch on the MI355X, {MSG_LEN}-byte messages: {d['num_cons']} constraints", "",
+             f"command: python tools/prove_batch_timing.py --runs {a.runs} --warmup {a.warmup} --ks {a.ks}" + (" --no-batch" if a.no_batch else "") + (" --no-kernels" if a.no_kernels else ""),
+             "", f"One process, the legs alternating; median (min .. max) of {a.runs} repetitions after {a.warmup}, host clock, ms. (a) = K sequential `prove` calls, the",
+             "headline driver; (b) = K sequential reference-order proves; (c) = one `prove_batch` call over the same K states.", "",
+             "| K | (a) total | (b) total | (c) total | (a) per proof | (b) per proof | (c) per proof | (c) / (a) | (c) / (b) |", "|---|---|---|---|---|---|---|---|---|"]
+    for K in ks:
+        ts = {name: [] for name, _ in legs}
+        for rep in range(a.warmup + a.runs):
+            for name, f in legs:
+                t0 = time.perf_counter()
+                f(K)
+                dt = (time.perf_counter() - t0) * 1e3
+                if rep >= a.warmup:
+                    ts[name].append(dt)
+        s = {name: stat(v) for name, v in ts.items()}
+        c = s.get("c")
+        lines.append(f"| {K} | {fmt(s['a'])} | {fmt(s['b'])} | {fmt(c) if c else '-'} | {s['a'][0] / K:.3f} | {s['b'][0] / K:.3f} | {c[0] / K if c else 0:.3f} | "
+                     f"{c[0] / s['a'][0] if c else 0:.2f} | {c[0] / s['b'][0] if c else 0:.2f} |")
+        print(lines[-1], flush=True)
+    if not a.no_batch:  # the batch's own phase split at the largest K (wall-clock of the whole batch per phase)
+        batch(kmax)
+        _, phases = sn.prove_batch(tapes[:kmax], states=states[:kmax])
+        lines += ["", f"phases of one prove_batch call at K = {kmax}, ms: " + ", ".join(f"{k} {v:.3f}" for k, v in phases.items())]
+    for ps, _ in states:
+        host.lib().ss_prep_free(ps)
+    if not a.no_batch and not a.no_kernels:
+        kernels_alone(ctx, lines)
+    sn.close()
+    ctx.close()
+    text = "\n".join(lines) + "\n"
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write(text)
+    print(text)
+
+
+if __name__ == "__main__":
+    main()

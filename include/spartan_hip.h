@@ -399,6 +399,22 @@ int sp_hyrax_rerandomize(sp_ctx* ctx, const sp_ck* ck, const uint64_t* comm_rows
 int sp_hyrax_prove(sp_ctx* ctx, const sp_ck* ck, const sp_ck* ck_eval, sp_transcript* tr, const uint64_t* comm_rows_aff, size_t rows, const sp_table* poly, size_t n,
                    const uint64_t* blinds, const uint64_t* point, size_t npt, const uint64_t comm_eval_aff[8], const uint64_t blind_eval[4], const uint8_t* rng,
                    size_t rng_blocks, uint64_t* out);
+/* `count` instances of sp_hyrax_prove on ONE ck / ck_eval pair, one `rows` and one n = 2^npt, opened in one pass: every device stage - the mask
+ * vectors d_k and <R_k, d_k>, LZ_k = L_k^T W_k, the table walks of the 2 count vectors delta_k and comm_LZ_k over the key's window tables,
+ * z_vec_k = r_k LZ_k + d_k - is one launch for all instances, and the per-instance host work (r_LZ_k, the commitment's transcript bytes and Keccak
+ * blocks, beta_k, the IPA's absorbs and squeeze) is spread over the library's polling host threads, which the call wakes, beside them. Per instance k: tr[k], comm_rows_aff[k] (`rows`
+ * affine points), poly[k], blinds[k] (`rows` elements) and rng[k] (rng_blocks[k] uniform blocks of 64 bytes) through pointer arrays; points (count x npt
+ * elements), comm_eval_aff (count x 8 words) and blind_eval (count x 4 words) instance-major; out = count x (16 + 4 cols + 8) words, instance k's in
+ * the layout of sp_hyrax_prove. For every k the output words, the cols + 2 blocks consumed and the state of tr[k] afterwards are exactly those of
+ * sp_hyrax_prove on instance k alone. Refused with SP_ERR_INVALID_INPUT_LENGTH before anything is launched, absorbed or written: count == 0 or
+ * count > SP_LOCKSTEP_MAX, a null argument or array entry, n != 2^npt or above a table's capacity, `rows` other than the key's row count for n, an
+ * rng_blocks[k] < cols + 2, the same transcript twice (the same table twice is allowed: tables are only read), ck_eval without tables. An opening
+ * announced on the context (sp_hyrax_prove_announce*) is retracted first and never consumed: the batched call uses no announcement slot. count == 1,
+ * a key without window tables (SPARTAN_KEY_TABLES=0, keys of fewer than 1023 or more than 4095 columns) and more than 2^10 rows run sp_hyrax_prove
+ * per instance: same words. Every staging copy of the mask vectors and of the randomness blocks - pinned and device - is wiped before return. */
+int sp_hyrax_prove_batch(sp_ctx* ctx, const sp_ck* ck, const sp_ck* ck_eval, size_t count, sp_transcript* const* tr, const uint64_t* const* comm_rows_aff, size_t rows,
+                         const sp_table* const* poly, size_t n, const uint64_t* const* blinds, const uint64_t* points, size_t npt, const uint64_t* comm_eval_aff,
+                         const uint64_t* blind_eval, const uint8_t* const* rng, const size_t* rng_blocks, uint64_t* out);
 /* PCS::prove announced ahead of its call. src/spartan.rs calls PCS::prove last (:425-435), but the commitment and its blinds exist when
  * r1cs_instance_and_witness returns (:238-245), the IPA's randomness is independent of everything (the reference draws it inside
  * InnerProductArgumentLinear::prove, ipa.rs:139-149) and the ROW half of the evaluation point exists once the inner sum-check has drawn it. A caller that

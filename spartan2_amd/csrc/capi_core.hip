@@ -278,6 +278,8 @@ void sp_ctx_destroy(sp_ctx* c) {
   delete c->pcs_worker;
   if (c->h_pcs) hipHostFree(c->h_pcs);
   if (c->pcs_ev) hipEventDestroy(c->pcs_ev);
+  if (c->h_opening) hipHostFree(c->h_opening);
+  if (c->opening_ev) hipEventDestroy(c->opening_ev);
   for (void* p_ : c->h_fbm)
     if (p_) hipHostFree(p_);
   for (void* p_ : c->d_mm_work)

@@ -3050,3 +3050,9 @@ void sp_hyrax_commit_split_drop(sp_split_commit* job) {
 
 
 }  // extern "C"
+
+namespace sp {
+jac_t ck_table_mul_host(const sp_ck* ck, size_t t, const fe_t& scalar) { return ck_mul_host(ck, t, scalar); }
+void eq_evals_host(const fe_t* r, size_t k, fe_t* out) { eq_table_host(r, k, out); }
+void point_transcript_bytes(const aff_t& a, uint8_t out[64]) { hp_point_bytes(a, out); }
+}  // namespace sp

@@ -234,6 +234,10 @@ struct sp_ctx {
   size_t h_pcs_bytes = 0;
   hipEvent_t pcs_ev = nullptr;
   sp::Worker* pcs_worker = nullptr;
+  // sp_hyrax_prove_batch (capi_opening_batch.hip): pinned staging of its uploads and landing buffer of its results, grow-only, and its event
+  void* h_opening = nullptr;
+  size_t h_opening_bytes = 0;
+  hipEvent_t opening_ev = nullptr;
   // an opening announced ahead of PCS::prove (sp_hyrax_prove_announce, capi_group.hip): the inner sum-check's round loop reports its challenges to it
   struct sp_pcs_ahead* pcs_ahead = nullptr;
   void* h_pinned_lane[2] = {nullptr, nullptr};  // pinned landing buffers for per-window MSM sums (one per stream), 8 KiB each
@@ -249,6 +253,7 @@ struct sp_ctx {
          WS_SAT_PRODUCTS, WS_SAT_BITMAP, WS_SAT_SUMMARY,  // sp_shape_is_sat / sp_r1cs_residual: Az | Bz | Cz, failure bitmaps, (count, first) pairs
          WS_MATEVAL_PARTIALS, WS_MATEVAL_TICKETS, WS_MATEVAL_OUT,  // sp_shape_matrix_evals_batched: block sums, arrival counters, the 3 results per pair
          WS_LOCKSTEP_EQ, WS_LOCKSTEP_PARTIALS, WS_LOCKSTEP_PARAMS,  // the lockstep sum-checks: eq pyramids per instance, block partials, taus / (lo_eff, hi_eff) per round
+         WS_OPENING_BLOCKS, WS_OPENING_VECS, WS_OPENING_PARAMS, WS_OPENING_WALK,  // sp_hyrax_prove_batch: uniform blocks | d, LZ, z | instances, points | tickets, block sums, results
          WS_PER_LANE,
          WS_SLOTS = 2 * WS_PER_LANE };  // lane 1 = the auxiliary stream used by asynchronous MSM jobs
   void* ws_ptr[WS_SLOTS] = {};

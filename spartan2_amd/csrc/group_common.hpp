@@ -81,6 +81,10 @@ int multi_mul_launch(sp_ctx* c, int lane, const aff_t* d_tables, const uint64_t*
                      size_t raw_blocks, bool expand = false);
 int multi_mul_collect(sp_ctx* c, int lane, unsigned seq, jac_t* out, bool yield);
 int ck_key_tables(sp_ctx* c, const sp_ck* ck);  // 0 = ready, 1 = not available (take the bucket MSM), < 0 = error
+// capi_group.hip: host-side pieces of sp_hyrax_prove that sp_hyrax_prove_batch (capi_opening_batch.hip) runs per instance
+jac_t ck_table_mul_host(const sp_ck* ck, size_t t, const fe_t& scalar);  // table t of a key (t = n_tables - 1: h) times a scalar
+void eq_evals_host(const fe_t* r, size_t k, fe_t* out);                 // eq table of k variables, r[0] on the index MSB (2^k elements)
+void point_transcript_bytes(const aff_t& a, uint8_t out[64]);            // x BE || y BE (src/provider/traits.rs:288-305)
 // capi_pippenger.hip: the general (multi-block) Pippenger for caller-supplied bases; window = 0 -> pippenger_window(n)
 int pippenger_window(size_t n);
 int msm_pippenger(sp_ctx* c, const fe_t* d_canon, const aff_t* d_bases, size_t n, bool full_width, int window, jac_t* result);

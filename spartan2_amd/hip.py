@@ -348,6 +348,39 @@ def _lockstep_lib():
     return L
 
 
+def _opening_batch_lib():
+    L = lib()
+    vpp, sz = ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t
+    L.sp_hyrax_prove_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, sz, vpp, vpp, sz, vpp, sz, vpp, c_u64p, sz, c_u64p, c_u64p, vpp,
+                                       ctypes.POINTER(sz), c_u64p]
+    L.sp_hyrax_prove_batch.restype = ctypes.c_int
+    return L
+
+
+def hyrax_prove_batch(ctx, key, key_eval, trs, comm_rows, polys, n, blinds, points, comm_evals, blind_evals, rngs):
+    """sp_hyrax_prove_batch: len(trs) instances of CommitmentKey.prove on one key pair and one n, opened in one pass. Per instance k: trs[k], comm_rows[k]
+    (rows, 8), polys[k], blinds[k] (rows, 4), points[k] (npt, 4), comm_evals[k] (8,), blind_evals[k] (4,), rngs[k] (>= cols + 2, 64) uniform bytes.
+    Returns (K, 16 + 4 cols + 8) words, row k in CommitmentKey.prove's layout. None entries of the per-instance lists, and None for comm_evals /
+    blind_evals, stay NULL (refusal tests)."""
+    K = len(trs)
+    c64 = lambda a, shape: np.ascontiguousarray(a, dtype=np.uint64).reshape(shape)
+    comm_rows = [None if a is None else c64(a, (-1, 8)) for a in comm_rows]
+    rows = next((a.shape[0] for a in comm_rows if a is not None), 1)
+    blinds = [None if a is None else c64(a, (-1, 4)) for a in blinds]
+    rngs = [None if a is None else np.ascontiguousarray(a, dtype=np.uint8).reshape(-1, 64) for a in rngs]
+    points = c64(points, (max(K, 1), -1, 4)) if K and np.size(points) else np.zeros((max(K, 1), 0, 4), dtype=np.uint64)
+    npt = points.shape[1]
+    cols = n // rows
+    out = np.zeros((max(K, 1), 16 + 4 * cols + 8), dtype=np.uint64)
+    arr = lambda xs: (ctypes.c_void_p * max(len(xs), 1))(*[None if a is None else a.ctypes.data for a in xs])
+    nblk = (ctypes.c_size_t * max(len(rngs), 1))(*[0 if a is None else a.shape[0] for a in rngs])
+    check(_opening_batch_lib().sp_hyrax_prove_batch(ctx.h, key.h, key_eval.h, K, _handles(trs), arr(comm_rows), rows, _handles(polys), n, arr(blinds),
+                                                    p64(points) if points.size else None, npt, None if comm_evals is None else p64(c64(comm_evals, (-1, 8))),
+                                                    None if blind_evals is None else p64(c64(blind_evals, (-1, 4))),
+                                                    arr(rngs), nblk, p64(out)))
+    return out
+
+
 def _handles(objs):
     """array of handles for a `sp_table* const*` / `sp_transcript* const*` argument (None entries stay NULL)"""
     return (ctypes.c_void_p * max(len(objs), 1))(*[None if o is None else o.h for o in objs])

@@ -92,6 +92,7 @@ def from_label(label: bytes, n: int):
 
 REST_HOOK = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, hip.c_u64p, ctypes.c_size_t, hip.c_u64p)
 SP_ERR_UNSAT = -6  # SpartanError::UnSat: what ss_prep_is_sat / nnz_prep_is_sat return for a finding (the reason is in the report)
+SS_BATCH_PER_PROOF_OPENING = 1  # ss_prove_batch_opts flag (host/spartan_snark.cpp)
 PHASES = ("witness_commit", "matrix_vector_multiply", "outer_sumcheck", "prepare_poly_ABC", "inner_sumcheck", "pcs_prove", "total")
 
 
@@ -205,10 +206,11 @@ class SpartanSNARK:
             used_all.append(used.value)
         return used_all
 
-    def prove_batch(self, tapes, states=None):
-        """ss_prove_batch over self.batch (or `states`, a list of (prep state, publics) pairs): one tape per proof -> ([(proof words, blocks used)],
+    def prove_batch(self, tapes, states=None, per_proof_opening=False):
+        """ss_prove_batch_opts over self.batch (or `states`, a list of (prep state, publics) pairs): one tape per proof -> ([(proof words, blocks used)],
         {phase: ms of the whole batch}). Proof k is word for word what prove() returns on state k with tape k; the outer and the inner sum-check of all
-        proofs run in lockstep (sp_sumcheck_cubic3_lockstep / sp_sumcheck_quad_lockstep), everything else per proof."""
+        proofs run in lockstep (sp_sumcheck_cubic3_lockstep / sp_sumcheck_quad_lockstep) and the openings are one sp_hyrax_prove_batch call -
+        per_proof_opening=True (SS_BATCH_PER_PROOF_OPENING) keeps them as one sp_hyrax_prove per proof; everything else per proof."""
         states = self.batch if states is None else states
         K = len(states)
         if len(tapes) != K:
@@ -226,8 +228,8 @@ class SpartanSNARK:
         pss = (ctypes.c_void_p * max(K, 1))(*[ps for ps, _ in states])
         used = (ctypes.c_size_t * max(K, 1))()
         ms = (ctypes.c_double * 7)()
-        _check(lib().ss_prove_batch(self.pk, pss, ctypes.c_size_t(K), hip.p64(pubs) if npub else None, ctypes.c_size_t(npub), tptr, tblk, used, hip.p64(words),
-                                    ctypes.c_size_t(n), ms))
+        _check(lib().ss_prove_batch_opts(self.pk, pss, ctypes.c_size_t(K), hip.p64(pubs) if npub else None, ctypes.c_size_t(npub), tptr, tblk, used, hip.p64(words),
+                                         ctypes.c_size_t(n), ms, ctypes.c_uint(SS_BATCH_PER_PROOF_OPENING if per_proof_opening else 0)))
         return [(words[k].copy(), int(used[k])) for k in range(K)], dict(zip(PHASES, list(ms)))
 
     def prep_phases(self):

@@ -1240,12 +1240,14 @@ ProofBuf prove_reference_order(const SpartanProverKey& pk, SpartanPrepSNARK& ps,
 // prove_reference_order restated over `count` prepared states of ONE key, on one thread, phase by phase: every statement of src/spartan.rs:226-466 is
 // run for proof 0 .. count - 1 before the next statement is begun, and the outer and the inner sum-check run as ONE lockstep sum-check each
 // (sp_sumcheck_cubic3_lockstep / sp_sumcheck_quad_lockstep: a launch per round for all proofs, one wait, `count` transcripts fed on this thread).
-// Everything else is the per-proof call prove_reference_order makes - the commitments, the matrix-vector product, poly_ABC and the opening are NOT
-// batched - and the opening is never announced ahead (the announcement is one slot per context). Proof k is word for word what
+// The openings are ONE sp_hyrax_prove_batch call (every device stage a launch for all proofs; never announced ahead: the announcement is one slot per
+// context); flags & SS_BATCH_PER_PROOF_OPENING keeps them as `count` sp_hyrax_prove calls, one after the other. Everything else is the per-proof call
+// prove_reference_order makes - the commitments, the matrix-vector product and poly_ABC are NOT batched. Proof k is word for word what
 // prove(pk, *ps[k], publics[k], tapes[k]) returns and consumes the same tape blocks; every state can be proved again afterwards, alone or in a batch.
 // pt (optional): the batch's wall-clock per phase, in prove's slots.
+enum : unsigned { SS_BATCH_PER_PROOF_OPENING = 1 };
 static void prove_batch_chunk(const SpartanProverKey& pk, SpartanPrepSNARK* const* pss, size_t count, const uint64_t* publics_u64, size_t npub, Tape* tapes,
-                              ProofBuf* out, size_t first, double* ms) {
+                              ProofBuf* out, size_t first, double* ms, unsigned flags) {
   const sp_dims& d = pk.dims;
   sp_ctx* ctx = pk.ctx;
   const size_t M = pk.num_vars, N = d.num_cons, W_ = DEFAULT_COMMITMENT_WIDTH;
@@ -1397,29 +1399,52 @@ static void prove_batch_chunk(const SpartanProverKey& pk, SpartanPrepSNARK* cons
     eval_W[k] = fe_mul<S>(fe_sub<S>(eval_Z, fe_mul<S>(it.r_y[0], eval_X)), fe_inv_vartime<S>(denom));
   });
   phase(4);
-  // :423-436 blind, commit to eval_W, PCS::prove - per proof, never announced ahead
+  // :423-436 blind, commit to eval_W, PCS::prove - never announced ahead. Per proof: the blind and the commitment of eval_W (a host walk of two table
+  // entries); then the openings - ONE sp_hyrax_prove_batch call, or with SS_BATCH_PER_PROOF_OPENING one sp_hyrax_prove per proof, one after the
+  // other, over the same arguments; then the per-proof appends
+  const size_t arg_words = 16 + 4 * cols + 8, npt = num_rounds_y - 1;
+  std::vector<fe_t> blind_eval_W(count), points(count * npt);
+  std::vector<aff_t> comm_eval_W(count);
+  std::vector<const uint64_t*> comms(count), blinds(count);
+  std::vector<const sp_table*> polys(count);
+  std::vector<const uint8_t*> rngs(count);
+  std::vector<size_t> rng_blocks(count);
   each([&](Item& it, size_t k) {
-    SpartanPrepSNARK& ps = *it.ps;
     Tape& tape = *it.tape;
-    const fe_t blind_eval_W = tape.next();
-    aff_t comm_eval_W;
-    ck(sp_hyrax_commit_small(ctx, pk.ck_s, u64p(&eval_W[k]), 1, u64p(&blind_eval_W), u64p(&comm_eval_W.x)), "commit eval_W");
+    blind_eval_W[k] = tape.next();
+    ck(sp_hyrax_commit_small(ctx, pk.ck_s, u64p(&eval_W[k]), 1, u64p(&blind_eval_W[k]), u64p(&comm_eval_W[k].x)), "commit eval_W");
     it.proof.pf(eval_W[k]);
-    it.proof.pf(blind_eval_W);
+    it.proof.pf(blind_eval_W[k]);
     if (tape.pos + cols + 2 > tape.blocks) throw Error(SP_ERR_INTERNAL, "random tape exhausted");
-    std::vector<uint64_t> arg(16 + 4 * cols + 8);
-    ck(sp_hyrax_prove(ctx, pk.ck, pk.ck_s, it.tr->t, u64p(&it.comm_W[0].x), it.comm_W.size(), ps.W, M, u64p(it.r_W.data()), u64p(it.r_y.data() + 1), num_rounds_y - 1,
-                      u64p(&comm_eval_W.x), u64p(&blind_eval_W), tape.bytes + 64 * tape.pos, tape.blocks - tape.pos, arg.data()),
-       "PCS::prove");
-    tape.skip(cols + 2);
-    it.proof.words.insert(it.proof.words.end(), arg.begin(), arg.end());
-    ps.queue_lz_tables(ctx);
+    comms[k] = u64p(&it.comm_W[0].x);
+    blinds[k] = u64p(it.r_W.data());
+    polys[k] = it.ps->W;
+    rngs[k] = tape.bytes + 64 * tape.pos;
+    rng_blocks[k] = tape.blocks - tape.pos;
+    std::copy(it.r_y.begin() + 1, it.r_y.end(), points.begin() + k * npt);
+  });
+  std::vector<uint64_t> args(count * arg_words);
+  const size_t rows_W = items[0].comm_W.size();
+  if (flags & SS_BATCH_PER_PROOF_OPENING)
+    each([&](Item&, size_t k) {
+      ck(sp_hyrax_prove(ctx, pk.ck, pk.ck_s, trs[k], comms[k], rows_W, polys[k], M, blinds[k], u64p(&points[k * npt]), npt, u64p(&comm_eval_W[k].x), u64p(&blind_eval_W[k]),
+                        rngs[k], rng_blocks[k], &args[k * arg_words]),
+         "PCS::prove");
+    });
+  else
+    ck(sp_hyrax_prove_batch(ctx, pk.ck, pk.ck_s, count, trs.data(), comms.data(), rows_W, polys.data(), M, blinds.data(), u64p(points.data()), npt, u64p(&comm_eval_W[0].x),
+                            u64p(blind_eval_W.data()), rngs.data(), rng_blocks.data(), args.data()),
+       "prove_batch: PCS::prove");
+  each([&](Item& it, size_t k) {
+    it.tape->skip(cols + 2);
+    it.proof.words.insert(it.proof.words.end(), args.begin() + k * arg_words, args.begin() + (k + 1) * arg_words);
+    it.ps->queue_lz_tables(ctx);
     out[k] = std::move(it.proof);
   });
   phase(5);
 }
 std::vector<ProofBuf> prove_batch(const SpartanProverKey& pk, SpartanPrepSNARK* const* pss, size_t count, const uint64_t* publics_u64, size_t npub, Tape* tapes,
-                                  PhaseTimes* pt) {
+                                  PhaseTimes* pt, unsigned flags) {
   const sp_dims& d = pk.dims;
   if (count == 0) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "prove_batch: no states");
   if (!pss || !tapes || (npub && !publics_u64)) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "prove_batch: null argument");
@@ -1449,7 +1474,7 @@ std::vector<ProofBuf> prove_batch(const SpartanProverKey& pk, SpartanPrepSNARK* 
       }
       continue;
     }
-    prove_batch_chunk(pk, pss + first, n, publics_u64 + first * npub, npub, tapes + first, out.data() + first, first, pt ? pt->ms : nullptr);
+    prove_batch_chunk(pk, pss + first, n, publics_u64 + first * npub, npub, tapes + first, out.data() + first, first, pt ? pt->ms : nullptr, flags);
   }
   if (pt) pt->ms[6] = now_ms() - t_start;
   return out;
@@ -2142,15 +2167,15 @@ int ss_prove_hook(void* pk, void* ps, const uint64_t* publics_u64, size_t npub, 
 }
 // prove_batch(): `count` states of one key (pss), publics count x npub words, one tape per proof (tapes[k]: tape_blocks[k] blocks of 64 bytes), out_words
 // count x out_cap_each words (proof k at k * out_cap_each, ss_proof_words(pk) words long), tape_used[k] = blocks proof k consumed; phase_ms[7]: the
-// batch's wall-clock per phase, in ss_prove's slots
-int ss_prove_batch(void* pk, void* const* pss, size_t count, const uint64_t* publics_u64, size_t npub, const uint8_t* const* tapes, const size_t* tape_blocks,
-                   size_t* tape_used, uint64_t* out_words, size_t out_cap_each, double* phase_ms) {
+// batch's wall-clock per phase, in ss_prove's slots; flags: SS_BATCH_PER_PROOF_OPENING = the openings as `count` sp_hyrax_prove calls (same proofs)
+int ss_prove_batch_opts(void* pk, void* const* pss, size_t count, const uint64_t* publics_u64, size_t npub, const uint8_t* const* tapes, const size_t* tape_blocks,
+                        size_t* tape_used, uint64_t* out_words, size_t out_cap_each, double* phase_ms, unsigned flags) {
   try {
     if (!pk || !tapes || !tape_blocks || !out_words) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "prove_batch: null argument");
     std::vector<Tape> ts;
     for (size_t k = 0; k < count; ++k) ts.push_back(Tape{tapes[k], tape_blocks[k]});
     PhaseTimes pt;
-    std::vector<ProofBuf> pf = prove_batch(*(SpartanProverKey*)pk, (SpartanPrepSNARK* const*)pss, count, publics_u64, npub, ts.data(), &pt);
+    std::vector<ProofBuf> pf = prove_batch(*(SpartanProverKey*)pk, (SpartanPrepSNARK* const*)pss, count, publics_u64, npub, ts.data(), &pt, flags);
     for (size_t k = 0; k < count; ++k) {
       if (pf[k].words.size() > out_cap_each) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "proof buffer too small");
       memcpy(out_words + k * out_cap_each, pf[k].words.data(), pf[k].words.size() * 8);
@@ -2161,6 +2186,10 @@ int ss_prove_batch(void* pk, void* const* pss, size_t count, const uint64_t* pub
   } catch (...) {
     return catch_all();
   }
+}
+int ss_prove_batch(void* pk, void* const* pss, size_t count, const uint64_t* publics_u64, size_t npub, const uint8_t* const* tapes, const size_t* tape_blocks,
+                   size_t* tape_used, uint64_t* out_words, size_t out_cap_each, double* phase_ms) {
+  return ss_prove_batch_opts(pk, pss, count, publics_u64, npub, tapes, tape_blocks, tape_used, out_words, out_cap_each, phase_ms, 0);
 }
 // ---- several proofs in flight on ONE thread ------------------------------------------------------------------------------------------------------
 // A prove is a chain of ~41 host <-> device round trips whose host side is a few microseconds of hashing and two kernel launches: one CPU spinning

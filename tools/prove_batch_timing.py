@@ -1,6 +1,8 @@
 """What prove_batch buys, timed on the device's host at the config-2 shape (2048-byte messages, one key): K proofs as (a) K sequential `prove` calls
 (the headline driver), (b) K sequential reference-order proves (one thread, the reference's statement order: what prove_batch restates), (c) one
-`prove_batch` call. One process, the legs alternating; median (min .. max) of `runs` repetitions after `warmup`, host clock. Then the lockstep cubic
+`prove_batch` call, (d) one `prove_batch(per_proof_opening=True)` call: (c) with the openings as K sp_hyrax_prove calls, what prove_batch did before
+sp_hyrax_prove_batch. One process, the legs alternating; median (min .. max) of `runs` repetitions after `warmup`, host clock; the phases of (c) and
+(d) per K, and the batched opening's kernels by HIP events. Then the lockstep cubic
 kernels alone at 2^20-element tables, 16 instances, by the HIP events attached to their dispatches (sp_ctx_kernel_stats), beside the single-proof
 k_bind_eval_cubic_stream of the same run. Writes a Markdown report (profiles/prove_batch.md holds this output for this commit and its parent).
 --no-batch: legs (a) and (b) only - they need nothing of prove_batch, so this form also runs on the commit before it (the baseline column).
@@ -102,39 +104,62 @@ def main():
             sn.prove(tapes[k])
         sn.ps = None
 
-    def batch(K):
+    def batch(K, per_proof_opening=False):
         for k in range(K):  # (a batch of one is handed to prove: the headline driver)
             sn.ps = states[k][0]
             sn.set_flags(reference_order=False)
         sn.ps = None
-        sn.prove_batch(tapes[:K], states=states[:K])
+        if per_proof_opening:
+            return sn.prove_batch(tapes[:K], states=states[:K], per_proof_opening=True)[1]
+        return sn.prove_batch(tapes[:K], states=states[:K])[1]
 
     legs = [("a", lambda K: sequential(K, False)), ("b", lambda K: sequential(K, True))]
     if not a.no_batch:
-        legs.append(("c", batch))
+        legs += [("c", batch), ("d", lambda K: batch(K, True))]
     lines = [f"# prove_batch on the MI355X, {MSG_LEN}-byte messages: {d['num_cons']} constraints", "",
              f"command: python tools/prove_batch_timing.py --runs {a.runs} --warmup {a.warmup} --ks {a.ks}" + (" --no-batch" if a.no_batch else "") + (" --no-kernels" if a.no_kernels else ""),
              "", f"One process, the legs alternating; median (min .. max) of {a.runs} repetitions after {a.warmup}, host clock, ms. (a) = K sequential `prove` calls, the",
-             "headline driver; (b) = K sequential reference-order proves; (c) = one `prove_batch` call over the same K states.", "",
-             "| K | (a) total | (b) total | (c) total | (a) per proof | (b) per proof | (c) per proof | (c) / (a) | (c) / (b) |", "|---|---|---|---|---|---|---|---|---|"]
+             "headline driver; (b) = K sequential reference-order proves" + ("." if a.no_batch else "; (c) = one `prove_batch` call over the same K states; (d) = (c) with")]
+    if not a.no_batch:
+        lines.append("`per_proof_opening=True`: the openings as K `sp_hyrax_prove` calls instead of one `sp_hyrax_prove_batch`.")
+    names = [name for name, _ in legs]
+    ratios = [] if a.no_batch else ["(c) / (a)", "(c) / (d)"]
+    cols = [f"({n}) total" for n in names] + [f"({n}) per proof" for n in names] + ratios
+    lines += ["", "| K | " + " | ".join(cols) + " |", "|---|" + "---|" * len(cols)]
+    phase_lines = []
     for K in ks:
         ts = {name: [] for name, _ in legs}
+        ph = {name: [] for name, _ in legs}
         for rep in range(a.warmup + a.runs):
             for name, f in legs:
                 t0 = time.perf_counter()
-                f(K)
+                phases = f(K)
                 dt = (time.perf_counter() - t0) * 1e3
                 if rep >= a.warmup:
                     ts[name].append(dt)
+                    ph[name].append(phases)
         s = {name: stat(v) for name, v in ts.items()}
-        c = s.get("c")
-        lines.append(f"| {K} | {fmt(s['a'])} | {fmt(s['b'])} | {fmt(c) if c else '-'} | {s['a'][0] / K:.3f} | {s['b'][0] / K:.3f} | {c[0] / K if c else 0:.3f} | "
-                     f"{c[0] / s['a'][0] if c else 0:.2f} | {c[0] / s['b'][0] if c else 0:.2f} |")
+        cells = [fmt(s[n]) for n in names] + [f"{s[n][0] / K:.3f}" for n in names]
+        if ratios:
+            cells += [f"{s['c'][0] / s['a'][0]:.2f}", f"{s['c'][0] / s['d'][0]:.2f}"]
+        lines.append(f"| {K} | " + " | ".join(cells) + " |")
         print(lines[-1], flush=True)
-    if not a.no_batch:  # the batch's own phase split at the largest K (wall-clock of the whole batch per phase)
+        for name in ("c", "d"):  # the batch's own phase split (wall-clock of the whole batch per phase), over the same repetitions
+            if ph.get(name):
+                phase_lines.append(f"| {K} | ({name}) | " + " | ".join(fmt(stat([p[k] for p in ph[name]])) for k in host.PHASES) + " |")
+    if phase_lines:
+        lines += ["", "Phases of the `prove_batch` calls above, ms for the whole batch, median (min .. max) over the same repetitions:", "",
+                  "| K | leg | " + " | ".join(host.PHASES) + " |", "|---|---|" + "---|" * len(host.PHASES)] + phase_lines
+    if not a.no_batch and not a.no_kernels:  # the batched opening's launches at the largest K, by the HIP events around them
         batch(kmax)
-        _, phases = sn.prove_batch(tapes[:kmax], states=states[:kmax])
-        lines += ["", f"phases of one prove_batch call at K = {kmax}, ms: " + ", ".join(f"{k} {v:.3f}" for k, v in phases.items())]
+        ctx.reset_stats(True)
+        batch(kmax)
+        ctx.synchronize()
+        lines += ["", f"The launches of one `sp_hyrax_prove_batch` at K = {kmax} (HIP events around each launch):", "", "| kernel class | launches | device ms |", "|---|---|---|"]
+        for what in ("opening_batch_mask", "opening_batch_rowmat", "opening_batch_walk", "opening_batch_z"):
+            ms, launches, _ = ctx.kernel_stats(what)
+            lines.append(f"| {what} | {launches} | {ms:.4f} |")
+        ctx.reset_stats(False)
     for ps, _ in states:
         host.lib().ss_prep_free(ps)
     if not a.no_batch and not a.no_kernels:

@@ -269,6 +269,14 @@ int sp_multiply_vec(sp_ctx* ctx, const sp_shape* s, const sp_table* z, sp_table*
 /* SplitR1CSShape::multiply_vec_batched (:1130-1166 -> PrecomputedSparseMatrix::multiply_vec_batched, sparse.rs:237-302): the three products for
  * `count` vectors z_k; az / bz / cz are arrays of `count` output tables */
 int sp_multiply_vec_batched(sp_ctx* ctx, const sp_shape* s, const sp_table* const* zs, size_t count, sp_table* const* az, sp_table* const* bz, sp_table* const* cz);
+/* The same products (multiply_vec_batched, sparse.rs:237-302: ONE pass over each matrix for all vectors) with chunks of sp_multiply_vec_chunk() vectors
+ * sharing one walk over A, B and C: every index, code and coefficient is loaded once per chunk and used for the chunk's gathers z_k[col]. Same words as
+ * sp_multiply_vec_batched and as `count` sp_multiply_vec calls; the same table may be several of the zs. Every argument is checked before the first
+ * launch: a null table, a z of the wrong length (SP_ERR_INVALID_WITNESS_LENGTH) or an output shorter than num_cons is refused with its index in
+ * sp_last_error ("..., vector 3") and nothing written. count == 0 is a no-op. Asynchronous like sp_multiply_vec. */
+int sp_multiply_vec_chunked(sp_ctx* ctx, const sp_shape* s, const sp_table* const* zs, size_t count, sp_table* const* az, sp_table* const* bz, sp_table* const* cz);
+/* vectors per launch of sp_multiply_vec_chunked (a compile-time constant of the kernel) */
+size_t sp_multiply_vec_chunk(void);
 /* R1CSShape::evaluate_with_tables_fast (src/r1cs/mod.rs:1216-1226; the verifier's call, src/spartan.rs:540-548) for `count` pairs of tables in chunks that
  * share one walk over A, B, C: out[12 k + 4 m ..] = sum_(row, col) M[row, col] tx[k][row] ty[k][col] for M = A, B, C (m = 0, 1, 2), Montgomery limbs like
  * every scalar of this ABI. No product table is formed. tx[k] has at least num_cons elements, ty[k] at least num_vars + 1 + num_public + num_challenges
@@ -377,6 +385,21 @@ int sp_ck_create(sp_ctx* ctx, const uint64_t* ck_aff, size_t num_cols, const uin
 void sp_ck_free(sp_ck* ck);
 /* PCS::commit (:207-303) on n elements of a device table starting at `off`; one Aff per row of num_cols */
 int sp_hyrax_commit(sp_ctx* ctx, const sp_ck* ck, const sp_table* v, size_t off, size_t n, const uint64_t* blinds, int is_small, uint64_t* out_rows_aff);
+/* PCS::commit (hyrax_pc.rs:207-300) of the SAME segment [off, off + n) of `count` polynomials on one key, in one pass: out_rows_aff[k] receives exactly what
+ * sp_hyrax_commit(ctx, ck, v[k], off, n, blinds[k], ., out) writes - one Aff per row, (0, 0) for an all-zero row with a zero blind. The polynomials are
+ * taken in chunks whose canonical workspace (grow-only context memory, rows x num_cols elements a polynomial) stays within
+ * sp_hyrax_commit_batch_workspace() elements: per chunk one launch forms canonical limbs and row classes (msm_binary / msm_small / msm, :243-292), the row
+ * kernels of the single call run over the chunk's rows, and the digit-path rows of all its polynomials go through ONE batched MSM per class; the blinds'
+ * terms h * blind (:294-299) are one launch for the whole batch, the final additions and normalisations one batch on the polling host threads. The
+ * fixed-base comb table of the key is built only where one polynomial's own digit rows would have had the single call build it, or where it exists -
+ * never on the batch's total. Keys the batch does not serve run sp_hyrax_commit per polynomial (same words): narrow keys (<= 64 bases, per-base tables,
+ * :221-260) and a segment that alone exceeds the workspace. Refused with SP_ERR_INVALID_INPUT_LENGTH before the context is touched: count == 0, a null
+ * array or element (null blinds only matter with n > 0), off + n beyond any table. n == 0 writes nothing. */
+int sp_hyrax_commit_batch(sp_ctx* ctx, const sp_ck* ck, size_t count, const sp_table* const* v, size_t off, size_t n, const uint64_t* const* blinds,
+                          uint64_t* const* out_rows_aff);
+/* the canonical workspace a chunk of sp_hyrax_commit_batch may take, in elements: 2^23 (256 MiB) by default and at most; elems != 0 sets it for the
+ * process (tests cross a chunk boundary with a few rows a polynomial), 0 only reads it. Returns the value now in force. */
+size_t sp_hyrax_commit_batch_workspace(size_t elems);
 /* PCS::commit_without_blind (:533-568): the per-row MSMs alone ((0,0) for an all-zero row) — what SpartanZkSNARK caches across proves
  * (cached_rest_msm, src/spartan_zk.rs:335-366) */
 int sp_hyrax_commit_without_blind(sp_ctx* ctx, const sp_ck* ck, const sp_table* v, size_t off, size_t n, int is_small, uint64_t* out_rows_aff);

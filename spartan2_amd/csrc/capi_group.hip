@@ -909,6 +909,148 @@ int sp_hyrax_commit(sp_ctx* c, const sp_ck* ck, const sp_table* v, size_t off, s
   int rc = commit_rows(c, ck, v, off, n, blinds, rows);
   return rc ? rc : rows_out(rows, out_rows_aff);
 }
+// PCS::commit (hyrax_pc.rs:207-300) of the same segment of `count` polynomials on one key (include/spartan_hip.h). Per chunk of polynomials: ONE launch
+// of k_commit_canon_classify into the padded layout [k][rows x cols], the row kernels of commit_rows over the chunk's kc x rows rows, one copy of
+// (row sums | flags) into pinned memory, one wait; the digit-path rows of the whole chunk in one comb_rows / msm_rows_batched call per class; then, for
+// the whole batch, one fixed_base_rows over all blinds and the additions + normalisations on the polling host threads. Every row is the group element
+// the single call computes, written as a canonical affine point: the words are those of `count` sp_hyrax_commit calls.
+static std::atomic<size_t> g_commit_batch_ws{(size_t)1 << 23};  // elements of canonical workspace a chunk may take (256 MiB)
+size_t sp_hyrax_commit_batch_workspace(size_t elems) {
+  const size_t cap = (size_t)1 << 23;
+  if (elems) g_commit_batch_ws.store(elems < cap ? elems : cap);
+  return g_commit_batch_ws.load();
+}
+int sp_hyrax_commit_batch(sp_ctx* c, const sp_ck* ck, size_t count, const sp_table* const* v, size_t off, size_t n, const uint64_t* const* blinds,
+                          uint64_t* const* out_rows_aff) {
+  // ---- refusals: before the context is touched
+  if (count == 0) return fail(SP_ERR_INVALID_INPUT_LENGTH, "sp_hyrax_commit_batch: count must be at least 1");
+  if (!c || !ck || !v || !out_rows_aff) return fail(SP_ERR_INVALID_INPUT_LENGTH, "sp_hyrax_commit_batch: null argument");
+  if (n && !blinds) return fail(SP_ERR_INVALID_INPUT_LENGTH, "sp_hyrax_commit_batch: null blinds");
+  for (size_t k = 0; k < count; ++k) {
+    const char* what = (!v[k] || !v[k]->d) ? "table" : !out_rows_aff[k] ? "output" : nullptr;
+    if (what) return fail(SP_ERR_INVALID_INPUT_LENGTH, std::string("sp_hyrax_commit_batch: null ") + what + ", polynomial " + std::to_string(k));
+    if (n && !blinds[k]) return fail(SP_ERR_INVALID_INPUT_LENGTH, "sp_hyrax_commit_batch: null blinds, polynomial " + std::to_string(k));
+    if (off > v[k]->cap || n > v[k]->cap - off)
+      return fail(SP_ERR_INVALID_INPUT_LENGTH, "sp_hyrax_commit_batch: range exceeds the table, polynomial " + std::to_string(k));
+  }
+  const size_t cols = ck->num_cols, rows = (n + cols - 1) / cols;
+  if (rows == 0) return SP_OK;
+  const size_t ws_elems = g_commit_batch_ws.load();
+  // narrow keys (per-base tables, commit_rows' first branch) and a polynomial that alone exceeds a chunk's workspace: the single call per polynomial
+  if (ck->d_cktables || rows * cols > ws_elems) {
+    for (size_t k = 0; k < count; ++k) {
+      const int rc = sp_hyrax_commit(c, ck, v[k], off, n, blinds[k], 1, out_rows_aff[k]);
+      if (rc) return rc;
+    }
+    return SP_OK;
+  }
+  const size_t total = count * rows;
+  size_t chunk = ws_elems / (rows * cols);
+  if (chunk > (size_t)spk::COMMIT_BATCH_POLYS) chunk = spk::COMMIT_BATCH_POLYS;
+  if (chunk > count) chunk = count;
+  const size_t chunk_rows = chunk * rows;
+  fe_t* canon = (fe_t*)c->workspace(sp_ctx::WS_COMMIT_CANON, chunk_rows * cols * sizeof(fe_t));
+  char* drow = (char*)c->workspace(sp_ctx::WS_COMMIT_ROWS, chunk_rows * (sizeof(jac_t) + 4));  // [row sums | flags]: one copy
+  if (!canon || !drow) return SP_ERR_NO_DEVICE;
+  const size_t pinned_bytes = chunk_rows * (sizeof(jac_t) + 4);
+  if (c->h_opening_bytes < pinned_bytes) {  // the batched opening's pinned buffer (grow-only; cleared below once the row sums are copied out, as that call clears it)
+    if (c->h_opening) hipHostFree(c->h_opening);
+    c->h_opening = nullptr;
+    c->h_opening_bytes = 0;
+    SP_HIP(hipHostMalloc(&c->h_opening, pinned_bytes + pinned_bytes / 4));
+    c->h_opening_bytes = pinned_bytes + pinned_bytes / 4;
+  }
+  std::vector<jac_t> all_rows(total);
+  bool blinds_done = false;
+  std::vector<jac_t> hb;
+  auto blind_terms = [&]() -> int {  // h * blind for every row of every polynomial: one launch
+    std::vector<uint64_t> bl(total * 4);
+    for (size_t k = 0; k < count; ++k) memcpy(bl.data() + k * rows * 4, blinds[k], rows * 32);
+    blinds_done = true;
+    return fixed_base_rows(c, ck->d_htable, 1, bl.data(), total, hb);
+  };
+  int rc;
+  for (size_t k0 = 0; k0 < count; k0 += chunk) {
+    const size_t kc = count - k0 < chunk ? count - k0 : chunk, R = kc * rows, nn = R * cols;
+    jac_t* rowsum = reinterpret_cast<jac_t*>(drow);
+    unsigned* flags = reinterpret_cast<unsigned*>(drow + R * sizeof(jac_t));
+    spk::CommitBatchSrc src;
+    for (size_t j = 0; j < (size_t)spk::COMMIT_BATCH_POLYS; ++j) src.p[j] = v[k0 + (j < kc ? j : 0)]->d + off;  // (blocks exist for j < kc only)
+    c->timed_kernel("commit_canon_classify", 64ull * nn, spk::k_commit_canon_classify, dim3((unsigned)rows, (unsigned)kc), dim3(256), src, n, cols, rows, canon, flags);
+    c->timed("msm_binary_rows", 72ull * nn, [&] {
+      hipLaunchKernelGGL(spk::k_msm_binary_rows, dim3((unsigned)R), dim3(256), 0, c->stream, canon, nn, cols, ck->d_bases, flags, rowsum);
+    });
+    SP_HIP(hipMemcpyAsync(c->h_opening, drow, R * (sizeof(jac_t) + 4), hipMemcpyDeviceToHost, c->stream));
+    // the blinds' walk behind the first chunk's kernels: its wait is this chunk's wait
+    if (!blinds_done && (rc = blind_terms())) return rc;
+    SP_HIP(sp::stream_sync(c->stream));
+    jac_t* msm_rows = all_rows.data() + k0 * rows;
+    memcpy(msm_rows, c->h_opening, R * sizeof(jac_t));
+    std::vector<unsigned> hflags_v(R);
+    memcpy(hflags_v.data(), static_cast<char*>(c->h_opening) + R * sizeof(jac_t), R * 4);
+    explicit_bzero(c->h_opening, R * (sizeof(jac_t) + 4));  // the unblinded row sums do not stay in the shared pinned buffer
+    const unsigned* hflags = hflags_v.data();
+    // digit path (msm.rs:367-409, :187-222) over the concatenated rows. Whether the comb table is built is decided as the single calls decide it: on
+    // ONE polynomial's digit-row count (or an existing table), never on the chunk's total - a batch builds no table `count` calls would not have built.
+    std::vector<unsigned> full_rows, narrow_rows;
+    bool comb_wanted = ck->d_comb != nullptr;
+    for (size_t j = 0; j < kc; ++j) {
+      size_t mine = 0;
+      for (size_t r = 0; r < rows; ++r) {
+        const unsigned f = hflags[j * rows + r];
+        if (f > 1u) {
+          ((f & 4u) ? full_rows : narrow_rows).push_back((unsigned)(j * rows + r));
+          ++mine;
+        }
+      }
+      if (mine >= sp::comb_min_rows()) comb_wanted = true;
+    }
+    std::vector<jac_t> digit_rows;
+    if (!full_rows.empty() || !narrow_rows.empty()) digit_rows.assign(msm_rows, msm_rows + R);  // (comb_rows / msm_rows_batched index a vector by row number)
+    for (int pass = 0; pass < 2; ++pass) {
+      const std::vector<unsigned>& sel = pass == 0 ? full_rows : narrow_rows;
+      const int windows = pass == 0 ? spk::MSM_MAX_WINDOWS : 9;
+      if (sel.size() > 2) {
+        int have = 1;
+        if (comb_wanted) {
+          have = sp::comb_ensure(c, ck);
+          if (have < 0) return have;
+        }
+        if (have == 0) rc = sp::comb_rows(c, ck, canon, cols, nn, sel, pass == 0 ? 256 : 64, digit_rows);
+        else rc = msm_rows_batched(c, canon, cols, nn, sel, windows, ck->d_bases, digit_rows);
+        if (rc) return rc;
+      } else {
+        for (unsigned r : sel)
+          if ((rc = msm_device(c, canon + (size_t)r * cols, ck->d_bases, cols, windows, &digit_rows[r]))) return rc;
+      }
+      for (unsigned r : sel) msm_rows[r] = digit_rows[r];
+    }
+  }
+  // commitment row = row sum + h * blind, normalised: ranges of rows on the polling host threads, each with an inversion of its own
+  std::vector<aff_t> aff(total);
+  struct Part {
+    const jac_t *a, *b;
+    aff_t* out;
+    size_t total;
+  } part{all_rows.data(), hb.data(), aff.data(), total};
+  auto fn = [](void* arg, unsigned k, unsigned np) {
+    Part& P = *static_cast<Part*>(arg);
+    const size_t lo = P.total * k / np, hi = P.total * (k + 1) / np;
+    std::vector<jac_t> mine(hi - lo);
+    for (size_t i = lo; i < hi; ++i) mine[i - lo] = jac_add(P.a[i], P.b[i]);
+    normalize_batch(mine, P.out + lo);
+  };
+  sp::WalkPool& pool = sp::WalkPool::get();
+  const unsigned np = total >= 64 && pool.walkers() > 0 ? (unsigned)std::min<size_t>(total / 32, (size_t)pool.walkers() + 1) : 1u;
+  if (np > 1) {
+    pool.keep_hot(2000);  // armed HERE: walkers claim parts only while awake, and the chunks above take milliseconds
+    pool.run(np, fn, &part);
+  } else {
+    fn(&part, 0, 1);
+  }
+  for (size_t k = 0; k < count; ++k) memcpy(out_rows_aff[k], aff.data() + k * rows, rows * sizeof(aff_t));
+  return SP_OK;
+}
 // PCS::commit_without_blind (hyrax_pc.rs:533-568): the cacheable, randomness-free part of a commitment
 int sp_hyrax_commit_without_blind(sp_ctx* c, const sp_ck* ck, const sp_table* v, size_t off, size_t n, int /*is_small: auto-detected*/, uint64_t* out_rows_aff) {
   std::vector<jac_t> rows;

@@ -5,11 +5,13 @@
 //                      (no 256-bit atomics): short columns one lane each, long columns (the constant-1 column of the
 //                      booleanity rows) one block each.
 //   k_matrix_evals_batched  evaluate_with_tables_fast (src/r1cs/mod.rs:1216-1226) for a chunk of (T_x, T_y) pairs in one walk (kernels_mateval.hpp)
+//   k_spmv3_multi      multiply_vec_batched (sparse.rs:237-302) for a chunk of vectors in one walk (kernels_spmv_multi.hpp)
 //   k_r1cs_residual    R1CSShape::is_sat / is_sat_relaxed (src/r1cs/mod.rs:358-394, :430-471): the row check behind multiply_vec (kernels_sat.hpp)
 // Entries keep the reference's classes: +-1 and |k| in 2..7 as an int8 code (add / sub / double-add chains, sparse.rs:137-155),
 // everything else as a full field coefficient.
 #include <algorithm>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "core.hpp"
@@ -243,6 +245,7 @@ __global__ void __launch_bounds__(256) k_polyabc_short_and_long(PolyAbcArgs a, c
 }  // namespace spk
 
 #include "kernels_mateval.hpp"
+#include "kernels_spmv_multi.hpp"
 
 // ---- host side: classification and upload ---------------------------------------------------------------------------
 namespace {
@@ -576,6 +579,43 @@ int sp_multiply_vec_batched(sp_ctx* c, const sp_shape* s, const sp_table* const*
     sp_table* outs[3] = {az[k], bz[k], cz[k]};
     int rc = spmv3(c, s, s->row, s->nnz, zs[k], nullptr, outs, "spmv");
     if (rc) return rc;
+  }
+  return SP_OK;
+}
+// multiply_vec_batched (sparse.rs:237-302) with the reference's ONE pass over the matrices for several vectors: chunks of SPMV_KC vectors, one launch
+// of k_spmv3_multi each. Every argument is checked before the first launch, so a refused call has written nothing.
+size_t sp_multiply_vec_chunk(void) { return (size_t)spk::SPMV_KC; }
+int sp_multiply_vec_chunked(sp_ctx* c, const sp_shape* s, const sp_table* const* zs, size_t count, sp_table* const* az, sp_table* const* bz, sp_table* const* cz) {
+  if (!c || !s || (count && (!zs || !az || !bz || !cz))) return fail(SP_ERR_INVALID_INPUT_LENGTH, "multiply_vec_chunked: null argument");
+  const size_t nrows = s->dims.num_cons;
+  for (size_t k = 0; k < count; ++k) {
+    const std::string at = ", vector " + std::to_string(k);
+    if (!zs[k] || !az[k] || !bz[k] || !cz[k]) return fail(SP_ERR_INVALID_INPUT_LENGTH, "multiply_vec_chunked: null table" + at);
+    if (zs[k]->len != s->num_cols) return fail(SP_ERR_INVALID_WITNESS_LENGTH, "multiply_vec_chunked: z has the wrong length" + at);
+    if (az[k]->cap < nrows || bz[k]->cap < nrows || cz[k]->cap < nrows) return fail(SP_ERR_INVALID_INPUT_LENGTH, "multiply_vec_chunked: output table too short" + at);
+  }
+  size_t blocks = (nrows + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  if (blocks == 0) blocks = 1;
+  const uint64_t nnz = s->nnz[0] + s->nnz[1] + s->nnz[2];
+  for (size_t k0 = 0; k0 < count; k0 += spk::SPMV_KC) {
+    const size_t kc = std::min<size_t>(spk::SPMV_KC, count - k0);
+    spk::SpmvMultiArgs a;
+    for (int m = 0; m < 3; ++m) a.m[m] = s->row[m].view();
+    for (size_t j = 0; j < (size_t)spk::SPMV_KC; ++j) {  // (the unused slots of a ragged chunk are never dereferenced)
+      const size_t k = k0 + (j < kc ? j : 0);
+      a.z[j] = zs[k]->d;
+      sp_table* outs[3] = {az[k], bz[k], cz[k]};
+      for (int m = 0; m < 3; ++m) {
+        a.out[m][j] = outs[m]->d;
+        outs[m]->len = nrows;
+        outs[m]->lo_eff = outs[m]->hi_eff = (size_t)-1;
+      }
+    }
+    a.kc = (int)kc;
+    // structure once per chunk (4-byte index + code, row pointers of both classes) + one 32-byte gather per entry and vector + the 3 outputs per vector
+    const uint64_t bytes = 5ull * nnz + 24ull * nrows + kc * (32ull * nnz + 96ull * nrows);
+    c->timed_kernel("spmv_multi", bytes, spk::k_spmv3_multi, dim3((unsigned)blocks, 3), dim3(256), a, nrows);
   }
   return SP_OK;
 }

@@ -83,6 +83,41 @@ __global__ void __launch_bounds__(256) k_classify_rows(const fe_t* __restrict__ 
   if (f) atomicOr(&flags[row], f);
 }
 
+// k_to_canonical + k_classify_rows for a CHUNK of polynomials of one key in one launch (sp_hyrax_commit_batch; PCS::commit, hyrax_pc.rs:207-300, of the
+// same segment of each): block (row, k) reads row `row` of polynomial k - src.p[k] already points at the segment's first element, n elements long -
+// and writes its canonical limbs to canon[(k * rows + row) * cols ..], ZERO past n, so the chunk is kc * rows full rows of `cols` to the row kernels
+// (k_msm_binary_rows, k_fold_sign_rows, k_comb_rows: their (n, cols) arithmetic holds with n = kc * rows * cols). The row's class bits are OR-ed over the
+// block (wave shuffles, then four words of LDS) and written with one plain store: no atomics, no zeroed flag buffer.
+constexpr int COMMIT_BATCH_POLYS = 64;  // polynomials a launch takes (their segment pointers travel by value)
+struct CommitBatchSrc {
+  const fe_t* p[COMMIT_BATCH_POLYS];
+};
+__global__ void __launch_bounds__(256) k_commit_canon_classify(CommitBatchSrc src, size_t n, size_t cols, size_t rows, fe_t* __restrict__ canon,
+                                                               unsigned* __restrict__ flags) {
+  __shared__ unsigned s_f[4];
+  const size_t row = blockIdx.x, k = blockIdx.y;
+  const fe_t* __restrict__ in = src.p[k];
+  fe_t* __restrict__ out = canon + (k * rows + row) * cols;
+  const size_t lo = row * cols;
+  unsigned f = 0;
+  for (size_t i = threadIdx.x; i < cols; i += blockDim.x) {
+    fe_t c = fe_zero();
+    if (lo + i < n) {
+      c = fe_to_canonical<SF>(in[lo + i]);
+      const unsigned upper = c.v[2] | c.v[3] | c.v[4] | c.v[5] | c.v[6] | c.v[7];
+      if (upper) f |= 7u;
+      else if (c.v[1] || c.v[0] > 1) f |= 3u;
+      else if (c.v[0]) f |= 1u;
+    }
+    out[i] = c;
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) f |= __shfl_xor(f, d, 64);
+  if ((threadIdx.x & 63u) == 0) s_f[threadIdx.x >> 6] = f;
+  __syncthreads();
+  if (threadIdx.x == 0) flags[k * rows + row] = s_f[0] | s_f[1] | s_f[2] | s_f[3];
+}
+
 // ---- K11 signed-digit Pippenger, window c = 8 ---------------------------------------------------------------------
 constexpr int MSM_C = 8;
 constexpr int MSM_BUCKETS = 1 << (MSM_C - 1);  // 128 signed buckets per window

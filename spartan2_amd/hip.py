@@ -59,6 +59,39 @@ def matrix_evals_chunk() -> int:
     return int(lib().sp_shape_matrix_evals_chunk())
 
 
+def multiply_vec_chunk() -> int:
+    """vectors per launch of sp_multiply_vec_chunked (sp_multiply_vec_chunk): where a batch crosses into the next chunk"""
+    lib().sp_multiply_vec_chunk.restype = ctypes.c_size_t
+    return int(lib().sp_multiply_vec_chunk())
+
+
+def __getattr__(name):
+    if name == "SPMV_KC":  # read from the library, not restated here
+        return multiply_vec_chunk()
+    raise AttributeError(name)
+
+
+def hyrax_commit_batch_workspace(elems: int = 0) -> int:
+    """sp_hyrax_commit_batch_workspace: elements of canonical workspace a chunk of hyrax_commit_batch may take (elems != 0 sets it, at most 2^23)"""
+    lib().sp_hyrax_commit_batch_workspace.restype = ctypes.c_size_t
+    return int(lib().sp_hyrax_commit_batch_workspace(ctypes.c_size_t(elems)))
+
+
+def hyrax_commit_batch(ctx, key, tables, off, n, blinds):
+    """sp_hyrax_commit_batch: PCS::commit (hyrax_pc.rs:207-300) of elements [off, off + n) of every table of `tables` on one key in one pass;
+    blinds[k]: (rows, 4) -> [(rows, 8) affine rows per table], each what key.commit(tables[k], off, n, blinds[k]) returns."""
+    K = len(tables)
+    rows = (n + key.num_cols - 1) // key.num_cols
+    bl = [np.ascontiguousarray(b, dtype=np.uint64).reshape(rows, 4) for b in blinds]
+    assert len(bl) == K
+    outs = [np.zeros((rows, 8), dtype=np.uint64) for _ in range(K)]
+    tarr = (ctypes.c_void_p * max(K, 1))(*[t.h for t in tables])
+    barr = (c_u64p * max(K, 1))(*[p64(b) if rows else None for b in bl])
+    oarr = (c_u64p * max(K, 1))(*[p64(o) if rows else o.ctypes.data_as(c_u64p) for o in outs])
+    check(lib().sp_hyrax_commit_batch(ctx.h, key.h, ctypes.c_size_t(K), tarr, ctypes.c_size_t(off), ctypes.c_size_t(n), barr, oarr))
+    return outs
+
+
 class SpartanHipError(RuntimeError):
     pass
 
@@ -816,6 +849,12 @@ class Shape:
         n = len(zs)
         arr = lambda ts: (ctypes.c_void_p * n)(*[t.h for t in ts])
         check(lib().sp_multiply_vec_batched(self.ctx.h, self.h, arr(zs), ctypes.c_size_t(n), arr(azs), arr(bzs), arr(czs)))
+
+    def multiply_vec_chunked(self, zs, azs, bzs, czs):
+        """sp_multiply_vec_chunked: multiply_vec_batched (sparse.rs:237-302) with chunks of SPMV_KC vectors sharing one walk over A, B, C"""
+        n = len(zs)
+        arr = lambda ts: (ctypes.c_void_p * max(n, 1))(*[t.h for t in ts])
+        check(lib().sp_multiply_vec_chunked(self.ctx.h, self.h, arr(zs), ctypes.c_size_t(n), arr(azs), arr(bzs), arr(czs)))
 
     def matrix_evals_batched(self, txs, tys) -> np.ndarray:
         """evaluate_with_tables_fast (src/r1cs/mod.rs:1216-1226) for every pair (txs[k], tys[k]) in chunks that share one walk over A, B, C:

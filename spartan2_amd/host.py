@@ -93,6 +93,9 @@ def from_label(label: bytes, n: int):
 REST_HOOK = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, hip.c_u64p, ctypes.c_size_t, hip.c_u64p)
 SP_ERR_UNSAT = -6  # SpartanError::UnSat: what ss_prep_is_sat / nnz_prep_is_sat return for a finding (the reason is in the report)
 SS_BATCH_PER_PROOF_OPENING = 1  # ss_prove_batch_opts flag (host/spartan_snark.cpp)
+SS_PREP_PER_STATE_COMMIT = 1  # ss_prep_prove_batch_opts / ss_prep_prove_sha256_batch_opts flags: one sp_hyrax_commit per state ...
+SS_PREP_PER_STATE_MATVEC = 2  # ... one sp_multiply_vec per state (what the driver takes unless asked otherwise: measured, profiles/prep_prove_batch.md)
+SS_PREP_CHUNKED_MATVEC = 4  # ... the cached products through sp_multiply_vec_chunked
 PHASES = ("witness_commit", "matrix_vector_multiply", "outer_sumcheck", "prepare_poly_ABC", "inner_sumcheck", "pcs_prove", "total")
 
 
@@ -170,10 +173,16 @@ class SpartanSNARK:
             lib().ss_prep_free(ps)
         self.batch = []
 
-    def prep_prove_batch(self, tapes, witnesses=None, msgs=None, is_small=True):
+    def prep_prove_batch(self, tapes, witnesses=None, msgs=None, is_small=True, one_pass=True, per_state_commit=False, per_state_matvec=False, chunked_matvec=False):
         """K prep states on this one key for prove_batch, kept in self.batch with their public values (self.ps is left alone): from `msgs` (K messages
-        of the key's length, through ss_prep_prove_sha256 as prep_prove_sha256), from `witnesses` (K instances of this key's circuit - objects with
-        .witness and .publics - through ss_prep_prove), or K = len(tapes) states of the key's own instance. Returns the blocks used of each tape."""
+        of the key's length, as prep_prove_sha256), from `witnesses` (K instances of this key's circuit - objects with .witness and .publics), or
+        K = len(tapes) states of the key's own instance. Returns the blocks used of each tape. State k is the state prep_prove / prep_prove_sha256 makes
+        of witness / message k with tape k. By default all K are prepared in one pass (ss_prep_prove_batch_opts / ss_prep_prove_sha256_batch_opts: one
+        witness launch, the commitments through sp_hyrax_commit_batch, one synchronise); per_state_commit (SS_PREP_PER_STATE_COMMIT) keeps one
+        sp_hyrax_commit per state; the cached products are one sp_multiply_vec per state - per_state_matvec (SS_PREP_PER_STATE_MATVEC) says so
+        explicitly - unless chunked_matvec (SS_PREP_CHUNKED_MATVEC) takes sp_multiply_vec_chunked, which was measured and does not win
+        (profiles/prep_prove_batch.md); one_pass=False is a loop of single prep_prove calls.
+        The phases of the last one-pass batch, ms: self.batch_prep_phases."""
         K = len(tapes)
         if msgs is not None and witnesses is not None:
             raise ValueError("prep_prove_batch: msgs or witnesses, not both")
@@ -181,17 +190,55 @@ class SpartanSNARK:
             if v is not None and len(v) != K:
                 raise ValueError(f"prep_prove_batch: {len(v)} {name} for {K} tapes")
         self._free_batch()
+        if msgs is not None and K:
+            msgs = [bytes(m) for m in msgs]
+            if self._sha_plan is None or self._sha_plan.msg_len != len(msgs[0]):
+                from . import frontend
+
+                self._sha_plan = hip.Sha256Plan(self.ctx, frontend.sha256_witness_plan(len(msgs[0])))
+        if not one_pass or K == 0:
+            return self._prep_prove_loop(tapes, witnesses, msgs, is_small)
+        flags = (SS_PREP_PER_STATE_COMMIT if per_state_commit else 0) | (SS_PREP_PER_STATE_MATVEC if per_state_matvec else 0) | (SS_PREP_CHUNKED_MATVEC if chunked_matvec else 0)
+        tapes = [np.ascontiguousarray(t, dtype=np.uint8) for t in tapes]
+        tptr = (hip.c_u8p * K)(*[hip.p8(t) for t in tapes])
+        tblk = (ctypes.c_size_t * K)(*[t.shape[0] for t in tapes])
+        used = (ctypes.c_size_t * K)()
+        pss = (ctypes.c_void_p * K)()
+        ms = (ctypes.c_double * 8)()
+        if msgs is not None:
+            n = len(msgs[0])
+            for k, m in enumerate(msgs):
+                if len(m) != n:
+                    raise hip.SpartanHipError(f"prep_prove_batch: state {k}: a message of {len(m)} bytes in a batch of {n}-byte messages")
+            buf = np.frombuffer(b"".join(msgs), dtype=np.uint8).copy() if n else np.zeros(1, dtype=np.uint8)
+            pubs = np.zeros((K, 256), dtype=np.uint64)
+            _check(lib().ss_prep_prove_sha256_batch_opts(self.pk, self._sha_plan.h, hip.p8(buf), ctypes.c_size_t(n), ctypes.c_size_t(K), int(is_small), tptr, tblk, used,
+                                                         pss, hip.p64(pubs), ms, ctypes.c_uint(flags)))
+            pub_list = [pubs[k].copy() for k in range(K)]
+        else:
+            srcs = [self.inst] * K if witnesses is None else list(witnesses)
+            ws = [np.ascontiguousarray(src.witness, dtype=np.uint64).reshape(-1) for src in srcs]
+            d = self.dims
+            want = d["num_shared_unpadded"] + d["num_precommitted_unpadded"] + d["num_rest_unpadded"]
+            for k, w in enumerate(ws):  # (the entry point takes one length for all states)
+                if len(w) != want:
+                    raise hip.SpartanHipError(f"prep_prove_batch: state {k}: InvalidWitnessLength ({len(w)} words, the key takes {want})")
+            wptr = (hip.c_u64p * K)(*[hip.p64(w) if len(w) else None for w in ws])
+            _check(lib().ss_prep_prove_batch_opts(self.pk, wptr, ctypes.c_size_t(want), ctypes.c_size_t(K), int(is_small), tptr, tblk, used, pss, ms, ctypes.c_uint(flags)))
+            pub_list = [np.ascontiguousarray(src.publics, dtype=np.uint64) for src in srcs]
+        self.batch = [(ctypes.c_void_p(pss[k]), pub_list[k]) for k in range(K)]
+        self.batch_prep_phases = dict(witness=ms[0], commit=ms[1], tables=ms[2], matvec=ms[3], scratch=ms[4], total=ms[6])
+        return [int(used[k]) for k in range(K)]
+
+    def _prep_prove_loop(self, tapes, witnesses, msgs, is_small):
+        """prep_prove_batch(one_pass=False): one ss_prep_prove / ss_prep_prove_sha256 call per state"""
         used_all = []
-        for k in range(K):
+        for k in range(len(tapes)):
             tape = tapes[k]
             used = ctypes.c_size_t(0)
             ps = ctypes.c_void_p()
             if msgs is not None:
-                msg = bytes(msgs[k])
-                if self._sha_plan is None or self._sha_plan.msg_len != len(msg):
-                    from . import frontend
-
-                    self._sha_plan = hip.Sha256Plan(self.ctx, frontend.sha256_witness_plan(len(msg)))
+                msg = msgs[k]
                 pub = np.zeros(256, dtype=np.uint64)
                 buf = np.frombuffer(msg, dtype=np.uint8).copy()
                 _check(lib().ss_prep_prove_sha256(self.pk, self._sha_plan.h, hip.p8(buf), ctypes.c_size_t(len(msg)), int(is_small), hip.p8(tape),

@@ -302,6 +302,204 @@ SpartanPrepSNARK* prep_prove_sha256(const SpartanProverKey& pk, const sp_sha256_
   return ps;
 }
 
+// ---- prep_prove for `count` states of one key in one pass -------------------------------------------------------------------------------------------
+// SpartanSNARK::prep_prove (src/spartan.rs:176-216) restated over a batch, phase by phase: what prep_prove_from does per state is done here for all of
+// them - the witnesses (one sp_sha256_witness launch for all messages, or the words of each state), the blinds (from tape k, shared first), the
+// commitments (sp_hyrax_commit_batch per segment: one launch, one copy, one wait and one normalisation for all states), the tables block, the cached
+// products (one sp_multiply_vec per state, queued back to back; sp_multiply_vec_chunked - one walk over A, B, C per chunk of vectors - on request: it
+// was measured and does not win, see the constants below), the scratch, one synchronise. State k is word for word the state
+// prep_prove_from makes of witness k with tape k: group sums as canonical affine points and exact field sums, so neither depends on how the work was
+// grouped. Still per state: the allocations and the lz_tables block (the tables are built lazily, behind a state's first prove).
+// flags: SS_PREP_PER_STATE_COMMIT keeps one sp_hyrax_commit per state and segment, SS_PREP_PER_STATE_MATVEC one sp_multiply_vec per state,
+// SS_PREP_CHUNKED_MATVEC takes sp_multiply_vec_chunked (same states; there so that one process can compare the paths; with both product flags set
+// SS_PREP_PER_STATE_MATVEC wins). A batch of one takes the
+// per-state calls: there is nothing to share.
+// What the driver takes by default was measured (profiles/prep_prove_batch.md, config 2, one process, legs alternating):
+//   commit: sp_hyrax_commit_batch beats one sp_hyrax_commit per state at every K >= 2 measured (1.15 against 2.37 ms at K = 4, 4.42 against 9.46 at
+//     K = 16): PREP_BATCH_COMMIT_MIN = 2, there is no K at which the loop wins.
+//   cached product: sp_multiply_vec_chunked does NOT beat one sp_multiply_vec per state at any K measured (k_spmv3_multi 0.093 ms a vector against
+//     0.083 for k_spmv3<true>; the whole call 1.01 x at K = 4, 1.02 x at K = 16, inside the spread): PREP_CHUNKED_MATVEC_DEFAULT = false, the driver
+//     takes the loop and the shared walk runs only when SS_PREP_CHUNKED_MATVEC asks for it.
+enum : unsigned { SS_PREP_PER_STATE_COMMIT = 1, SS_PREP_PER_STATE_MATVEC = 2, SS_PREP_CHUNKED_MATVEC = 4 };
+static constexpr size_t PREP_BATCH_COMMIT_MIN = 2;
+static constexpr bool PREP_CHUNKED_MATVEC_DEFAULT = false;
+static std::vector<SpartanPrepSNARK*> prep_prove_batch_from(const SpartanProverKey& pk, size_t count, bool is_small, Tape* tapes, unsigned flags,
+                                                            const std::function<void(sp_table* const* W)>& fill_W, double* phase_ms) {
+  const sp_dims& d = pk.dims;
+  std::vector<std::unique_ptr<SpartanPrepSNARK>> st(count);
+  size_t at = (size_t)-1;  // the state a per-state step is working on (names the state in an error)
+  try {
+    sp_ctx* ctx = pk.ctx;
+    const size_t M = pk.num_vars, N = d.num_cons;
+    double ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    const double t_begin = now_ms();
+    double t_last = t_begin;
+    auto phase = [&](int k) {
+      const double t = now_ms();
+      ms[k] += t - t_last;
+      t_last = t;
+    };
+    unsigned state_flags = 0;
+    {
+      const char* e = getenv("SPARTAN_LZ_DIRECT");
+      if (e && e[0] == '1') state_flags |= FLAG_LZ_DIRECT;
+      e = getenv("SPARTAN_PREFIX_CACHE");
+      if (e && e[0] == '1') state_flags |= FLAG_PREFIX_CACHE;
+    }
+    // 1. witness
+    std::vector<sp_table*> Ws(count);
+    for (at = 0; at < count; ++at) {
+      st[at].reset(new SpartanPrepSNARK());
+      SpartanPrepSNARK* ps = st[at].get();
+      ps->bg.set_spin_policy(&helper_may_spin);
+      ps->bg2.set_spin_policy(&helper_may_spin);
+      ps->is_small = is_small;
+      ps->key = &pk;
+      ps->flags = state_flags;
+      ck(sp_table_zeros(ctx, M, (size_t)-1, (size_t)-1, &ps->W), "alloc W");
+      Ws[at] = ps->W;
+    }
+    at = (size_t)-1;
+    fill_W(Ws.data());
+    phase(0);
+    // 2. blinds: PCS::blind (hyrax_pc.rs:192-205) from tape k, shared first
+    const size_t CW = DEFAULT_COMMITMENT_WIDTH;
+    const size_t rows_shared = d.num_shared_unpadded ? (d.num_shared + CW - 1) / CW : 0;
+    const size_t rows_pre = d.num_precommitted_unpadded ? (d.num_precommitted + CW - 1) / CW : 0;
+    for (at = 0; at < count; ++at) {
+      SpartanPrepSNARK* ps = st[at].get();
+      ps->rows_shared = rows_shared;
+      ps->rows_precommitted = rows_pre;
+      ps->r_W_fixed.resize(rows_shared + rows_pre);
+      for (auto& b : ps->r_W_fixed) b = tapes[at].next();
+      ps->comm_W_fixed.resize(ps->r_W_fixed.size());
+    }
+    at = (size_t)-1;
+    // 3. commit: the shared segment of every state, then the precommitted one
+    const bool batch_commit = !(flags & SS_PREP_PER_STATE_COMMIT) && count >= PREP_BATCH_COMMIT_MIN;
+    for (int seg = 0; seg < 2; ++seg) {
+      const size_t rows = seg == 0 ? rows_shared : rows_pre, first = seg == 0 ? 0 : rows_shared;
+      const size_t off = seg == 0 ? 0 : d.num_shared, n = seg == 0 ? d.num_shared : d.num_precommitted;
+      if (!rows) continue;
+      if (batch_commit) {
+        std::vector<const uint64_t*> bl(count);
+        std::vector<uint64_t*> out(count);
+        for (size_t k = 0; k < count; ++k) {
+          bl[k] = u64p(st[k]->r_W_fixed.data() + first);
+          out[k] = u64p(&st[k]->comm_W_fixed[first].x);
+        }
+        ck(sp_hyrax_commit_batch(ctx, pk.ck, count, Ws.data(), off, n, bl.data(), out.data()), seg == 0 ? "commit shared" : "commit precommitted");
+      } else {
+        for (at = 0; at < count; ++at)
+          ck(sp_hyrax_commit(ctx, pk.ck, Ws[at], off, n, u64p(st[at]->r_W_fixed.data() + first), is_small ? 1 : 0, u64p(&st[at]->comm_W_fixed[first].x)),
+             seg == 0 ? "commit shared" : "commit precommitted");
+        at = (size_t)-1;
+      }
+      for (size_t k = 0; k < count; ++k)
+        (seg == 0 ? st[k]->comm_shared_bytes : st[k]->comm_pre_bytes) = commitment_bytes(st[k]->comm_W_fixed.data() + first, rows);
+    }
+    phase(1);
+    // 4. tables (see prep_prove_from)
+    for (at = 0; at < count; ++at) {
+      SpartanPrepSNARK* ps = st[at].get();
+      const size_t fixed = ps->comm_W_fixed.size(), rows_all = (M + CW - 1) / CW;
+      if (!(ps->flags & FLAG_LZ_DIRECT) && d.num_rest_unpadded == 0 && d.num_challenges == 0 && fixed >= 1 && fixed + 1 <= 512 && rows_all > 1) {
+        const char* mode = getenv("SPARTAN_PREP_TABLES");
+        ps->lz_points.assign(ps->comm_W_fixed.begin(), ps->comm_W_fixed.end());
+        ps->lz_points.push_back(pk.gens[CW]);  // h
+        ps->lz_mode = !mode || !strcmp(mode, "lazy") ? 1 : (!strcmp(mode, "off") ? 0 : 2);
+        if (mode && !strcmp(mode, "sync")) ck(sp_fbtables_create(ctx, u64p(&ps->lz_points[0].x), ps->lz_points.size(), &ps->lz_tables), "tables of the committed rows");
+        else if (ps->lz_mode == 2) ck(sp_fbtables_create_async(ctx, u64p(&ps->lz_points[0].x), ps->lz_points.size(), &ps->lz_tables), "tables of the committed rows");
+      }
+    }
+    phase(2);
+    // 5. multiply_vec_precommitted (src/r1cs/mod.rs:1112-1128) for every state: z_k = [W_k cached | 0 ...]
+    for (at = 0; at < count; ++at) {
+      SpartanPrepSNARK* ps = st[at].get();
+      ck(sp_table_zeros(ctx, 2 * M, (size_t)-1, (size_t)-1, &ps->z), "alloc z");
+      ck(sp_table_copy(ctx, ps->z, 0, ps->W, 0, d.num_shared + d.num_precommitted), "copy W");
+      ck(sp_table_set_len(ps->z, pk.num_cols, (size_t)-1, (size_t)-1), "z len");
+      for (sp_table** t : {&ps->caz, &ps->cbz, &ps->ccz, &ps->az, &ps->bz, &ps->cz}) ck(sp_table_zeros(ctx, N, (size_t)-1, (size_t)-1, t), "alloc Az");
+    }
+    if (!(flags & SS_PREP_PER_STATE_MATVEC) && (PREP_CHUNKED_MATVEC_DEFAULT || (flags & SS_PREP_CHUNKED_MATVEC)) && count >= 2) {
+      at = (size_t)-1;
+      std::vector<const sp_table*> zs(count);
+      std::vector<sp_table*> az(count), bz(count), cz(count);
+      for (size_t k = 0; k < count; ++k) zs[k] = st[k]->z, az[k] = st[k]->caz, bz[k] = st[k]->cbz, cz[k] = st[k]->ccz;
+      ck(sp_multiply_vec_chunked(ctx, pk.S, zs.data(), count, az.data(), bz.data(), cz.data()), "multiply_vec_precommitted");
+    } else {
+      for (at = 0; at < count; ++at) ck(sp_multiply_vec(ctx, pk.S, st[at]->z, st[at]->caz, st[at]->cbz, st[at]->ccz), "multiply_vec_precommitted");
+    }
+    at = (size_t)-1;
+    if (getenv("SPARTAN_PREP_TRACE")) ck(sp_ctx_synchronize(ctx), "sync");
+    phase(3);
+    // 6. scratch
+    const char* no_p0 = getenv("SPARTAN_ROUND0_PRODUCTS");
+    for (at = 0; at < count; ++at) {
+      SpartanPrepSNARK* ps = st[at].get();
+      ck(sp_table_zeros(ctx, N, (size_t)-1, (size_t)-1, &ps->rx), "alloc rx");
+      if (N >= 2 && !(no_p0 && no_p0[0] == '0')) {
+        ck(sp_table_zeros(ctx, N / 2, (size_t)-1, (size_t)-1, &ps->p0), "alloc round-0 products");
+        ck(sp_table_zeros(ctx, N / 2, (size_t)-1, (size_t)-1, &ps->p1), "alloc round-0 products");
+      }
+      ck(sp_table_zeros(ctx, 2 * M, (size_t)-1, (size_t)-1, &ps->abc), "alloc poly_ABC");
+    }
+    at = (size_t)-1;
+    ck(sp_ctx_synchronize(ctx), "sync");
+    phase(4);
+    ms[6] = now_ms() - t_begin;
+    for (size_t k = 0; k < count; ++k)
+      for (int i = 0; i < 8; ++i) st[k]->prep_ms[i] = ms[i] / (double)count;
+    if (phase_ms) memcpy(phase_ms, ms, sizeof ms);
+    if (getenv("SPARTAN_PREP_TRACE"))
+      fprintf(stderr, "prep_prove_batch(%zu): witness %.3f commit %.3f tables %.3f matvec %.3f scratch %.3f total %.3f ms\n", count, ms[0], ms[1], ms[2], ms[3], ms[4], ms[6]);
+  } catch (const Error& e) {
+    // every state made so far goes with `st`
+    throw Error(e.code, "prep_prove_batch: " + (at == (size_t)-1 ? std::string() : "state " + std::to_string(at) + ": ") + e.what());
+  }
+  std::vector<SpartanPrepSNARK*> out(count);
+  for (size_t k = 0; k < count; ++k) out[k] = st[k].release();
+  return out;
+}
+
+std::vector<SpartanPrepSNARK*> prep_prove_batch(const SpartanProverKey& pk, const uint64_t* const* witnesses_u64, size_t n_witness, size_t count, bool is_small, Tape* tapes,
+                                                unsigned flags, double* phase_ms) {
+  const sp_dims& d = pk.dims;
+  for (size_t k = 0; k < count; ++k) {
+    if (!witnesses_u64[k] && n_witness) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "prep_prove_batch: state " + std::to_string(k) + ": null witness");
+  }
+  if (n_witness != d.num_shared_unpadded + d.num_precommitted_unpadded + d.num_rest_unpadded)
+    throw Error(SP_ERR_INVALID_WITNESS_LENGTH, "prep_prove_batch: state 0: InvalidWitnessLength");
+  sp_ctx* ctx = pk.ctx;
+  return prep_prove_batch_from(pk, count, is_small, tapes, flags, [&](sp_table* const* W) {
+    for (size_t k = 0; k < count; ++k) {
+      auto put = [&](size_t dst, size_t src, size_t cnt) { ck(sp_table_write_u64(ctx, W[k], dst, witnesses_u64[k] + src, cnt), "upload W"); };
+      put(0, 0, d.num_shared_unpadded);
+      put(d.num_shared, d.num_shared_unpadded, d.num_precommitted_unpadded);
+      if (d.num_challenges == 0) put(d.num_shared + d.num_precommitted, d.num_shared_unpadded + d.num_precommitted_unpadded, d.num_rest_unpadded);
+    }
+  }, phase_ms);
+}
+
+std::vector<SpartanPrepSNARK*> prep_prove_sha256_batch(const SpartanProverKey& pk, const sp_sha256_plan* plan, const uint8_t* msgs, size_t len, size_t count, bool is_small,
+                                                       Tape* tapes, uint64_t* out_publics, unsigned flags, double* phase_ms) {
+  const sp_dims& d = pk.dims;
+  uint64_t info[5];
+  ck(sp_sha256_plan_info(plan, info), "prep_prove_batch: plan info");
+  if (d.num_shared_unpadded != 0 || d.num_rest_unpadded != 0 || d.num_challenges != 0 || info[0] != d.num_precommitted_unpadded)
+    throw Error(SP_ERR_INVALID_WITNESS_LENGTH, "prep_prove_batch: InvalidWitnessLength: the plan's variable count is not the key's");
+  if (len != info[3] || !info[4] || d.num_public != 256)
+    throw Error(SP_ERR_INVALID_INPUT_LENGTH, "prep_prove_batch: the plan does not serve this message length / this key is not a SHA-256 digest circuit");
+  sp_ctx* ctx = pk.ctx;
+  std::vector<uint8_t> digests(32 * count);
+  std::vector<SpartanPrepSNARK*> out = prep_prove_batch_from(pk, count, is_small, tapes, flags, [&](sp_table* const* W) {
+    ck(sp_sha256_witness(ctx, plan, msgs, len, count, W, d.num_shared, digests.data()), "sha256 witness");
+  }, phase_ms);
+  for (size_t k = 0; k < count; ++k)
+    for (int i = 0; i < 256; ++i) out_publics[256 * k + i] = (digests[32 * k + i / 8] >> (7 - i % 8)) & 1u;
+  return out;
+}
+
 
 // SpartanSNARK::prove (src/spartan.rs:219-466)
 // `synth`: circuit.synthesize(.., Some(&challenges)) for circuits with verifier challenges (bellpepper/r1cs.rs:443-461): receives the challenges and
@@ -2007,8 +2205,65 @@ int ss_prep_prove_sha256(void* pk, const sp_sha256_plan* plan, const uint8_t* ms
     return catch_all();
   }
 }
+// prep_prove for `count` states of one key in one pass (see prep_prove_batch_from): witnesses_u64[k] = the n_witness words of state k (one length for all:
+// the key's), tapes[k] / tape_blocks[k] = its tape, tape_used[k] = the blocks it consumed, out_ps[k] = its state - the state ss_prep_prove makes of the same
+// witness and tape, to be proved alone or in any ss_prove_batch, checked, freed on its own. phase_ms (8, optional): the batch's wall-clock per phase in
+// ss_prep_phases' slots. flags: SS_PREP_PER_STATE_COMMIT (1) = one sp_hyrax_commit per state, SS_PREP_PER_STATE_MATVEC (2) = one sp_multiply_vec per state
+// (what the driver takes anyway, as measured), SS_PREP_CHUNKED_MATVEC (4) = the cached products through sp_multiply_vec_chunked.
+// count == 0, null arguments and a wrong witness length are refused before any device work; on any failure every state made so far is freed and out_ps
+// is not written; the error names the state where one is at fault ("prep_prove_batch: state 2: ...").
+int ss_prep_prove_batch_opts(void* pk, const uint64_t* const* witnesses_u64, size_t n_witness, size_t count, int is_small, const uint8_t* const* tapes,
+                             const size_t* tape_blocks, size_t* tape_used, void** out_ps, double* phase_ms, unsigned flags) {
+  try {
+    if (count == 0) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "prep_prove_batch: count must be at least 1");
+    if (!pk || !witnesses_u64 || !tapes || !tape_blocks || !out_ps) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "prep_prove_batch: null argument");
+    std::vector<Tape> ts;
+    for (size_t k = 0; k < count; ++k) {
+      if (!tapes[k]) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "prep_prove_batch: state " + std::to_string(k) + ": null tape");
+      ts.push_back(Tape{tapes[k], tape_blocks[k]});
+    }
+    std::vector<SpartanPrepSNARK*> st = prep_prove_batch(*(SpartanProverKey*)pk, witnesses_u64, n_witness, count, is_small != 0, ts.data(), flags, phase_ms);
+    for (size_t k = 0; k < count; ++k) {
+      out_ps[k] = st[k];
+      if (tape_used) tape_used[k] = ts[k].pos;
+    }
+    return 0;
+  } catch (...) {
+    return catch_all();
+  }
+}
+int ss_prep_prove_batch(void* pk, const uint64_t* const* witnesses_u64, size_t n_witness, size_t count, int is_small, const uint8_t* const* tapes, const size_t* tape_blocks,
+                        size_t* tape_used, void** out_ps, double* phase_ms) {
+  return ss_prep_prove_batch_opts(pk, witnesses_u64, n_witness, count, is_small, tapes, tape_blocks, tape_used, out_ps, phase_ms, 0);
+}
+// the same with the SHA-256 witnesses generated on the device in ONE launch (see prep_prove_sha256): msgs = count x len bytes, out_publics = count x 256 digest bits
+int ss_prep_prove_sha256_batch_opts(void* pk, const sp_sha256_plan* plan, const uint8_t* msgs, size_t len, size_t count, int is_small, const uint8_t* const* tapes,
+                                    const size_t* tape_blocks, size_t* tape_used, void** out_ps, uint64_t* out_publics, double* phase_ms, unsigned flags) {
+  try {
+    if (count == 0) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "prep_prove_batch: count must be at least 1");
+    if (!pk || !plan || (!msgs && len) || !tapes || !tape_blocks || !out_ps || !out_publics) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "prep_prove_batch: null argument");
+    std::vector<Tape> ts;
+    for (size_t k = 0; k < count; ++k) {
+      if (!tapes[k]) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "prep_prove_batch: state " + std::to_string(k) + ": null tape");
+      ts.push_back(Tape{tapes[k], tape_blocks[k]});
+    }
+    std::vector<SpartanPrepSNARK*> st = prep_prove_sha256_batch(*(SpartanProverKey*)pk, plan, msgs, len, count, is_small != 0, ts.data(), out_publics, flags, phase_ms);
+    for (size_t k = 0; k < count; ++k) {
+      out_ps[k] = st[k];
+      if (tape_used) tape_used[k] = ts[k].pos;
+    }
+    return 0;
+  } catch (...) {
+    return catch_all();
+  }
+}
+int ss_prep_prove_sha256_batch(void* pk, const sp_sha256_plan* plan, const uint8_t* msgs, size_t len, size_t count, int is_small, const uint8_t* const* tapes,
+                               const size_t* tape_blocks, size_t* tape_used, void** out_ps, uint64_t* out_publics, double* phase_ms) {
+  return ss_prep_prove_sha256_batch_opts(pk, plan, msgs, len, count, is_small, tapes, tape_blocks, tape_used, out_ps, out_publics, phase_ms, 0);
+}
 void ss_prep_free(void* ps) { delete (SpartanPrepSNARK*)ps; }
-// host wall-clock of the last prep_prove's phases, ms: witness, commit, tables, matvec, scratch, (spare), total, (spare)
+// host wall-clock of the last prep_prove's phases, ms: witness, commit, tables, matvec, scratch, (spare), total, (spare). A state made by
+// ss_prep_prove_batch* carries the BATCH's phase times divided by its count (the phases ran once for all states).
 // the FixedBaseMul tables of the committed rows (queued by prep_prove): 1 = built, 0 = still building (wait != 0: blocks), -1 = this state has none
 int ss_prep_tables_ready(void* ps, int wait) {
   auto* p = (SpartanPrepSNARK*)ps;

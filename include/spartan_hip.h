@@ -298,6 +298,18 @@ int sp_multiply_vec_incremental_round0(sp_ctx* ctx, const sp_shape* s, const sp_
 /* SplitR1CSShape::bind_and_prepare_poly_ABC[_full] (:1235-1321): out[col] = sum_row rx[row] (A + r B + r^2 C)[row,col],
  * written into the first out_len elements of `out` */
 int sp_poly_abc(sp_ctx* ctx, const sp_shape* s, const sp_table* rx, const uint64_t r[4], size_t out_len, sp_table* out);
+/* EqPolynomial::evals_from_points (src/polys/eq.rs:59-117) + SplitR1CSShape::bind_and_prepare_poly_ABC[_full] (:1235-1321) for `count` proofs of one
+ * shape in one pass: the first out_len elements of out[k] are word for word what sp_eq_table_into(ctx, r_x + 4 ell k, ell, rx) followed by
+ * sp_poly_abc(ctx, s, rx, r + 4 k, out_len, out[k]) write (the zero tail past the length of z included); elements past out_len and the length fields of
+ * out[k] are left alone. Chunks of sp_poly_abc_batch_chunk() proofs share one walk over A, B and C: the chunk's eq tables are written interleaved
+ * (element `row` of all its proofs adjacent, grow-only context memory of chunk x num_cons elements, reused by every chunk), so one index / code load
+ * starts a gather for every proof of the chunk. r_x: count x ell elements, r: count elements; both may die when the call returns. Asynchronous on the
+ * context's stream like sp_poly_abc. Every argument is checked before the first launch and a refused call (SP_ERR_INVALID_INPUT_LENGTH) has written
+ * nothing: a null argument or table, 2^ell != num_cons, out_len shorter than z, a table of fewer than out_len elements, the same table as two outputs -
+ * with the offending index in sp_last_error ("..., proof 3"). count == 0 is a no-op. */
+int sp_poly_abc_batch(sp_ctx* ctx, const sp_shape* s, size_t count, const uint64_t* r_x, size_t ell, const uint64_t* r, size_t out_len, sp_table* const* out);
+/* proofs per launch of sp_poly_abc_batch (a compile-time constant of the kernel) */
+size_t sp_poly_abc_batch_chunk(void);
 
 /* R1CSShape::is_sat / is_sat_relaxed (src/r1cs/mod.rs:358-394, :430-471): the witness checked against the constraints ON THE DEVICE - the drivers never
  * hold W on the host once witnesses are generated there. The entry points return SP_OK whenever the check itself RAN; whether the instance is satisfied

@@ -6,6 +6,7 @@
 //                      booleanity rows) one block each.
 //   k_matrix_evals_batched  evaluate_with_tables_fast (src/r1cs/mod.rs:1216-1226) for a chunk of (T_x, T_y) pairs in one walk (kernels_mateval.hpp)
 //   k_spmv3_multi      multiply_vec_batched (sparse.rs:237-302) for a chunk of vectors in one walk (kernels_spmv_multi.hpp)
+//   k_pab_*            evals_rx + poly_ABC (src/polys/eq.rs:59-117, src/r1cs/mod.rs:1235-1321) for a chunk of proofs in one walk over interleaved eq tables (kernels_polyabc_batch.hpp)
 //   k_r1cs_residual    R1CSShape::is_sat / is_sat_relaxed (src/r1cs/mod.rs:358-394, :430-471): the row check behind multiply_vec (kernels_sat.hpp)
 // Entries keep the reference's classes: +-1 and |k| in 2..7 as an int8 code (add / sub / double-add chains, sparse.rs:137-155),
 // everything else as a full field coefficient.
@@ -245,6 +246,7 @@ __global__ void __launch_bounds__(256) k_polyabc_short_and_long(PolyAbcArgs a, c
 }  // namespace spk
 
 #include "kernels_mateval.hpp"
+#include "kernels_polyabc_batch.hpp"
 #include "kernels_spmv_multi.hpp"
 
 // ---- host side: classification and upload ---------------------------------------------------------------------------
@@ -667,6 +669,75 @@ int sp_poly_abc(sp_ctx* c, const sp_shape* s, const sp_table* rx, const uint64_t
     hipLaunchKernelGGL(spk::k_polyabc_short_and_long, dim3((unsigned)(blocks + spk::LONG_NB_MAX * s->n_long_cols + zblocks)), dim3(256), 0, c->stream, a, rx->d, s->d_short_order,
                        s->n_short, out->d, s->d_long_cols, (unsigned)s->n_long_cols, partials, tickets, (unsigned)blocks, (size_t)s->num_cols, zero_n, s->col_permuted ? 1 : 0);
   });
+  return SP_OK;
+}
+
+// evals_rx + poly_ABC of `count` proofs of one shape: chunks of PAB_KC proofs, per chunk the pyramids of its points, the outer product that writes the
+// chunk's eq tables interleaved (the context's workspace, reused by every chunk: the stream orders them) and one walk (kernels_polyabc_batch.hpp). Every
+// argument is checked before the first launch, so a refused call has written nothing. The points and challenges travel by value: nothing of the
+// caller's is read after the call returns. The arrival counters are this entry point's own (not sp_poly_abc's).
+size_t sp_poly_abc_batch_chunk(void) { return (size_t)spk::PAB_KC; }
+int sp_poly_abc_batch(sp_ctx* c, const sp_shape* s, size_t count, const uint64_t* r_x, size_t ell, const uint64_t* r_, size_t out_len, sp_table* const* out) {
+  if (!c || !s || (count && ((ell && !r_x) || !r_ || !out))) return fail(SP_ERR_INVALID_INPUT_LENGTH, "poly_abc_batch: null argument");
+  if (count == 0) return SP_OK;
+  const size_t nrows = s->dims.num_cons;
+  if (ell > (size_t)spk::PAB_MAX_ELL || ((size_t)1 << ell) != nrows) return fail(SP_ERR_INVALID_INPUT_LENGTH, "poly_abc_batch: r_x must have log2(num_cons) coordinates");
+  if (out_len < s->num_cols) return fail(SP_ERR_INVALID_INPUT_LENGTH, "poly_abc_batch: out_len is shorter than z");
+  for (size_t k = 0; k < count; ++k) {
+    const std::string at = ", proof " + std::to_string(k);
+    if (!out[k]) return fail(SP_ERR_INVALID_INPUT_LENGTH, "poly_abc_batch: null table" + at);
+    if (out[k]->cap < out_len) return fail(SP_ERR_INVALID_INPUT_LENGTH, "poly_abc_batch: output table too short" + at);
+    for (size_t j = 0; j < k; ++j)
+      if (out[j] == out[k] || out[j]->d == out[k]->d) return fail(SP_ERR_INVALID_INPUT_LENGTH, "poly_abc_batch: the same table as the output of proof " + std::to_string(j) + at);
+  }
+  constexpr size_t KC = (size_t)spk::PAB_KC;
+  const int hi_bits = (int)(ell / 2), lo_bits = (int)ell - hi_bits;  // both <= 10 up to 2^20 rows: every level of both pyramids stays in LDS
+  const size_t pyr_hi = (size_t)2 << hi_bits, pyr_stride = pyr_hi + ((size_t)2 << lo_bits);
+  const size_t ticket_bytes = (s->n_long_cols + 1) * sizeof(unsigned);
+  const bool fresh = c->ws_bytes[sp_ctx::WS_POLYABC_BATCH_TICKETS] < ticket_bytes;
+  unsigned* tickets = (unsigned*)c->workspace(sp_ctx::WS_POLYABC_BATCH_TICKETS, ticket_bytes);
+  if (!tickets) return SP_ERR_NO_DEVICE;
+  if (fresh) SP_HIP(hipMemsetAsync(tickets, 0, c->ws_bytes[sp_ctx::WS_POLYABC_BATCH_TICKETS], c->stream));
+  fe_t* partials = (fe_t*)c->workspace(sp_ctx::WS_POLYABC_BATCH_PARTIALS, (s->n_long_cols + 1) * spk::LONG_NB_MAX * 3 * KC * sizeof(fe_t));
+  fe_t* pyr = (fe_t*)c->workspace(sp_ctx::WS_POLYABC_BATCH_PYRAMIDS, KC * pyr_stride * sizeof(fe_t));
+  fe_t* E = (fe_t*)c->workspace(sp_ctx::WS_POLYABC_BATCH_EQ, KC * nrows * sizeof(fe_t));
+  if (!partials || !pyr || !E) return SP_ERR_NO_DEVICE;
+  size_t blocks = (s->n_short + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  if (blocks == 0) blocks = 1;
+  const size_t zero_n = out_len - s->num_cols;
+  size_t zblocks = (2 * zero_n + 256 * 16 - 1) / (256 * 16);  // 16 stores of 16 bytes per thread and table
+  if (zblocks > 2048) zblocks = 2048;
+  size_t eblocks = (KC * nrows + 255) / 256;
+  if (eblocks > 8192) eblocks = 8192;
+  const uint64_t nnz = s->nnz[0] + s->nnz[1] + s->nnz[2];
+  const dim3 grid((unsigned)(blocks + spk::LONG_NB_MAX * s->n_long_cols + zblocks));
+  for (size_t k0 = 0; k0 < count; k0 += KC) {
+    const size_t kc = std::min<size_t>(KC, count - k0);
+    spk::PabPoints pts;
+    spk::PabArgs a;
+    for (int m = 0; m < 3; ++m) a.m[m] = s->col[m].view();
+    for (size_t j = 0; j < KC; ++j) {  // (the unused slots of a ragged chunk are never dereferenced)
+      const size_t k = k0 + (j < kc ? j : 0);
+      if (ell) memcpy(pts.v[j], r_x + 4 * ell * k, ell * sizeof(fe_t));
+      memcpy(&a.r[j], r_ + 4 * k, sizeof(fe_t));
+      a.r2[j] = fe_mul<S>(a.r[j], a.r[j]);
+      a.out[j] = out[k]->d;
+    }
+    a.kc = (int)kc;
+    c->timed_kernel("eq_levels_batch", (uint64_t)kc * pyr_stride * sizeof(fe_t), spk::k_pab_eq_levels, dim3(2, (unsigned)kc), dim3(1024), pts, (int)ell, hi_bits, pyr,
+                    (unsigned long long)pyr_stride, (unsigned long long)pyr_hi);
+    c->timed_kernel("eq_table_batch", 32ull * nrows * kc, spk::k_pab_eq_outer, dim3((unsigned)eblocks), dim3(256), (const fe_t*)pyr, (unsigned long long)pyr_stride,
+                    (unsigned long long)spk::eq_level_offset(hi_bits), (unsigned long long)(pyr_hi + spk::eq_level_offset(lo_bits)), lo_bits, nrows, (int)kc, E);
+    // structure once per chunk (4-byte index + code, column pointers of both classes) + one 32-byte gather per entry and proof + the output per proof
+    const uint64_t bytes = 5ull * nnz + 24ull * s->num_cols + kc * (32ull * nnz + 32ull * out_len);
+    if (kc == KC)
+      c->timed_kernel("poly_abc_batch", bytes, spk::k_pab_walk<true>, grid, dim3(256), a, (const fe_t*)E, (const unsigned*)s->d_short_order, s->n_short,
+                      (const unsigned*)s->d_long_cols, (unsigned)s->n_long_cols, partials, tickets, (unsigned)blocks, (size_t)s->num_cols, zero_n, s->col_permuted ? 1 : 0);
+    else
+      c->timed_kernel("poly_abc_batch", bytes, spk::k_pab_walk<false>, grid, dim3(256), a, (const fe_t*)E, (const unsigned*)s->d_short_order, s->n_short,
+                      (const unsigned*)s->d_long_cols, (unsigned)s->n_long_cols, partials, tickets, (unsigned)blocks, (size_t)s->num_cols, zero_n, s->col_permuted ? 1 : 0);
+  }
   return SP_OK;
 }
 

@@ -254,6 +254,7 @@ struct sp_ctx {
          WS_MATEVAL_PARTIALS, WS_MATEVAL_TICKETS, WS_MATEVAL_OUT,  // sp_shape_matrix_evals_batched: block sums, arrival counters, the 3 results per pair
          WS_LOCKSTEP_EQ, WS_LOCKSTEP_PARTIALS, WS_LOCKSTEP_PARAMS,  // the lockstep sum-checks: eq pyramids per instance, block partials, taus / (lo_eff, hi_eff) per round
          WS_OPENING_BLOCKS, WS_OPENING_VECS, WS_OPENING_PARAMS, WS_OPENING_WALK,  // sp_hyrax_prove_batch: uniform blocks | d, LZ, z | instances, points | tickets, block sums, results
+         WS_POLYABC_BATCH_EQ, WS_POLYABC_BATCH_PYRAMIDS, WS_POLYABC_BATCH_PARTIALS, WS_POLYABC_BATCH_TICKETS,  // sp_poly_abc_batch: a chunk's interleaved eq tables, its eq pyramids, the long columns' partial triples, their arrival counters
          WS_PER_LANE,
          WS_SLOTS = 2 * WS_PER_LANE };  // lane 1 = the auxiliary stream used by asynchronous MSM jobs
   void* ws_ptr[WS_SLOTS] = {};

@@ -65,6 +65,12 @@ def multiply_vec_chunk() -> int:
     return int(lib().sp_multiply_vec_chunk())
 
 
+def poly_abc_batch_chunk() -> int:
+    """proofs per launch of sp_poly_abc_batch (sp_poly_abc_batch_chunk): where a batch crosses into the next chunk"""
+    lib().sp_poly_abc_batch_chunk.restype = ctypes.c_size_t
+    return int(lib().sp_poly_abc_batch_chunk())
+
+
 def __getattr__(name):
     if name == "SPMV_KC":  # read from the library, not restated here
         return multiply_vec_chunk()
@@ -883,6 +889,16 @@ class Shape:
     def poly_abc(self, rx: Table, r, out_len, out: Table):
         r = np.ascontiguousarray(r, dtype=np.uint64).reshape(4)
         check(lib().sp_poly_abc(self.ctx.h, self.h, rx.h, p64(r), ctypes.c_size_t(out_len), out.h))
+
+    def poly_abc_batch(self, r_x, r, out_len, outs):
+        """sp_poly_abc_batch: evals_rx + poly_ABC of len(outs) proofs in one pass. r_x: (K, ell, 4) uint64, r: (K, 4) uint64, outs: K tables."""
+        n = len(outs)
+        r_x = np.ascontiguousarray(r_x, dtype=np.uint64)
+        r_x = r_x.reshape(n, -1, 4) if n else r_x.reshape(1, -1, 4)[:, :0]
+        r = np.ascontiguousarray(r, dtype=np.uint64).reshape(n, 4)
+        arr = (ctypes.c_void_p * max(n, 1))(*[t.h for t in outs])
+        check(lib().sp_poly_abc_batch(self.ctx.h, self.h, ctypes.c_size_t(n), p64(r_x) if n else None, ctypes.c_size_t(r_x.shape[1]), p64(r) if n else None,
+                                      ctypes.c_size_t(out_len), arr))
 
     def __del__(self):
         try:

@@ -93,6 +93,10 @@ def from_label(label: bytes, n: int):
 REST_HOOK = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, hip.c_u64p, ctypes.c_size_t, hip.c_u64p)
 SP_ERR_UNSAT = -6  # SpartanError::UnSat: what ss_prep_is_sat / nnz_prep_is_sat return for a finding (the reason is in the report)
 SS_BATCH_PER_PROOF_OPENING = 1  # ss_prove_batch_opts flag (host/spartan_snark.cpp)
+SS_BATCH_PER_PROOF_POLYABC = 2  # ... one sp_eq_table_into + sp_poly_abc per proof
+SS_BATCH_BATCHED_POLYABC = 4  # ... evals_rx + poly_ABC of all proofs through sp_poly_abc_batch
+SS_BATCH_PER_PROOF_REST_COMMIT = 8  # ... one rest commitment call per proof
+SS_BATCH_BATCHED_REST_COMMIT = 16  # ... the rest commitments of all proofs in one call
 SS_PREP_PER_STATE_COMMIT = 1  # ss_prep_prove_batch_opts / ss_prep_prove_sha256_batch_opts flags: one sp_hyrax_commit per state ...
 SS_PREP_PER_STATE_MATVEC = 2  # ... one sp_multiply_vec per state (what the driver takes unless asked otherwise: measured, profiles/prep_prove_batch.md)
 SS_PREP_CHUNKED_MATVEC = 4  # ... the cached products through sp_multiply_vec_chunked
@@ -253,11 +257,19 @@ class SpartanSNARK:
             used_all.append(used.value)
         return used_all
 
-    def prove_batch(self, tapes, states=None, per_proof_opening=False):
+    def prove_batch(self, tapes, states=None, per_proof_opening=False, per_proof_polyabc=None, per_proof_rest_commit=None):
         """ss_prove_batch_opts over self.batch (or `states`, a list of (prep state, publics) pairs): one tape per proof -> ([(proof words, blocks used)],
         {phase: ms of the whole batch}). Proof k is word for word what prove() returns on state k with tape k; the outer and the inner sum-check of all
         proofs run in lockstep (sp_sumcheck_cubic3_lockstep / sp_sumcheck_quad_lockstep) and the openings are one sp_hyrax_prove_batch call -
-        per_proof_opening=True (SS_BATCH_PER_PROOF_OPENING) keeps them as one sp_hyrax_prove per proof; everything else per proof."""
+        per_proof_opening=True (SS_BATCH_PER_PROOF_OPENING) keeps them as one sp_hyrax_prove per proof. per_proof_polyabc: True = one sp_eq_table_into +
+        sp_poly_abc per proof, False = one sp_poly_abc_batch call, None = what the driver measured to be faster; per_proof_rest_commit likewise for the
+        rest commitments (one call per proof / one sp_fixed_base_mul_h or sp_hyrax_commit_batch call for all). Still per proof: the z assembly,
+        sp_multiply_vec_incremental, the eval_W commitment and the lz_tables build."""
+        flags = SS_BATCH_PER_PROOF_OPENING if per_proof_opening else 0
+        if per_proof_polyabc is not None:
+            flags |= SS_BATCH_PER_PROOF_POLYABC if per_proof_polyabc else SS_BATCH_BATCHED_POLYABC
+        if per_proof_rest_commit is not None:
+            flags |= SS_BATCH_PER_PROOF_REST_COMMIT if per_proof_rest_commit else SS_BATCH_BATCHED_REST_COMMIT
         states = self.batch if states is None else states
         K = len(states)
         if len(tapes) != K:
@@ -276,7 +288,7 @@ class SpartanSNARK:
         used = (ctypes.c_size_t * max(K, 1))()
         ms = (ctypes.c_double * 7)()
         _check(lib().ss_prove_batch_opts(self.pk, pss, ctypes.c_size_t(K), hip.p64(pubs) if npub else None, ctypes.c_size_t(npub), tptr, tblk, used, hip.p64(words),
-                                         ctypes.c_size_t(n), ms, ctypes.c_uint(SS_BATCH_PER_PROOF_OPENING if per_proof_opening else 0)))
+                                         ctypes.c_size_t(n), ms, ctypes.c_uint(flags)))
         return [(words[k].copy(), int(used[k])) for k in range(K)], dict(zip(PHASES, list(ms)))
 
     def prep_phases(self):

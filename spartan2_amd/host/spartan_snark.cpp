@@ -1439,11 +1439,30 @@ ProofBuf prove_reference_order(const SpartanProverKey& pk, SpartanPrepSNARK& ps,
 // run for proof 0 .. count - 1 before the next statement is begun, and the outer and the inner sum-check run as ONE lockstep sum-check each
 // (sp_sumcheck_cubic3_lockstep / sp_sumcheck_quad_lockstep: a launch per round for all proofs, one wait, `count` transcripts fed on this thread).
 // The openings are ONE sp_hyrax_prove_batch call (every device stage a launch for all proofs; never announced ahead: the announcement is one slot per
-// context); flags & SS_BATCH_PER_PROOF_OPENING keeps them as `count` sp_hyrax_prove calls, one after the other. Everything else is the per-proof call
-// prove_reference_order makes - the commitments, the matrix-vector product and poly_ABC are NOT batched. Proof k is word for word what
+// context); flags & SS_BATCH_PER_PROOF_OPENING keeps them as `count` sp_hyrax_prove calls, one after the other. evals_rx + poly_ABC and the rest
+// commitments have a batched form as well (flags and defaults below). Still the per-proof calls prove_reference_order makes: the z assembly,
+// sp_multiply_vec_incremental, the eval_W commitment and the lz_tables build. Proof k is word for word what
 // prove(pk, *ps[k], publics[k], tapes[k]) returns and consumes the same tape blocks; every state can be proved again afterwards, alone or in a batch.
 // pt (optional): the batch's wall-clock per phase, in prove's slots.
-enum : unsigned { SS_BATCH_PER_PROOF_OPENING = 1 };
+// flags & SS_BATCH_PER_PROOF_POLYABC / SS_BATCH_BATCHED_POLYABC: evals_rx + poly_ABC as one sp_eq_table_into + sp_poly_abc per proof / as ONE
+// sp_poly_abc_batch call; SS_BATCH_PER_PROOF_REST_COMMIT / SS_BATCH_BATCHED_REST_COMMIT: the rest commitments one call per proof / one call for all
+// (commit_zeros: one sp_fixed_base_mul_h over count x rows blinds; a non-empty rest segment: sp_hyrax_commit_batch). Same proofs either way; the flags
+// are there so that one process can compare the paths, and PER_PROOF wins when both of a pair are set. With neither, the driver takes what was measured
+// (profiles/prove_batch.md, config 2, one process, legs alternating): each constant is the smallest K from which the batched form is taken,
+// SIZE_MAX = never (the entry point stays reachable by flag). Rule: the smallest measured K (1, 4, 16) at which the median of the batch with both forms
+// batched lies below the MINIMUM of the same batch with that one form per proof.
+//   poly_ABC: 3.83 ms against a minimum of 3.94 at K = 4, 10.75 against 11.03 at K = 16 (the launches: 76 us a proof against 82): BATCH_POLYABC_MIN = 4.
+//   rest commitment (commit_zeros at config 2): 3.83 against 3.88 at K = 4, 10.75 against 11.20 at K = 16: BATCH_REST_COMMIT_MIN = 4.
+//   K = 2 and 3 were not measured and keep the per-proof calls.
+enum : unsigned {
+  SS_BATCH_PER_PROOF_OPENING = 1,
+  SS_BATCH_PER_PROOF_POLYABC = 2,
+  SS_BATCH_BATCHED_POLYABC = 4,
+  SS_BATCH_PER_PROOF_REST_COMMIT = 8,
+  SS_BATCH_BATCHED_REST_COMMIT = 16
+};
+static constexpr size_t BATCH_POLYABC_MIN = 4;
+static constexpr size_t BATCH_REST_COMMIT_MIN = 4;
 static void prove_batch_chunk(const SpartanProverKey& pk, SpartanPrepSNARK* const* pss, size_t count, const uint64_t* publics_u64, size_t npub, Tape* tapes,
                               ProofBuf* out, size_t first, double* ms, unsigned flags) {
   const sp_dims& d = pk.dims;
@@ -1478,6 +1497,8 @@ static void prove_batch_chunk(const SpartanProverKey& pk, SpartanPrepSNARK* cons
     t_last = t;
   };
   const size_t rows_rest = (d.num_rest + W_ - 1) / W_;
+  const bool batch_abc = !(flags & SS_BATCH_PER_PROOF_POLYABC) && ((flags & SS_BATCH_BATCHED_POLYABC) || count >= BATCH_POLYABC_MIN);
+  const bool batch_rest = rows_rest && !(flags & SS_BATCH_PER_PROOF_REST_COMMIT) && ((flags & SS_BATCH_BATCHED_REST_COMMIT) || count >= BATCH_REST_COMMIT_MIN);
   // :226-236 transcript, vk, public values; r1cs_instance_and_witness (src/bellpepper/r1cs.rs:411-540)
   each([&](Item& it, size_t k) {
     it.ps = pss[k];
@@ -1502,10 +1523,33 @@ static void prove_batch_chunk(const SpartanProverKey& pk, SpartanPrepSNARK* cons
     const size_t rows_pre = ps.comm_W_fixed.size();
     it.comm_W.resize(rows_pre + rows_rest);
     std::copy(ps.comm_W_fixed.begin(), ps.comm_W_fixed.end(), it.comm_W.begin());
+    if (batch_rest) return;
     if (rows_rest && d.num_rest_unpadded == 0) ck(sp_fixed_base_mul_h(ctx, pk.ck, u64p(it.r_W_rest.data()), rows_rest, u64p(&it.comm_W[rows_pre].x)), "commit_zeros");
     else if (rows_rest)
       ck(sp_hyrax_commit(ctx, pk.ck, ps.W, d.num_shared + d.num_precommitted, d.num_rest, u64p(it.r_W_rest.data()), ps.is_small ? 1 : 0, u64p(&it.comm_W[rows_pre].x)),
          "commit rest");
+  });
+  if (batch_rest && d.num_rest_unpadded == 0) {
+    // commit_zeros of every proof in ONE call: the same base h and the same words per scalar, count x rows_rest blinds
+    std::vector<fe_t> blinds(count * rows_rest);
+    std::vector<aff_t> rows(count * rows_rest);
+    for (size_t k = 0; k < count; ++k) std::copy(items[k].r_W_rest.begin(), items[k].r_W_rest.end(), blinds.begin() + k * rows_rest);
+    ck(sp_fixed_base_mul_h(ctx, pk.ck, u64p(blinds.data()), blinds.size(), u64p(&rows[0].x)), "prove_batch: commit_zeros");
+    for (size_t k = 0; k < count; ++k) std::copy(rows.begin() + k * rows_rest, rows.begin() + (k + 1) * rows_rest, items[k].comm_W.begin() + items[k].ps->comm_W_fixed.size());
+  } else if (batch_rest) {
+    std::vector<const sp_table*> Ws(count);
+    std::vector<const uint64_t*> bl(count);
+    std::vector<uint64_t*> outs(count);
+    for (size_t k = 0; k < count; ++k) {
+      Ws[k] = items[k].ps->W;
+      bl[k] = u64p(items[k].r_W_rest.data());
+      outs[k] = u64p(&items[k].comm_W[items[k].ps->comm_W_fixed.size()].x);
+    }
+    ck(sp_hyrax_commit_batch(ctx, pk.ck, count, Ws.data(), d.num_shared + d.num_precommitted, d.num_rest, bl.data(), outs.data()), "prove_batch: commit rest");
+  }
+  each([&](Item& it, size_t) {
+    SpartanPrepSNARK& ps = *it.ps;
+    const size_t rows_pre = ps.comm_W_fixed.size();
     std::vector<uint8_t> b = commitment_bytes(it.comm_W.data() + rows_pre, rows_rest);
     it.tr->absorb("comm_W_rest", b.data(), b.size());
     it.r_W = ps.r_W_fixed;
@@ -1565,9 +1609,19 @@ static void prove_batch_chunk(const SpartanProverKey& pk, SpartanPrepSNARK* cons
     SpartanPrepSNARK& ps = *it.ps;
     it.r = it.tr->squeeze("r");
     claims[k] = fe_add<S>(fe_add<S>(it.claims_outer[0], fe_mul<S>(it.r, it.claims_outer[1])), fe_mul<S>(fe_mul<S>(it.r, it.r), it.claims_outer[2]));
+    if (batch_abc) return;
     ck(sp_eq_table_into(ctx, u64p(&r_x[k * num_rounds_x]), num_rounds_x, ps.rx), "evals_rx");
     ck(sp_poly_abc(ctx, pk.S, ps.rx, u64p(&it.r), 2 * M, ps.abc), "poly_ABC");
   });
+  if (batch_abc) {  // one walk per chunk of proofs over their interleaved eq tables; ps.rx is not written on this path
+    std::vector<fe_t> rs(count);
+    std::vector<sp_table*> abcs(count);
+    for (size_t k = 0; k < count; ++k) {
+      rs[k] = items[k].r;
+      abcs[k] = items[k].ps->abc;
+    }
+    ck(sp_poly_abc_batch(ctx, pk.S, count, u64p(r_x.data()), num_rounds_x, u64p(rs.data()), 2 * M, abcs.data()), "prove_batch: poly_ABC");
+  }
   phase(3);
   // :323-404 inner sum-check (manual round 0 == a generic round on (lo_eff, hi_eff) = (M, num_extra) tables), all proofs in lockstep
   each([&](Item& it, size_t k) {

@@ -226,6 +226,17 @@ int sp_sumcheck_cubic3_lockstep(sp_ctx* ctx, size_t count, const uint64_t* claim
                                 sp_table* const* C, sp_transcript* const* tr, uint64_t* out_cpolys, uint64_t* out_r, uint64_t* out_final);
 int sp_sumcheck_quad_lockstep(sp_ctx* ctx, size_t count, const uint64_t* claims, size_t rounds, sp_table* const* A, sp_table* const* B, sp_transcript* const* tr,
                               uint64_t* out_cpolys, uint64_t* out_r, uint64_t* out_final);
+/* The same two calls for a caller that wants each round's challenges while the sum-check runs (prove_batch hands the inner sum-check's row challenges
+ * to sp_hyrax_prove_batch_rows): observe(user, round, r) is called on the calling thread once per round, round = 0 .. rounds - 1 in order, with the
+ * `count` challenges of that round (count x 4 words, instance-major: out_r's values), after all of them are drawn and after the next round's launch is
+ * queued - so what the hook costs runs beside the device and no launch waits for it. The hook must not touch the sum-check's tables or transcripts.
+ * A null hook makes these the plain calls; outputs and transcript states are identical either way. */
+typedef void (*sp_lockstep_hook)(void* user, size_t round, const uint64_t* r);
+int sp_sumcheck_cubic3_lockstep_observed(sp_ctx* ctx, size_t count, const uint64_t* claims, const uint64_t* taus, size_t ell, sp_table* const* A, sp_table* const* B,
+                                         sp_table* const* C, sp_transcript* const* tr, uint64_t* out_cpolys, uint64_t* out_r, uint64_t* out_final,
+                                         sp_lockstep_hook observe, void* user);
+int sp_sumcheck_quad_lockstep_observed(sp_ctx* ctx, size_t count, const uint64_t* claims, size_t rounds, sp_table* const* A, sp_table* const* B, sp_transcript* const* tr,
+                                       uint64_t* out_cpolys, uint64_t* out_r, uint64_t* out_final, sp_lockstep_hook observe, void* user);
 /* EqSumCheckInstance::evaluation_points_zero_check_round0 (src/sumcheck.rs:1163-1271; the round-0 shortcut of the *_zk cubic provers, :595): on a
  * zero-check (claim 0, A o B = C on the hypercube) t(0) vanishes, so only t_inf = sum E(x) (A1 - A0)(B1 - B0) is computed (C is not read) and the
  * evaluations (s(0), s(2), s(3)) of the round polynomial are derived from it (derive_from_claim :1276-1324, or the tau = 0 fallback :1244-1268).
@@ -450,6 +461,38 @@ int sp_hyrax_prove(sp_ctx* ctx, const sp_ck* ck, const sp_ck* ck_eval, sp_transc
 int sp_hyrax_prove_batch(sp_ctx* ctx, const sp_ck* ck, const sp_ck* ck_eval, size_t count, sp_transcript* const* tr, const uint64_t* const* comm_rows_aff, size_t rows,
                          const sp_table* const* poly, size_t n, const uint64_t* const* blinds, const uint64_t* points, size_t npt, const uint64_t* comm_eval_aff,
                          const uint64_t* blind_eval, const uint8_t* const* rng, const size_t* rng_blocks, uint64_t* out);
+/* sp_hyrax_prove_batch opened ahead of its point, in three calls, for a caller with sum-checks to hide it under (prove_batch). Each stage starts when
+ * its inputs exist, on the context's auxiliary stream and helper thread, and waits for nothing:
+ *   _begin   the commitments, blinds and randomness blocks are known (src/spartan.rs:238-245; the IPA's draws are independent of everything,
+ *            ipa.rs:139-149): uploads the blocks, writes the mask vectors d_k (ipa.rs:139-145), queues the walk of the `count` vectors
+ *            delta_k = <d_k, ck> + r_delta_k h (ipa.rs:146-147) and starts the commitments' transcript bytes and Keccak blocks (hyrax_pc.rs:410,
+ *            :714-729). It is given no transcript and touches none. Its refusals are sp_hyrax_prove_batch's for the arguments it has.
+ *   _rows    optional; the row half of every point is known (row_points: count x nvr elements, instance-major - r_y[1 ..= nvr] of the inner
+ *            sum-check): forms r_LZ_k = <L_k, blinds_k> on the host and queues LZ_k = L_k^T W_k and the walk of the `count` vectors comm_LZ_k
+ *            (hyrax_pc.rs:446-455) behind the delta walk. Only enqueues. A no-op when the polynomial has one row (hyrax_pc.rs:417-423).
+ *   _finish  takes every argument of sp_hyrax_prove_batch. It compares them with what the job holds - the keys and the count, per instance the table,
+ *            the commitment pointer and words, the blinds, the cols + 2 randomness blocks and, if _rows ran, the row half of the point - and on any
+ *            difference drops the job's results and computes as sp_hyrax_prove_batch does. On a match it collects: <R_k, d_k> and beta_k (ipa.rs:148-149),
+ *            the per-instance transcript steps (hyrax_pc.rs:410, ipa.rs:132-158; a sponge hashed ahead is used only for a transcript that has
+ *            absorbed nothing since its last squeeze) and z_vec_k (ipa.rs:160-168). Either way, for every k the output words, the cols + 2 blocks
+ *            consumed and the state of tr[k] afterwards are exactly those of sp_hyrax_prove_batch on the same arguments, whether or not _rows ran.
+ *            It consumes the job whatever it returns; a null job makes it sp_hyrax_prove_batch.
+ *   _drop    waits for what the job queued, wipes the mask material and frees the job (an error exit of the caller).
+ * One job per context: while it is open, a second _begin, sp_hyrax_prove_batch and sp_hyrax_commit_batch on the context are refused with
+ * SP_ERR_INVALID_INPUT_LENGTH before anything is touched (they share the job's workspaces and pinned buffer). _begin retracts a single-proof
+ * announcement as sp_hyrax_prove_batch does. The shapes sp_hyrax_prove_batch opens instance by instance (count 1, keys without window tables or of
+ * fewer than 1023 / more than 4095 columns, more than 2^10 rows) give a job that starts nothing; _finish runs that loop. Every staging copy of the
+ * mask vectors, the randomness blocks and the blinds - pinned, device and the job's own - is wiped by _finish and by _drop. */
+typedef struct sp_opening_job sp_opening_job;
+int sp_hyrax_prove_batch_begin(sp_ctx* ctx, const sp_ck* ck, const sp_ck* ck_eval, size_t count, const uint64_t* const* comm_rows_aff, size_t rows,
+                               const sp_table* const* poly, size_t n, const uint64_t* const* blinds, const uint8_t* const* rng, const size_t* rng_blocks,
+                               sp_opening_job** job);
+int sp_hyrax_prove_batch_rows(sp_ctx* ctx, sp_opening_job* job, const uint64_t* row_points);
+int sp_hyrax_prove_batch_finish(sp_ctx* ctx, sp_opening_job* job, const sp_ck* ck, const sp_ck* ck_eval, size_t count, sp_transcript* const* tr,
+                                const uint64_t* const* comm_rows_aff, size_t rows, const sp_table* const* poly, size_t n, const uint64_t* const* blinds,
+                                const uint64_t* points, size_t npt, const uint64_t* comm_eval_aff, const uint64_t* blind_eval, const uint8_t* const* rng,
+                                const size_t* rng_blocks, uint64_t* out);
+void sp_hyrax_prove_batch_drop(sp_ctx* ctx, sp_opening_job* job);
 /* PCS::prove announced ahead of its call. src/spartan.rs calls PCS::prove last (:425-435), but the commitment and its blinds exist when
  * r1cs_instance_and_witness returns (:238-245), the IPA's randomness is independent of everything (the reference draws it inside
  * InnerProductArgumentLinear::prove, ipa.rs:139-149) and the ROW half of the evaluation point exists once the inner sum-check has drawn it. A caller that

@@ -254,6 +254,7 @@ void sp_ctx_destroy(sp_ctx* c) {
   sp::g_live_contexts.fetch_sub(1, std::memory_order_relaxed);
   sp::pcs_ahead_free(c);
   hipSetDevice(c->device);
+  sp::opening_job_free(c);
   c->drain_stats();
   for (hipEvent_t e : c->event_pool) hipEventDestroy(e);
   if (c->d_scratch) hipFree(c->d_scratch);

@@ -935,6 +935,7 @@ int sp_hyrax_commit_batch(sp_ctx* c, const sp_ck* ck, size_t count, const sp_tab
   }
   const size_t cols = ck->num_cols, rows = (n + cols - 1) / cols;
   if (rows == 0) return SP_OK;
+  if (c->opening_job) return fail(SP_ERR_INVALID_INPUT_LENGTH, "sp_hyrax_commit_batch: a batch opened ahead holds the pinned buffer (sp_hyrax_prove_batch_finish or _drop first)");
   const size_t ws_elems = g_commit_batch_ws.load();
   // narrow keys (per-base tables, commit_rows' first branch) and a polynomial that alone exceeds a chunk's workspace: the single call per polynomial
   if (ck->d_cktables || rows * cols > ws_elems) {

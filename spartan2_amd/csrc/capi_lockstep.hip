@@ -3,7 +3,8 @@
 // (kernels_lockstep.hpp), one wait collects the `count` records, the host finishes `count` round polynomials (sumcheck_round.hpp: the algebra of the
 // host-table provers), feeds each to its own transcript and hands the `count` challenges to the next launch by value. A round trip per round, as for
 // a lone instance - shared by all of them. Every instance's polynomials, challenges, final claims and transcript are those of sp_sumcheck_cubic3 /
-// sp_sumcheck_quad on that instance alone. gfx950 only; no CPU fallback.
+// sp_sumcheck_quad on that instance alone. The _observed forms report each round's challenges to a hook of the caller once the next launch is queued.
+// gfx950 only; no CPU fallback.
 #include <cstring>
 #include <string>
 #include <vector>
@@ -69,12 +70,17 @@ int wait_records(sp_ctx* c, size_t count, unsigned seq, int nvals, fe_t* v) {
   return SP_OK;
 }
 unsigned blocks_per_instance(size_t q) { return (unsigned)((q + spk::LS_CHUNK - 1) / spk::LS_CHUNK); }
+// the caller's hook (sp_*_lockstep_observed): the challenges of `round`, reported once the launch that consumes them is queued
+void report(sp_lockstep_hook observe, void* user, size_t round, const spk::LsChallenges& ch) {
+  if (observe) observe(user, round, reinterpret_cast<const uint64_t*>(ch.r));
+}
 }  // namespace
 
 extern "C" {
 
-int sp_sumcheck_cubic3_lockstep(sp_ctx* c, size_t count, const uint64_t* claims, const uint64_t* taus_, size_t ell, sp_table* const* A, sp_table* const* B,
-                                sp_table* const* C, sp_transcript* const* tr, uint64_t* out_cpolys, uint64_t* out_r, uint64_t* out_final) {
+int sp_sumcheck_cubic3_lockstep_observed(sp_ctx* c, size_t count, const uint64_t* claims, const uint64_t* taus_, size_t ell, sp_table* const* A, sp_table* const* B,
+                                         sp_table* const* C, sp_transcript* const* tr, uint64_t* out_cpolys, uint64_t* out_r, uint64_t* out_final, sp_lockstep_hook observe,
+                                         void* user) {
   static const char* who = "prove_cubic_with_three_inputs (lockstep)";
   if (!c || !claims || !taus_ || !out_cpolys || !out_r || !out_final) return fail(SP_ERR_INVALID_INPUT_LENGTH, std::string(who) + ": null argument");
   sp_table* const* tabs[3] = {A, B, C};
@@ -141,6 +147,7 @@ int sp_sumcheck_cubic3_lockstep(sp_ctx* c, size_t count, const uint64_t* claims,
         for (sp_table* t : {A[k], B[k], C[k]}) sp::after_bind(t);
     }
     if (nb > 1) c->timed_kernel("ls_sum_partials", 96ull * nb * count, spk::k_ls_sum_partials<3>, dim3((unsigned)count), dim3(64), (const fe_t*)d_part, nb, c->d_pinned, o.seq);
+    if (rnd > 1) report(observe, user, rnd - 2, ch);
     if ((rc = wait_records(c, count, o.seq, 3, rec.data()))) return rc;
     for (size_t k = 0; k < count; ++k) {
       const fe_t tau = taus[k * ell + rnd - 1];
@@ -162,14 +169,20 @@ int sp_sumcheck_cubic3_lockstep(sp_ctx* c, size_t count, const uint64_t* claims,
   hipLaunchKernelGGL((spk::k_ls_bind_last<3>), dim3((unsigned)count), dim3(64), 0, c->stream, tb, ch, (const spk::LsEff*)nullptr, c->d_pinned, seq);
   for (size_t k = 0; k < count; ++k)
     for (sp_table* t : {A[k], B[k], C[k]}) sp::after_bind(t);
+  report(observe, user, ell - 1, ch);
   if ((rc = wait_records(c, count, seq, 3, rec.data()))) return rc;
   for (size_t k = 0; k < count; ++k)
     for (int j = 0; j < 3; ++j) store_fe(out_final + 12 * k + 4 * j, rec[3 * k + j]);
   return SP_OK;
 }
 
-int sp_sumcheck_quad_lockstep(sp_ctx* c, size_t count, const uint64_t* claims, size_t rounds, sp_table* const* A, sp_table* const* B, sp_transcript* const* tr,
-                              uint64_t* out_cpolys, uint64_t* out_r, uint64_t* out_final) {
+int sp_sumcheck_cubic3_lockstep(sp_ctx* c, size_t count, const uint64_t* claims, const uint64_t* taus, size_t ell, sp_table* const* A, sp_table* const* B,
+                                sp_table* const* C, sp_transcript* const* tr, uint64_t* out_cpolys, uint64_t* out_r, uint64_t* out_final) {
+  return sp_sumcheck_cubic3_lockstep_observed(c, count, claims, taus, ell, A, B, C, tr, out_cpolys, out_r, out_final, nullptr, nullptr);
+}
+
+int sp_sumcheck_quad_lockstep_observed(sp_ctx* c, size_t count, const uint64_t* claims, size_t rounds, sp_table* const* A, sp_table* const* B, sp_transcript* const* tr,
+                                       uint64_t* out_cpolys, uint64_t* out_r, uint64_t* out_final, sp_lockstep_hook observe, void* user) {
   static const char* who = "prove_quad (lockstep)";
   if (!c || !claims || !out_cpolys || !out_r || !out_final) return fail(SP_ERR_INVALID_INPUT_LENGTH, std::string(who) + ": null argument");
   sp_table* const* tabs[2] = {A, B};
@@ -223,6 +236,7 @@ int sp_sumcheck_quad_lockstep(sp_ctx* c, size_t count, const uint64_t* claims, s
       }
     }
     if (nb > 1) c->timed_kernel("ls_sum_partials", 64ull * nb * count, spk::k_ls_sum_partials<2>, dim3((unsigned)count), dim3(64), (const fe_t*)d_part, nb, c->d_pinned, o.seq);
+    if (round > 0) report(observe, user, round - 1, ch);
     if ((rc = wait_records(c, count, o.seq, 2, rec.data()))) return rc;
     for (size_t k = 0; k < count; ++k) {
       const sp::UniPoly poly = sp::quad_round_poly(claim[k], &rec[3 * k]);
@@ -243,10 +257,16 @@ int sp_sumcheck_quad_lockstep(sp_ctx* c, size_t count, const uint64_t* claims, s
     sp::after_bind(A[k]);
     sp::after_bind(B[k]);
   }
+  report(observe, user, rounds - 1, ch);
   if ((rc = wait_records(c, count, seq, 2, rec.data()))) return rc;
   for (size_t k = 0; k < count; ++k)
     for (int j = 0; j < 2; ++j) store_fe(out_final + 8 * k + 4 * j, rec[3 * k + j]);
   return SP_OK;
+}
+
+int sp_sumcheck_quad_lockstep(sp_ctx* c, size_t count, const uint64_t* claims, size_t rounds, sp_table* const* A, sp_table* const* B, sp_transcript* const* tr,
+                              uint64_t* out_cpolys, uint64_t* out_r, uint64_t* out_final) {
+  return sp_sumcheck_quad_lockstep_observed(c, count, claims, rounds, A, B, tr, out_cpolys, out_r, out_final, nullptr, nullptr);
 }
 
 }  // extern "C"

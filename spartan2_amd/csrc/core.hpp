@@ -44,6 +44,7 @@ void slow_note(const char* site, long spins);
 void pcs_ahead_on_challenge(void* ctx, size_t round, const uint64_t r[4]);
 void pcs_ahead_free(sp_ctx* c);
 bool pcs_ahead_wants(const sp_ctx* c, size_t rounds);  // is an opening announced whose point a sum-check of this many rounds draws?
+void opening_job_free(sp_ctx* c);  // capi_opening_batch.hip: waits for what a batch opened ahead has queued, wipes its mask material, frees it
 
 #define SP_HIP(expr)                                                                               \
   do {                                                                                             \
@@ -238,6 +239,8 @@ struct sp_ctx {
   void* h_opening = nullptr;
   size_t h_opening_bytes = 0;
   hipEvent_t opening_ev = nullptr;
+  // a batch opened ahead (sp_hyrax_prove_batch_begin): at most one per context; it owns the WS_OPENING_* workspaces and h_opening until it is finished or dropped
+  struct sp_opening_job* opening_job = nullptr;
   // an opening announced ahead of PCS::prove (sp_hyrax_prove_announce, capi_group.hip): the inner sum-check's round loop reports its challenges to it
   struct sp_pcs_ahead* pcs_ahead = nullptr;
   void* h_pinned_lane[2] = {nullptr, nullptr};  // pinned landing buffers for per-window MSM sums (one per stream), 8 KiB each

@@ -5,6 +5,8 @@
 //   k_ob_walk     the table walk over one key's window tables for 2 count scalar vectors: delta_k = <d_k, ck> + r_delta_k h (ipa.rs:147), reduced
 //                 from the uniform blocks as k_multi_mul_wide's raw64 form does, and comm_LZ_k = <LZ_k, ck> + r_LZ_k h (hyrax_pc.rs:454-455)
 //   k_ob_z        z_vec_k = r_k LZ_k + d_k (ipa.rs:160-163)
+// k_ob_walk takes a vector base, so that one launch covers the delta vectors alone (base 0) or the comm_LZ vectors alone (base count): a batch opened
+// ahead (sp_hyrax_prove_batch_begin / _rows / _finish) walks them at different times. Its two halves of k_ob_mask are in kernels_opening_ahead.hpp.
 // The walk is k_multi_mul_wide (kernels_msm.hpp) with the per-block item layout, CoopAdd / xyzz_add_block4 and the last-block join unchanged; what is
 // new is the indexing: vector v = blockIdx.y has its own scalars, block-sum area, ticket and result, and the result is a plain store into device
 // memory that the host fetches with one copy for all vectors. Results are group elements compared as canonical affine points and exact field
@@ -106,16 +108,17 @@ __global__ void __launch_bounds__(OB_RMV_THREADS) k_ob_rowmat(const ObInst* __re
   }
 }
 
-// grid (ceil(32 n / 1024) <= 128, vectors), 512 threads. Vector v < count: delta of instance v - scalar idx < nraw is from_uniform(block idx); vector
+// grid (ceil(32 n / 1024) <= 128, vectors), 512 threads, vector v = vbase + blockIdx.y (vbase = 0 and 2 count vectors: all of them; count vectors from
+// base 0 / from base count: the delta / the comm_LZ vectors alone). Vector v < count: delta of instance v - scalar idx < nraw is from_uniform(block idx); vector
 // v >= count: comm_LZ of instance v - count - scalar idx < nraw is lz[idx]. Scalars nraw .. n - 2 are zero (a polynomial narrower than the key) and
 // scalar n - 1, h's, is the instance's blind. partial: OB_WALK_MAX_BLOCKS block sums a vector; ticket: one counter a vector, zero at entry and at
 // exit; out[v]: the Jacobian sum.
-__global__ void __launch_bounds__(4 * 128) k_ob_walk(const ObInst* __restrict__ inst, unsigned count, size_t n, size_t nraw, const aff_t* __restrict__ tables,
+__global__ void __launch_bounds__(4 * 128) k_ob_walk(const ObInst* __restrict__ inst, unsigned count, unsigned vbase, size_t n, size_t nraw, const aff_t* __restrict__ tables,
                                                      xyzz_t* __restrict__ partial, unsigned* __restrict__ ticket, jac_t* __restrict__ out) {
   __shared__ CoopAdd<128> L;
   __shared__ xyzz_t s[256];
   __shared__ unsigned s_last;
-  const unsigned v = blockIdx.y;
+  const unsigned v = vbase + blockIdx.y;
   const bool raw64 = v < count;
   const ObInst& I = inst[raw64 ? v : v - count];
   partial += (size_t)v * OB_WALK_MAX_BLOCKS;

@@ -375,6 +375,7 @@ def sumcheck_quad(ctx, claim, rounds, A: Table, B: Table, tr: Transcript):
 
 
 LOCKSTEP_MAX = 64  # SP_LOCKSTEP_MAX
+LOCKSTEP_HOOK = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint64))  # sp_lockstep_hook(user, round, r)
 
 
 def _lockstep_lib():
@@ -384,6 +385,10 @@ def _lockstep_lib():
     L.sp_sumcheck_cubic3_lockstep.restype = ctypes.c_int
     L.sp_sumcheck_quad_lockstep.argtypes = [ctypes.c_void_p, sz, c_u64p, sz, vpp, vpp, vpp, c_u64p, c_u64p, c_u64p]
     L.sp_sumcheck_quad_lockstep.restype = ctypes.c_int
+    L.sp_sumcheck_cubic3_lockstep_observed.argtypes = L.sp_sumcheck_cubic3_lockstep.argtypes + [LOCKSTEP_HOOK, ctypes.c_void_p]
+    L.sp_sumcheck_cubic3_lockstep_observed.restype = ctypes.c_int
+    L.sp_sumcheck_quad_lockstep_observed.argtypes = L.sp_sumcheck_quad_lockstep.argtypes + [LOCKSTEP_HOOK, ctypes.c_void_p]
+    L.sp_sumcheck_quad_lockstep_observed.restype = ctypes.c_int
     return L
 
 
@@ -393,10 +398,54 @@ def _opening_batch_lib():
     L.sp_hyrax_prove_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, sz, vpp, vpp, sz, vpp, sz, vpp, c_u64p, sz, c_u64p, c_u64p, vpp,
                                        ctypes.POINTER(sz), c_u64p]
     L.sp_hyrax_prove_batch.restype = ctypes.c_int
+    L.sp_hyrax_prove_batch_begin.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, sz, vpp, sz, vpp, sz, vpp, vpp, ctypes.POINTER(sz), vpp]
+    L.sp_hyrax_prove_batch_begin.restype = ctypes.c_int
+    L.sp_hyrax_prove_batch_rows.argtypes = [ctypes.c_void_p, ctypes.c_void_p, c_u64p]
+    L.sp_hyrax_prove_batch_rows.restype = ctypes.c_int
+    L.sp_hyrax_prove_batch_finish.argtypes = [ctypes.c_void_p, ctypes.c_void_p] + L.sp_hyrax_prove_batch.argtypes[1:]
+    L.sp_hyrax_prove_batch_finish.restype = ctypes.c_int
+    L.sp_hyrax_prove_batch_drop.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    L.sp_hyrax_prove_batch_drop.restype = None
     return L
 
 
-def hyrax_prove_batch(ctx, key, key_eval, trs, comm_rows, polys, n, blinds, points, comm_evals, blind_evals, rngs):
+class OpeningJob:
+    """A batch opened ahead (sp_hyrax_prove_batch_begin): per instance k comm_rows[k] (rows, 8), polys[k], blinds[k] (rows, 4), rngs[k] (>= cols + 2, 64)
+    uniform bytes - the arguments of hyrax_prove_batch that exist before the point does. rows(row_points) hands over the row half of every point
+    (K, nvr, 4) once it is known (optional); finish(...) takes every argument of hyrax_prove_batch and returns its words; drop() withdraws the job.
+    The arrays given here are kept alive by the object: the library holds their addresses until finish or drop. None entries stay NULL (refusal tests)."""
+
+    def __init__(self, ctx, key, key_eval, comm_rows, polys, n, blinds, rngs):
+        c64 = lambda a, shape: np.ascontiguousarray(a, dtype=np.uint64).reshape(shape)
+        K = len(polys)
+        self.ctx = ctx
+        self.comm_rows = [None if a is None else c64(a, (-1, 8)) for a in comm_rows]
+        self.blinds = [None if a is None else c64(a, (-1, 4)) for a in blinds]
+        self.rngs = [None if a is None else np.ascontiguousarray(a, dtype=np.uint8).reshape(-1, 64) for a in rngs]
+        self.polys = list(polys)
+        rows = next((a.shape[0] for a in self.comm_rows if a is not None), 1)
+        arr = lambda xs: (ctypes.c_void_p * max(len(xs), 1))(*[None if a is None else a.ctypes.data for a in xs])
+        nblk = (ctypes.c_size_t * max(len(self.rngs), 1))(*[0 if a is None else a.shape[0] for a in self.rngs])
+        h = ctypes.c_void_p()
+        check(_opening_batch_lib().sp_hyrax_prove_batch_begin(ctx.h, None if key is None else key.h, None if key_eval is None else key_eval.h, K, arr(self.comm_rows), rows,
+                                                              _handles(self.polys), n, arr(self.blinds), arr(self.rngs), nblk, ctypes.byref(h)))
+        self.h = h
+
+    def rows(self, row_points):
+        pts = np.ascontiguousarray(row_points, dtype=np.uint64)
+        check(_opening_batch_lib().sp_hyrax_prove_batch_rows(self.ctx.h, self.h, p64(pts) if pts.size else None))
+
+    def finish(self, key, key_eval, trs, comm_rows, polys, n, blinds, points, comm_evals, blind_evals, rngs):
+        h, self.h = self.h, None  # consumed whatever it returns
+        return hyrax_prove_batch(self.ctx, key, key_eval, trs, comm_rows, polys, n, blinds, points, comm_evals, blind_evals, rngs, _job=h)
+
+    def drop(self):
+        if self.h is not None:
+            _opening_batch_lib().sp_hyrax_prove_batch_drop(self.ctx.h, self.h)
+            self.h = None
+
+
+def hyrax_prove_batch(ctx, key, key_eval, trs, comm_rows, polys, n, blinds, points, comm_evals, blind_evals, rngs, _job=None):
     """sp_hyrax_prove_batch: len(trs) instances of CommitmentKey.prove on one key pair and one n, opened in one pass. Per instance k: trs[k], comm_rows[k]
     (rows, 8), polys[k], blinds[k] (rows, 4), points[k] (npt, 4), comm_evals[k] (8,), blind_evals[k] (4,), rngs[k] (>= cols + 2, 64) uniform bytes.
     Returns (K, 16 + 4 cols + 8) words, row k in CommitmentKey.prove's layout. None entries of the per-instance lists, and None for comm_evals /
@@ -413,10 +462,12 @@ def hyrax_prove_batch(ctx, key, key_eval, trs, comm_rows, polys, n, blinds, poin
     out = np.zeros((max(K, 1), 16 + 4 * cols + 8), dtype=np.uint64)
     arr = lambda xs: (ctypes.c_void_p * max(len(xs), 1))(*[None if a is None else a.ctypes.data for a in xs])
     nblk = (ctypes.c_size_t * max(len(rngs), 1))(*[0 if a is None else a.shape[0] for a in rngs])
-    check(_opening_batch_lib().sp_hyrax_prove_batch(ctx.h, key.h, key_eval.h, K, _handles(trs), arr(comm_rows), rows, _handles(polys), n, arr(blinds),
-                                                    p64(points) if points.size else None, npt, None if comm_evals is None else p64(c64(comm_evals, (-1, 8))),
-                                                    None if blind_evals is None else p64(c64(blind_evals, (-1, 4))),
-                                                    arr(rngs), nblk, p64(out)))
+    L = _opening_batch_lib()
+    call = L.sp_hyrax_prove_batch if _job is None else (lambda ctx_h, *a: L.sp_hyrax_prove_batch_finish(ctx_h, _job, *a))
+    check(call(ctx.h, key.h, key_eval.h, K, _handles(trs), arr(comm_rows), rows, _handles(polys), n, arr(blinds),
+               p64(points) if points.size else None, npt, None if comm_evals is None else p64(c64(comm_evals, (-1, 8))),
+               None if blind_evals is None else p64(c64(blind_evals, (-1, 4))),
+               arr(rngs), nblk, p64(out)))
     return out
 
 
@@ -425,9 +476,25 @@ def _handles(objs):
     return (ctypes.c_void_p * max(len(objs), 1))(*[None if o is None else o.h for o in objs])
 
 
-def sumcheck_cubic3_lockstep(ctx, claims, taus, As, Bs, Cs, trs):
+def _hook(observe, K):
+    """sp_lockstep_hook around observe(round, r) with r a (K, 4) copy of the round's challenges; an exception raised by it is re-raised after the call"""
+    if observe is None:
+        return LOCKSTEP_HOOK(), []
+    raised = []
+
+    def tramp(_user, rnd, r):
+        try:
+            observe(int(rnd), np.ctypeslib.as_array(r, shape=(K, 4)).copy())
+        except BaseException as e:  # (must not unwind through the C frames)
+            raised.append(e)
+
+    return LOCKSTEP_HOOK(tramp), raised
+
+
+def sumcheck_cubic3_lockstep(ctx, claims, taus, As, Bs, Cs, trs, observe=None, observed=False):
     """sp_sumcheck_cubic3_lockstep: len(trs) instances of sumcheck_cubic3 over tables of one length, one launch per round for all of them.
-    claims (K, 4), taus (K, ell, 4) -> polys (K, ell, 3, 4), r (K, ell, 4), final claims (K, 3, 4)."""
+    claims (K, 4), taus (K, ell, 4) -> polys (K, ell, 3, 4), r (K, ell, 4), final claims (K, 3, 4). observe(round, r (K, 4)) or observed=True:
+    sp_sumcheck_cubic3_lockstep_observed (observed=True with no observe passes a null hook)."""
     K = len(trs)
     taus = np.ascontiguousarray(taus, dtype=np.uint64).reshape(max(K, 1), -1, 4)
     ell = taus.shape[1]
@@ -435,19 +502,35 @@ def sumcheck_cubic3_lockstep(ctx, claims, taus, As, Bs, Cs, trs):
     polys = np.zeros((max(K, 1), ell, 3, 4), dtype=np.uint64)
     r = np.zeros((max(K, 1), ell, 4), dtype=np.uint64)
     fin = np.zeros((max(K, 1), 3, 4), dtype=np.uint64)
-    check(_lockstep_lib().sp_sumcheck_cubic3_lockstep(ctx.h, K, p64(claims), p64(taus), ell, _handles(As), _handles(Bs), _handles(Cs), _handles(trs), p64(polys), p64(r),
-                                                      p64(fin)))
+    if observe is None and not observed:
+        check(_lockstep_lib().sp_sumcheck_cubic3_lockstep(ctx.h, K, p64(claims), p64(taus), ell, _handles(As), _handles(Bs), _handles(Cs), _handles(trs), p64(polys), p64(r),
+                                                          p64(fin)))
+        return polys, r, fin
+    hook, raised = _hook(observe, K)
+    rc = _lockstep_lib().sp_sumcheck_cubic3_lockstep_observed(ctx.h, K, p64(claims), p64(taus), ell, _handles(As), _handles(Bs), _handles(Cs), _handles(trs), p64(polys),
+                                                              p64(r), p64(fin), hook, None)
+    if raised:
+        raise raised[0]
+    check(rc)
     return polys, r, fin
 
 
-def sumcheck_quad_lockstep(ctx, claims, rounds, As, Bs, trs):
-    """sp_sumcheck_quad_lockstep: len(trs) instances of sumcheck_quad -> polys (K, rounds, 2, 4), r (K, rounds, 4), final claims (K, 2, 4)."""
+def sumcheck_quad_lockstep(ctx, claims, rounds, As, Bs, trs, observe=None, observed=False):
+    """sp_sumcheck_quad_lockstep: len(trs) instances of sumcheck_quad -> polys (K, rounds, 2, 4), r (K, rounds, 4), final claims (K, 2, 4).
+    observe / observed: sp_sumcheck_quad_lockstep_observed, as for sumcheck_cubic3_lockstep."""
     K = len(trs)
     claims = np.ascontiguousarray(claims, dtype=np.uint64).reshape(-1, 4)
     polys = np.zeros((max(K, 1), rounds, 2, 4), dtype=np.uint64)
     r = np.zeros((max(K, 1), rounds, 4), dtype=np.uint64)
     fin = np.zeros((max(K, 1), 2, 4), dtype=np.uint64)
-    check(_lockstep_lib().sp_sumcheck_quad_lockstep(ctx.h, K, p64(claims), rounds, _handles(As), _handles(Bs), _handles(trs), p64(polys), p64(r), p64(fin)))
+    if observe is None and not observed:
+        check(_lockstep_lib().sp_sumcheck_quad_lockstep(ctx.h, K, p64(claims), rounds, _handles(As), _handles(Bs), _handles(trs), p64(polys), p64(r), p64(fin)))
+        return polys, r, fin
+    hook, raised = _hook(observe, K)
+    rc = _lockstep_lib().sp_sumcheck_quad_lockstep_observed(ctx.h, K, p64(claims), rounds, _handles(As), _handles(Bs), _handles(trs), p64(polys), p64(r), p64(fin), hook, None)
+    if raised:
+        raise raised[0]
+    check(rc)
     return polys, r, fin
 
 

@@ -97,6 +97,8 @@ SS_BATCH_PER_PROOF_POLYABC = 2  # ... one sp_eq_table_into + sp_poly_abc per pro
 SS_BATCH_BATCHED_POLYABC = 4  # ... evals_rx + poly_ABC of all proofs through sp_poly_abc_batch
 SS_BATCH_PER_PROOF_REST_COMMIT = 8  # ... one rest commitment call per proof
 SS_BATCH_BATCHED_REST_COMMIT = 16  # ... the rest commitments of all proofs in one call
+SS_BATCH_OPENING_AHEAD = 32  # ... the openings begun ahead of the sum-checks (sp_hyrax_prove_batch_begin / _rows / _finish)
+SS_BATCH_OPENING_BEHIND = 64  # ... the openings as one sp_hyrax_prove_batch call behind the inner sum-check
 SS_PREP_PER_STATE_COMMIT = 1  # ss_prep_prove_batch_opts / ss_prep_prove_sha256_batch_opts flags: one sp_hyrax_commit per state ...
 SS_PREP_PER_STATE_MATVEC = 2  # ... one sp_multiply_vec per state (what the driver takes unless asked otherwise: measured, profiles/prep_prove_batch.md)
 SS_PREP_CHUNKED_MATVEC = 4  # ... the cached products through sp_multiply_vec_chunked
@@ -257,11 +259,13 @@ class SpartanSNARK:
             used_all.append(used.value)
         return used_all
 
-    def prove_batch(self, tapes, states=None, per_proof_opening=False, per_proof_polyabc=None, per_proof_rest_commit=None):
+    def prove_batch(self, tapes, states=None, per_proof_opening=False, per_proof_polyabc=None, per_proof_rest_commit=None, opening_ahead=None):
         """ss_prove_batch_opts over self.batch (or `states`, a list of (prep state, publics) pairs): one tape per proof -> ([(proof words, blocks used)],
         {phase: ms of the whole batch}). Proof k is word for word what prove() returns on state k with tape k; the outer and the inner sum-check of all
         proofs run in lockstep (sp_sumcheck_cubic3_lockstep / sp_sumcheck_quad_lockstep) and the openings are one sp_hyrax_prove_batch call -
-        per_proof_opening=True (SS_BATCH_PER_PROOF_OPENING) keeps them as one sp_hyrax_prove per proof. per_proof_polyabc: True = one sp_eq_table_into +
+        per_proof_opening=True (SS_BATCH_PER_PROOF_OPENING) keeps them as one sp_hyrax_prove per proof. opening_ahead: True = that opening begun ahead
+        (sp_hyrax_prove_batch_begin once comm_W is complete, _rows from the inner sum-check's hook, _finish in its place: SS_BATCH_OPENING_AHEAD), False =
+        the one call behind the inner sum-check (SS_BATCH_OPENING_BEHIND), None = what the driver measured to be faster; per_proof_opening wins. per_proof_polyabc: True = one sp_eq_table_into +
         sp_poly_abc per proof, False = one sp_poly_abc_batch call, None = what the driver measured to be faster; per_proof_rest_commit likewise for the
         rest commitments (one call per proof / one sp_fixed_base_mul_h or sp_hyrax_commit_batch call for all). Still per proof: the z assembly,
         sp_multiply_vec_incremental, the eval_W commitment and the lz_tables build."""
@@ -270,6 +274,8 @@ class SpartanSNARK:
             flags |= SS_BATCH_PER_PROOF_POLYABC if per_proof_polyabc else SS_BATCH_BATCHED_POLYABC
         if per_proof_rest_commit is not None:
             flags |= SS_BATCH_PER_PROOF_REST_COMMIT if per_proof_rest_commit else SS_BATCH_BATCHED_REST_COMMIT
+        if opening_ahead is not None:
+            flags |= SS_BATCH_OPENING_AHEAD if opening_ahead else SS_BATCH_OPENING_BEHIND
         states = self.batch if states is None else states
         K = len(states)
         if len(tapes) != K:

@@ -1438,8 +1438,12 @@ ProofBuf prove_reference_order(const SpartanProverKey& pk, SpartanPrepSNARK& ps,
 // prove_reference_order restated over `count` prepared states of ONE key, on one thread, phase by phase: every statement of src/spartan.rs:226-466 is
 // run for proof 0 .. count - 1 before the next statement is begun, and the outer and the inner sum-check run as ONE lockstep sum-check each
 // (sp_sumcheck_cubic3_lockstep / sp_sumcheck_quad_lockstep: a launch per round for all proofs, one wait, `count` transcripts fed on this thread).
-// The openings are ONE sp_hyrax_prove_batch call (every device stage a launch for all proofs; never announced ahead: the announcement is one slot per
-// context); flags & SS_BATCH_PER_PROOF_OPENING keeps them as `count` sp_hyrax_prove calls, one after the other. evals_rx + poly_ABC and the rest
+// The openings are ONE sp_hyrax_prove_batch call (every device stage a launch for all proofs) behind the inner sum-check, or - SS_BATCH_OPENING_AHEAD -
+// the same opening begun ahead: sp_hyrax_prove_batch_begin once the rest commitments are in comm_W (the mask vectors, the delta walks and the
+// commitments' hashing run under the sum-checks), sp_hyrax_prove_batch_rows from the inner sum-check's hook at the round that completes
+// r_y[1 ..= nvr] (L^T W and the comm_LZ walks run under its remaining rounds), sp_hyrax_prove_batch_finish where the batched call stood;
+// SS_BATCH_OPENING_BEHIND keeps the one call. flags & SS_BATCH_PER_PROOF_OPENING keeps them as `count` sp_hyrax_prove calls, one after the other, and
+// wins over both. evals_rx + poly_ABC and the rest
 // commitments have a batched form as well (flags and defaults below). Still the per-proof calls prove_reference_order makes: the z assembly,
 // sp_multiply_vec_incremental, the eval_W commitment and the lz_tables build. Proof k is word for word what
 // prove(pk, *ps[k], publics[k], tapes[k]) returns and consumes the same tape blocks; every state can be proved again afterwards, alone or in a batch.
@@ -1453,16 +1457,41 @@ ProofBuf prove_reference_order(const SpartanProverKey& pk, SpartanPrepSNARK& ps,
 // batched lies below the MINIMUM of the same batch with that one form per proof.
 //   poly_ABC: 3.83 ms against a minimum of 3.94 at K = 4, 10.75 against 11.03 at K = 16 (the launches: 76 us a proof against 82): BATCH_POLYABC_MIN = 4.
 //   rest commitment (commit_zeros at config 2): 3.83 against 3.88 at K = 4, 10.75 against 11.20 at K = 16: BATCH_REST_COMMIT_MIN = 4.
-//   K = 2 and 3 were not measured and keep the per-proof calls.
+//   the opening begun ahead, by the same rule against the same batch with SS_BATCH_OPENING_BEHIND: 3.61 ms against a minimum of 3.77 at K = 4, 9.91
+//   against 10.42 at K = 16 (pcs_prove 0.61 -> 0.18 and 1.70 -> 0.45 ms; the delta walks show up in matrix_vector_multiply, +0.09 / +0.34 ms, and the
+//   row stage in inner_sumcheck, +0.11 / +0.07): BATCH_OPENING_AHEAD_MIN = 4. One placement was measured: _begin once comm_W is complete, _rows at the
+//   inner round that completes the row point.
+//   K = 2 and 3 were not measured and keep the per-proof calls and the opening behind.
 enum : unsigned {
   SS_BATCH_PER_PROOF_OPENING = 1,
   SS_BATCH_PER_PROOF_POLYABC = 2,
   SS_BATCH_BATCHED_POLYABC = 4,
   SS_BATCH_PER_PROOF_REST_COMMIT = 8,
-  SS_BATCH_BATCHED_REST_COMMIT = 16
+  SS_BATCH_BATCHED_REST_COMMIT = 16,
+  SS_BATCH_OPENING_AHEAD = 32,
+  SS_BATCH_OPENING_BEHIND = 64
 };
 static constexpr size_t BATCH_POLYABC_MIN = 4;
 static constexpr size_t BATCH_REST_COMMIT_MIN = 4;
+static constexpr size_t BATCH_OPENING_AHEAD_MIN = 4;
+// a batch opened ahead never outlives its chunk: dropped on every exit that has not handed it to sp_hyrax_prove_batch_finish
+struct OpeningAhead {
+  sp_ctx* ctx;
+  sp_opening_job* job = nullptr;
+  size_t count = 0, nvr = 0;
+  std::vector<fe_t> row_pts;  // count x nvr, filled by the inner sum-check's hook
+  int rc = SP_OK;
+  ~OpeningAhead() {
+    if (job) sp_hyrax_prove_batch_drop(ctx, job);
+  }
+  // sp_lockstep_hook of the inner sum-check: r_y[0] separates W from (1, X); rounds 1 .. nvr draw the opening's row variables
+  static void on_inner_round(void* user, size_t round, const uint64_t* r) {
+    OpeningAhead& a = *static_cast<OpeningAhead*>(user);
+    if (!a.job || a.rc || round == 0 || round > a.nvr) return;
+    for (size_t k = 0; k < a.count; ++k) memcpy(&a.row_pts[k * a.nvr + round - 1], r + 4 * k, sizeof(fe_t));
+    if (round == a.nvr) a.rc = sp_hyrax_prove_batch_rows(a.ctx, a.job, u64p(a.row_pts.data()));
+  }
+};
 static void prove_batch_chunk(const SpartanProverKey& pk, SpartanPrepSNARK* const* pss, size_t count, const uint64_t* publics_u64, size_t npub, Tape* tapes,
                               ProofBuf* out, size_t first, double* ms, unsigned flags) {
   const sp_dims& d = pk.dims;
@@ -1499,6 +1528,8 @@ static void prove_batch_chunk(const SpartanProverKey& pk, SpartanPrepSNARK* cons
   const size_t rows_rest = (d.num_rest + W_ - 1) / W_;
   const bool batch_abc = !(flags & SS_BATCH_PER_PROOF_POLYABC) && ((flags & SS_BATCH_BATCHED_POLYABC) || count >= BATCH_POLYABC_MIN);
   const bool batch_rest = rows_rest && !(flags & SS_BATCH_PER_PROOF_REST_COMMIT) && ((flags & SS_BATCH_BATCHED_REST_COMMIT) || count >= BATCH_REST_COMMIT_MIN);
+  const bool opening_ahead =
+      !(flags & (SS_BATCH_PER_PROOF_OPENING | SS_BATCH_OPENING_BEHIND)) && ((flags & SS_BATCH_OPENING_AHEAD) || count >= BATCH_OPENING_AHEAD_MIN);
   // :226-236 transcript, vk, public values; r1cs_instance_and_witness (src/bellpepper/r1cs.rs:411-540)
   each([&](Item& it, size_t k) {
     it.ps = pss[k];
@@ -1555,6 +1586,31 @@ static void prove_batch_chunk(const SpartanProverKey& pk, SpartanPrepSNARK* cons
     it.r_W = ps.r_W_fixed;
     it.r_W.insert(it.r_W.end(), it.r_W_rest.begin(), it.r_W_rest.end());
   });
+  // The opening, begun ahead: comm_W and its blinds are complete, and the IPA's randomness is the tape's blocks behind blind_eval_W's (the one draw
+  // between here and PCS::prove), as prove's announcement takes them. The pointers are checked against the tape's position when the opening comes.
+  const size_t num_rows = (M + W_ - 1) / W_, cols = M / num_rows, rows_W = items[0].comm_W.size();
+  std::vector<const uint64_t*> comms(count), blinds(count);
+  std::vector<const sp_table*> polys(count);
+  std::vector<const uint8_t*> rngs_ahead(count);
+  std::vector<size_t> rng_blocks_ahead(count);
+  bool ahead_fits = true;
+  for (size_t k = 0; k < count; ++k) {
+    Item& it = items[k];
+    comms[k] = u64p(&it.comm_W[0].x);
+    blinds[k] = u64p(it.r_W.data());
+    polys[k] = it.ps->W;
+    ahead_fits = ahead_fits && it.tape->pos + 1 + cols + 2 <= it.tape->blocks;  // (an exhausted tape is reported where prove reports it)
+    rngs_ahead[k] = it.tape->bytes + 64 * (it.tape->pos + 1);
+    rng_blocks_ahead[k] = ahead_fits ? it.tape->blocks - it.tape->pos - 1 : 0;
+  }
+  OpeningAhead ahead{ctx};
+  if (opening_ahead && ahead_fits) {
+    ahead.count = count;
+    for (ahead.nvr = 0; ((size_t)1 << ahead.nvr) < num_rows; ++ahead.nvr) {}
+    ahead.row_pts.resize(count * ahead.nvr);
+    ck(sp_hyrax_prove_batch_begin(ctx, pk.ck, pk.ck_s, count, comms.data(), rows_W, polys.data(), M, blinds.data(), rngs_ahead.data(), rng_blocks_ahead.data(), &ahead.job),
+       "prove_batch: PCS::prove (begin)");
+  }
   phase(0);
   // :246-253 z = [W | 1 | public]
   each([&](Item& it, size_t) {
@@ -1632,10 +1688,10 @@ static void prove_batch_chunk(const SpartanProverKey& pk, SpartanPrepSNARK* cons
     tB[k] = ps.z;
   });
   std::vector<fe_t> inner_polys(count * 2 * num_rounds_y), r_y(count * num_rounds_y), inner_final(count * 2);
-  ck(sp_sumcheck_quad_lockstep(ctx, count, u64p(claims.data()), num_rounds_y, tA.data(), tB.data(), trs.data(), u64p(inner_polys.data()), u64p(r_y.data()),
-                               u64p(inner_final.data())),
+  ck(sp_sumcheck_quad_lockstep_observed(ctx, count, u64p(claims.data()), num_rounds_y, tA.data(), tB.data(), trs.data(), u64p(inner_polys.data()), u64p(r_y.data()),
+                                        u64p(inner_final.data()), ahead.job ? &OpeningAhead::on_inner_round : nullptr, &ahead),
      "prove_batch: inner sum-check");
-  const size_t num_rows = (M + W_ - 1) / W_, cols = M / num_rows;
+  ck(ahead.rc, "prove_batch: PCS::prove (rows)");
   std::vector<fe_t> eval_W(count);
   // :405-421 eval_W
   each([&](Item& it, size_t k) {
@@ -1651,14 +1707,12 @@ static void prove_batch_chunk(const SpartanProverKey& pk, SpartanPrepSNARK* cons
     eval_W[k] = fe_mul<S>(fe_sub<S>(eval_Z, fe_mul<S>(it.r_y[0], eval_X)), fe_inv_vartime<S>(denom));
   });
   phase(4);
-  // :423-436 blind, commit to eval_W, PCS::prove - never announced ahead. Per proof: the blind and the commitment of eval_W (a host walk of two table
-  // entries); then the openings - ONE sp_hyrax_prove_batch call, or with SS_BATCH_PER_PROOF_OPENING one sp_hyrax_prove per proof, one after the
-  // other, over the same arguments; then the per-proof appends
+  // :423-436 blind, commit to eval_W, PCS::prove. Per proof: the blind and the commitment of eval_W (a host walk of two table
+  // entries); then the openings - sp_hyrax_prove_batch_finish of the job begun ahead, or ONE sp_hyrax_prove_batch call, or with
+  // SS_BATCH_PER_PROOF_OPENING one sp_hyrax_prove per proof, one after the other, over the same arguments; then the per-proof appends
   const size_t arg_words = 16 + 4 * cols + 8, npt = num_rounds_y - 1;
   std::vector<fe_t> blind_eval_W(count), points(count * npt);
   std::vector<aff_t> comm_eval_W(count);
-  std::vector<const uint64_t*> comms(count), blinds(count);
-  std::vector<const sp_table*> polys(count);
   std::vector<const uint8_t*> rngs(count);
   std::vector<size_t> rng_blocks(count);
   each([&](Item& it, size_t k) {
@@ -1668,16 +1722,19 @@ static void prove_batch_chunk(const SpartanProverKey& pk, SpartanPrepSNARK* cons
     it.proof.pf(eval_W[k]);
     it.proof.pf(blind_eval_W[k]);
     if (tape.pos + cols + 2 > tape.blocks) throw Error(SP_ERR_INTERNAL, "random tape exhausted");
-    comms[k] = u64p(&it.comm_W[0].x);
-    blinds[k] = u64p(it.r_W.data());
-    polys[k] = it.ps->W;
     rngs[k] = tape.bytes + 64 * tape.pos;
     rng_blocks[k] = tape.blocks - tape.pos;
+    if (ahead.job && rngs[k] != rngs_ahead[k]) throw Error(SP_ERR_INTERNAL, "the opening was begun on other tape blocks than PCS::prove draws");
     std::copy(it.r_y.begin() + 1, it.r_y.end(), points.begin() + k * npt);
   });
   std::vector<uint64_t> args(count * arg_words);
-  const size_t rows_W = items[0].comm_W.size();
-  if (flags & SS_BATCH_PER_PROOF_OPENING)
+  if (ahead.job) {
+    sp_opening_job* job = ahead.job;
+    ahead.job = nullptr;  // consumed by _finish whatever it returns
+    ck(sp_hyrax_prove_batch_finish(ctx, job, pk.ck, pk.ck_s, count, trs.data(), comms.data(), rows_W, polys.data(), M, blinds.data(), u64p(points.data()), npt,
+                                   u64p(&comm_eval_W[0].x), u64p(blind_eval_W.data()), rngs.data(), rng_blocks.data(), args.data()),
+       "prove_batch: PCS::prove (finish)");
+  } else if (flags & SS_BATCH_PER_PROOF_OPENING)
     each([&](Item&, size_t k) {
       ck(sp_hyrax_prove(ctx, pk.ck, pk.ck_s, trs[k], comms[k], rows_W, polys[k], M, blinds[k], u64p(&points[k * npt]), npt, u64p(&comm_eval_W[k].x), u64p(&blind_eval_W[k]),
                         rngs[k], rng_blocks[k], &args[k * arg_words]),
@@ -2476,7 +2533,8 @@ int ss_prove_hook(void* pk, void* ps, const uint64_t* publics_u64, size_t npub, 
 }
 // prove_batch(): `count` states of one key (pss), publics count x npub words, one tape per proof (tapes[k]: tape_blocks[k] blocks of 64 bytes), out_words
 // count x out_cap_each words (proof k at k * out_cap_each, ss_proof_words(pk) words long), tape_used[k] = blocks proof k consumed; phase_ms[7]: the
-// batch's wall-clock per phase, in ss_prove's slots; flags: SS_BATCH_PER_PROOF_OPENING = the openings as `count` sp_hyrax_prove calls (same proofs)
+// batch's wall-clock per phase, in ss_prove's slots; flags: SS_BATCH_PER_PROOF_OPENING = the openings as `count` sp_hyrax_prove calls (same proofs);
+// SS_BATCH_OPENING_AHEAD / SS_BATCH_OPENING_BEHIND = the batched opening begun ahead of the sum-checks / called behind them (same proofs; prove_batch_chunk)
 int ss_prove_batch_opts(void* pk, void* const* pss, size_t count, const uint64_t* publics_u64, size_t npub, const uint8_t* const* tapes, const size_t* tape_blocks,
                         size_t* tape_used, uint64_t* out_words, size_t out_cap_each, double* phase_ms, unsigned flags) {
   try {

@@ -3,13 +3,15 @@
 `prove_batch` call, (d) one `prove_batch(per_proof_opening=True)` call: (c) with the openings as K sp_hyrax_prove calls, what prove_batch did before
 sp_hyrax_prove_batch, (e) / (f) / (g) one `prove_batch` call with evals_rx + poly_ABC and the rest commitments both forced to their batched forms except
 (e) per_proof_polyabc=True, (f) per_proof_rest_commit=True, (g) neither: the three legs the driver's two defaults are decided by (the batched form is
-taken from the smallest K at which (g)'s median lies below the minimum of (e), respectively (f)). One process, the legs alternating; median (min .. max) of `runs` repetitions after `warmup`, host clock; the phases of (c) and
+taken from the smallest K at which (g)'s median lies below the minimum of (e), respectively (f)), (h) / (i) one `prove_batch` call with the openings begun
+ahead of the sum-checks (opening_ahead=True: sp_hyrax_prove_batch_begin / _rows / _finish) and the same batch with opening_ahead=False (the ahead form
+becomes the default from the smallest K at which (h)'s median lies below (i)'s minimum). One process, the legs alternating; median (min .. max) of `runs` repetitions after `warmup`, host clock; the phases of (c) and
 (d) per K, the batched opening's kernels and the launches of one sp_poly_abc_batch beside the same K as sp_eq_table_into + sp_poly_abc pairs, by HIP
 events. Then the lockstep cubic
 kernels alone at 2^20-element tables, 16 instances, by the HIP events attached to their dispatches (sp_ctx_kernel_stats), beside the single-proof
 k_bind_eval_cubic_stream of the same run. Writes a Markdown report (profiles/prove_batch.md holds this output for this commit and its parent).
 --no-batch: legs (a) and (b) only - they need nothing of prove_batch, so this form also runs on the commit before it (the baseline column).
-usage: python tools/prove_batch_timing.py [--out FILE] [--runs 20] [--warmup 3] [--ks 1,4,16] [--no-batch] [--no-options] [--no-kernels]"""
+usage: python tools/prove_batch_timing.py [--out FILE] [--runs 20] [--warmup 3] [--ks 1,4,16] [--no-batch] [--no-options] [--no-ahead] [--no-kernels]"""
 import argparse
 import ctypes
 import os
@@ -128,6 +130,7 @@ def main():
     ap.add_argument("--no-batch", action="store_true", help="legs (a) and (b) only: runs on the commit before prove_batch too")
     ap.add_argument("--no-kernels", action="store_true")
     ap.add_argument("--no-options", action="store_true", help="without legs (e), (f), (g): runs on the commit before sp_poly_abc_batch too")
+    ap.add_argument("--no-ahead", action="store_true", help="without legs (h), (i): runs on the commit before sp_hyrax_prove_batch_begin too")
     a = ap.parse_args()
     ks = [int(k) for k in a.ks.split(",")]
     kmax = max(ks)
@@ -165,8 +168,10 @@ def main():
     if not a.no_batch and not a.no_options:
         legs += [("e", lambda K: batch(K, per_proof_polyabc=True, per_proof_rest_commit=False)), ("f", lambda K: batch(K, per_proof_polyabc=False, per_proof_rest_commit=True)),
                  ("g", lambda K: batch(K, per_proof_polyabc=False, per_proof_rest_commit=False))]
+    if not a.no_batch and not a.no_ahead:
+        legs += [("h", lambda K: batch(K, opening_ahead=True)), ("i", lambda K: batch(K, opening_ahead=False))]
     lines = [f"# prove_batch on the MI355X, {MSG_LEN}-byte messages: {d['num_cons']} constraints", "",
-             f"command: python tools/prove_batch_timing.py --runs {a.runs} --warmup {a.warmup} --ks {a.ks}" + (" --no-batch" if a.no_batch else "") + (" --no-kernels" if a.no_kernels else ""),
+             f"command: python tools/prove_batch_timing.py --runs {a.runs} --warmup {a.warmup} --ks {a.ks}" + (" --no-batch" if a.no_batch else "") + (" --no-ahead" if a.no_ahead else "") + (" --no-kernels" if a.no_kernels else ""),
              "", f"One process, the legs alternating; median (min .. max) of {a.runs} repetitions after {a.warmup}, host clock, ms. (a) = K sequential `prove` calls, the",
              "headline driver; (b) = K sequential reference-order proves" + ("." if a.no_batch else "; (c) = one `prove_batch` call over the same K states; (d) = (c) with")]
     if not a.no_batch:
@@ -175,10 +180,16 @@ def main():
         lines.append("(g) = (c) with evals_rx + poly_ABC (`sp_poly_abc_batch`) and the rest commitments (one `sp_fixed_base_mul_h`) both forced to their batched forms; (e) = (g) with")
         lines.append("`per_proof_polyabc=True`; (f) = (g) with `per_proof_rest_commit=True`. A batched form becomes the driver's default from the smallest K at which the")
         lines.append("median of (g) lies below the minimum of (e), respectively (f).")
+    if not a.no_batch and not a.no_ahead:
+        lines.append("(h) = (c) with `opening_ahead=True`: the openings begun once comm_W is complete (`sp_hyrax_prove_batch_begin`), their row stage queued from the inner")
+        lines.append("sum-check's hook (`_rows`) and collected by `_finish`; (i) = (c) with `opening_ahead=False`. The ahead form becomes the default from the smallest K at")
+        lines.append("which the median of (h) lies below the minimum of (i).")
     names = [name for name, _ in legs]
     ratios = [] if a.no_batch else ["(c) / (a)", "(c) / (d)"]
     if "g" in names:
         ratios += ["(g) median < (e) min", "(g) median < (f) min"]
+    if "h" in names:
+        ratios += ["(h) median < (i) min"]
     cols = [f"({n}) total" for n in names] + [f"({n}) per proof" for n in names] + ratios
     lines += ["", "| K | " + " | ".join(cols) + " |", "|---|" + "---|" * len(cols)]
     phase_lines = []
@@ -199,23 +210,36 @@ def main():
             cells += [f"{s['c'][0] / s['a'][0]:.2f}", f"{s['c'][0] / s['d'][0]:.2f}"]
         if "g" in s:
             cells += ["yes" if s["g"][0] < s["e"][1] else "no", "yes" if s["g"][0] < s["f"][1] else "no"]
+        if "h" in s:
+            cells += ["yes" if s["h"][0] < s["i"][1] else "no"]
         lines.append(f"| {K} | " + " | ".join(cells) + " |")
         print(lines[-1], flush=True)
-        for name in ("c", "d", "e", "f", "g"):  # the batch's own phase split (wall-clock of the whole batch per phase), over the same repetitions
+        for name in ("c", "d", "e", "f", "g", "h", "i"):  # the batch's own phase split (wall-clock of the whole batch per phase), over the same repetitions
             if ph.get(name):
                 phase_lines.append(f"| {K} | ({name}) | " + " | ".join(fmt(stat([p[k] for p in ph[name]])) for k in host.PHASES) + " |")
     if phase_lines:
         lines += ["", "Phases of the `prove_batch` calls above, ms for the whole batch, median (min .. max) over the same repetitions:", "",
                   "| K | leg | " + " | ".join(host.PHASES) + " |", "|---|---|" + "---|" * len(host.PHASES)] + phase_lines
     if not a.no_batch and not a.no_kernels:  # the batched opening's launches at the largest K, by the HIP events around them
-        batch(kmax)
+        behind = {} if a.no_ahead else {"opening_ahead": False}
+        batch(kmax, **behind)
         ctx.reset_stats(True)
-        batch(kmax)
+        batch(kmax, **behind)
         ctx.synchronize()
         lines += ["", f"The launches of one `sp_hyrax_prove_batch` at K = {kmax} (HIP events around each launch):", "", "| kernel class | launches | device ms |", "|---|---|---|"]
         for what in ("opening_batch_mask", "opening_batch_rowmat", "opening_batch_walk", "opening_batch_z"):
             ms, launches, _ = ctx.kernel_stats(what)
             lines.append(f"| {what} | {launches} | {ms:.4f} |")
+        if not a.no_ahead:
+            batch(kmax, opening_ahead=True)
+            ctx.reset_stats(True)
+            batch(kmax, opening_ahead=True)
+            ctx.synchronize()
+            lines += ["", f"The launches of the same opening begun ahead (`opening_ahead=True`) at K = {kmax}, on the auxiliary stream beside the sum-checks' launches:", "",
+                      "| kernel class | launches | device ms |", "|---|---|---|"]
+            for what in ("opening_batch_dvec", "opening_batch_rowmat", "opening_batch_walk", "opening_batch_ip", "opening_batch_z"):
+                ms, launches, _ = ctx.kernel_stats(what)
+                lines.append(f"| {what} | {launches} | {ms:.4f} |")
         ctx.reset_stats(False)
     if not a.no_batch and not a.no_options and not a.no_kernels:
         poly_abc_launches(ctx, sn, lines, kmax)

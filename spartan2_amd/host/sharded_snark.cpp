@@ -299,8 +299,7 @@ ProofBuf sharded_prove(const ShardedKey& pk, ShardedPrep& ps, const uint64_t* pu
     fprintf(stderr, "sharded lap %-28s %.3f ms\n", name, t - t_lap);
     t_lap = t;
   };
-  std::vector<fe_t> publics(npub);
-  for (size_t i = 0; i < npub; ++i) publics[i] = fe_from_u64<S>(publics_u64[i]);
+  const std::vector<fe_t> publics = publics_from_u64(publics_u64, npub), no_challenges;  // (the sharded key takes no circuit with verifier challenges)
 
   // The rest rows of this rank's block when the segment is all padding (commit_zeros = h * blind, hyrax_pc.rs:305-319): their blinds are drawn and the
   // fixed-base job launched before anything else, as the unsharded driver does - the chain commitment -> absorb -> tau is what the outer sum-check waits
@@ -312,17 +311,7 @@ ProofBuf sharded_prove(const ShardedKey& pk, ShardedPrep& ps, const uint64_t* pu
   size_t rest_first = 0, rest_cnt = 0;
   block_overlap(lo, hi, rows_fixed, rows_all, &rest_first, &rest_cnt);
   sp_fb_job* rest_job = nullptr;
-  struct RestGuard {  // an error exit must not leave the context's one asynchronous fixed-base job outstanding
-    sp_ctx* ctx;
-    sp_fb_job*& job;
-    size_t n;
-    ~RestGuard() {
-      if (job) {
-        std::vector<uint64_t> sink(8 * n + 8);
-        sp_fixed_base_mul_h_finish(ctx, job, sink.data());
-      }
-    }
-  } rest_guard{ctx, rest_job, rest_cnt};
+  FbJobGuard rest_guard{ctx, rest_job, rest_cnt};
   if (rest_cnt && d.num_rest_unpadded == 0)
     ck(sp_fixed_base_mul_h_begin(ctx, pk.ck, u64p(r_W_rest.data() + (rest_first - rows_fixed)), rest_cnt, &rest_job), "commit_zeros (row block, begin)");
   // z = [W | 1 | public | 0 ...] replicated; Az, Bz, Cz of this rank's rows and the round-0 products of its pairs. Issued next: the products depend on
@@ -332,9 +321,7 @@ ProofBuf sharded_prove(const ShardedKey& pk, ShardedPrep& ps, const uint64_t* pu
   ck(sp_table_copy(ctx, ps.z, 0, ps.W, 0, M), "z <- W");
   {
     ck(sp_table_zero(ctx, ps.z, M, M), "clear z high half");
-    std::vector<fe_t> tail(pk.num_extra);
-    tail[0] = fe_one<S>();
-    std::copy(publics.begin(), publics.end(), tail.begin() + 1);
+    const std::vector<fe_t> tail = z_tail(pk.num_extra, publics, no_challenges);
     if (tail.size() <= 2048) ck(sp_table_write_async(ctx, ps.z, M, u64p(tail.data()), tail.size()), "z tail");
     else ck(sp_table_write(ctx, ps.z, M, u64p(tail.data()), tail.size()), "z tail");
   }
@@ -351,10 +338,7 @@ ProofBuf sharded_prove(const ShardedKey& pk, ShardedPrep& ps, const uint64_t* pu
 
   lap("z_and_spmv_issue");
   Tr tr(ctx, "SpartanSNARK");
-  tr.absorb("vk", pk.vk_digest, 32);
-  tr.absorb_scalars("public_values", publics.data(), npub);
-  if (ps.rows_shared) tr.absorb("comm_W_shared", ps.comm_shared_bytes.data(), ps.comm_shared_bytes.size());
-  if (ps.rows_precommitted) tr.absorb("comm_W_precommitted", ps.comm_pre_bytes.data(), ps.comm_pre_bytes.size());
+  absorb_instance_prefix(tr, pk.vk_digest, publics.data(), npub, ps.comm_shared_bytes, ps.comm_pre_bytes);
   // rest rows (bellpepper/r1cs.rs:463-491): every rank draws all blinds, commits the rest rows of its block (commit_zeros = h * blind when the
   // segment is all padding), one all-gather
   {
@@ -374,8 +358,7 @@ ProofBuf sharded_prove(const ShardedKey& pk, ShardedPrep& ps, const uint64_t* pu
     gather_rows(comm, mine, &all);
     lap("gather_rows");
     for (size_t r = rows_fixed; r < rows_all; ++r) ps.comm_W[r] = all[r];
-    const std::vector<uint8_t> b = commitment_bytes(ps.comm_W.data() + rows_fixed, rows_rest);
-    tr.absorb("comm_W_rest", b.data(), b.size());
+    absorb_comm_W_rest(tr, ps.comm_W.data() + rows_fixed, rows_rest);
     lap("absorb_rest_rows");
   }
   // the proof's comm_W omits the rows of empty segments (there are none in the padded layout: a segment with no variables has no rows)
@@ -557,8 +540,7 @@ ProofBuf sharded_prove(const ShardedKey& pk, ShardedPrep& ps, const uint64_t* pu
   lap("helper_start_and_tau");
 
   ProofBuf proof;
-  for (const aff_t& a : comm_W) proof.pp(a);
-  for (const fe_t& f : publics) proof.pf(f);
+  proof.header(comm_W, publics, no_challenges);
   // outer sum-check on slices: ell - k local rounds with one exchange each, then k rounds on the gathered 2^k-element tables
   std::vector<fe_t> outer_polys(3 * lx), r_x(lx);
   fe_t claims_outer[3];
@@ -617,13 +599,12 @@ ProofBuf sharded_prove(const ShardedKey& pk, ShardedPrep& ps, const uint64_t* pu
     for (int i = 0; i < 3; ++i) claims_outer[i] = fin[i];
   }
   tr.absorb_scalars("claims_outer", claims_outer, 3);
-  for (const fe_t& f : outer_polys) proof.pf(f);
-  for (int i = 0; i < 3; ++i) proof.pf(claims_outer[i]);
+  proof.outer(outer_polys.data(), lx, claims_outer);
   const double t_outer = now_ms();
   lap("outer");
 
   const fe_t r = tr.squeeze("r");
-  const fe_t claim_inner_joint = fe_add<S>(fe_add<S>(claims_outer[0], fe_mul<S>(r, claims_outer[1])), fe_mul<S>(fe_mul<S>(r, r), claims_outer[2]));
+  const fe_t claim_inner_joint = joint_inner_claim(claims_outer, r);
   ck(sp_eq_table_into(ctx, u64p(r_x.data()), lx, ps.rx), "evals_rx");
   ck(sp_poly_abc(ctx, pk.S_cols, ps.rx, u64p(&r), 2 * M / world, ps.abc), "poly_ABC (column slice)");
   const double t_abc = now_ms();
@@ -690,15 +671,8 @@ ProofBuf sharded_prove(const ShardedKey& pk, ShardedPrep& ps, const uint64_t* pu
     claims_inner[0] = fin[0];
     claims_inner[1] = fin[1];
   }
-  for (const fe_t& f : inner_polys) proof.pf(f);
-  const fe_t eval_Z = claims_inner[1];
-  std::vector<fe_t> X;
-  X.push_back(fe_one<S>());
-  X.insert(X.end(), publics.begin(), publics.end());
-  const fe_t eval_X = sparse_poly_evaluate(ly - 1, X, r_y.data() + 1);
-  const fe_t denom = fe_sub<S>(fe_one<S>(), r_y[0]);
-  if (fe_is_zero(denom)) throw Error(SP_ERR_DIVISION_BY_ZERO, "DivisionByZero");
-  const fe_t eval_W = fe_mul<S>(fe_sub<S>(eval_Z, fe_mul<S>(r_y[0], eval_X)), fe_inv_vartime<S>(denom));
+  proof.inner(inner_polys.data(), ly);
+  const fe_t eval_W = eval_W_from(claims_inner[1], r_y.data(), ly, publics, no_challenges);
   const double t_inner = now_ms();
   lap("abc_and_inner");
 
@@ -806,16 +780,7 @@ ProofBuf sharded_prove(const ShardedKey& pk, ShardedPrep& ps, const uint64_t* pu
   }
   aff_t beta;
   ck(sp_hyrax_commit_small(ctx, pk.ck_s, u64p(&ip), 1, u64p(&r_beta), u64p(&beta.x)), "beta");
-  {
-    uint8_t b[128];
-    point_bytes(comm_LZ, b);
-    point_bytes(comm_eval_W, b + 64);
-    tr.absorb("U", b, 128);
-    point_bytes(delta, b);
-    tr.absorb("delta", b, 64);
-    point_bytes(beta, b);
-    tr.absorb("beta", b, 64);
-  }
+  absorb_ipa_instance(tr, comm_LZ, comm_eval_W, delta, beta);
   const fe_t rr = tr.squeeze("r");
   lap("beta_and_transcript");
   proof.pp(delta);
@@ -826,13 +791,7 @@ ProofBuf sharded_prove(const ShardedKey& pk, ShardedPrep& ps, const uint64_t* pu
   const double t_end = now_ms();
   lap("z_vec");
   if (phase_ms) {
-    phase_ms[0] = t_wit - t_start;
-    phase_ms[1] = t_mv - t_wit;
-    phase_ms[2] = t_outer - t_mv;
-    phase_ms[3] = t_abc - t_outer;
-    phase_ms[4] = t_inner - t_abc;
-    phase_ms[5] = t_end - t_inner;
-    phase_ms[6] = t_end - t_start;
+    fill_phase_ms(phase_ms, t_start, t_wit, t_mv, t_outer, t_abc, t_inner, t_end);
     phase_ms[7] = (double)comm.calls;
   }
   return proof;

@@ -1,5 +1,7 @@
-// Pieces shared by the host-side protocol drivers above the C ABI (spartan_snark.cpp, sharded_snark.cpp): the integer R1CS view and
-// SplitR1CSShape::new padding, this build's generator derivation, the vk digest (the reference's SHA-256 stream), the O(sqrt N) host-side eq tables.
+// Pieces shared by the host-side protocol drivers above the C ABI (spartan_snark.cpp, sharded_snark.cpp, neutronnova_zk.cpp): the integer R1CS view and
+// SplitR1CSShape::new padding, this build's generator derivation, the vk digest (the reference's SHA-256 stream), the O(sqrt N) host-side eq tables,
+// the verifier-side pieces (sum-check verification, canonicity) and the prover-side ones: each host-side statement of SpartanSNARK::prove
+// (src/spartan.rs:226-466) that more than one driver makes, stated once.
 #pragma once
 #include "host_common.hpp"
 
@@ -225,7 +227,130 @@ struct ProofBuf {  // a proof in the canonical flat layout of DESIGN.md section 
   void pc(const std::vector<aff_t>& c) {
     for (const aff_t& a : c) pp(a);
   }
+  void pfs(const fe_t* f, size_t n) { words.insert(words.end(), u64p(f), u64p(f) + 4 * n); }
+  // the blocks a prover appends, in order: the instance (comm_W, public values, challenges - SplitR1CSInstance carries them, src/r1cs/mod.rs:1423-1437), ...
+  void header(const std::vector<aff_t>& comm_W, const std::vector<fe_t>& publics, const std::vector<fe_t>& challenges) {
+    pc(comm_W);
+    pfs(publics.data(), publics.size());
+    pfs(challenges.data(), challenges.size());
+  }
+  // ... the outer sum-check's 3 coefficients a round and its three claims (src/spartan.rs:291-310), the inner one's 2 a round (:323-404)
+  void outer(const fe_t* polys, size_t rounds, const fe_t claims[3]) {
+    pfs(polys, 3 * rounds);
+    pfs(claims, 3);
+  }
+  void inner(const fe_t* polys, size_t rounds) { pfs(polys, 2 * rounds); }
 };
+
+// ---- prover-side pieces shared by the Spartan drivers -----------------------------------------------------------------------------------------------
+// The statements of SpartanSNARK::prove (src/spartan.rs:226-466, bellpepper/r1cs.rs:411-540) that prove, prove_reference_order, prove_batch_chunk
+// (spartan_snark.cpp), sharded_prove (sharded_snark.cpp) and is_sat make alike. Each driver stays straight-line code in its own order - what it issues
+// when, on which thread, through which entry point - and calls these for the statement bodies. Nothing here knows a key or a prep-state type.
+
+// `synth`: circuit.synthesize(.., Some(&challenges)) for circuits with verifier challenges (bellpepper/r1cs.rs:443-461): receives the challenges and
+// writes the num_rest_unpadded values of the rest segment (Montgomery limbs); non-zero return = SynthesisError
+typedef int (*ss_rest_hook)(void* user, const uint64_t* challenges, size_t num_challenges, uint64_t* out_rest);
+
+inline std::vector<fe_t> publics_from_u64(const uint64_t* publics_u64, size_t n) {
+  std::vector<fe_t> publics(n);
+  for (size_t i = 0; i < n; ++i) publics[i] = fe_from_u64<S>(publics_u64[i]);
+  return publics;
+}
+// the transcript up to the rest commitment (src/spartan.rs:226-236, bellpepper/r1cs.rs:422-427): vk, public_values, comm_W_shared, comm_W_precommitted.
+// shared_bytes / pre_bytes: the commitments' transcript encodings (commitment_bytes), empty for a segment without variables
+inline void absorb_instance_prefix(Tr& tr, const uint8_t vk_digest[32], const fe_t* publics, size_t n, const std::vector<uint8_t>& shared_bytes,
+                                   const std::vector<uint8_t>& pre_bytes) {
+  tr.absorb("vk", vk_digest, 32);
+  tr.absorb_scalars("public_values", publics, n);
+  if (!shared_bytes.empty()) tr.absorb("comm_W_shared", shared_bytes.data(), shared_bytes.size());
+  if (!pre_bytes.empty()) tr.absorb("comm_W_precommitted", pre_bytes.data(), pre_bytes.size());
+}
+// verifier challenges (bellpepper/r1cs.rs:429-431): squeezed right after the precommitted commitment
+inline std::vector<fe_t> squeeze_challenges(Tr& tr, size_t n) {
+  std::vector<fe_t> challenges(n);
+  for (auto& c : challenges) c = tr.squeeze("challenge");
+  return challenges;
+}
+// the rest of the witness that depends on the challenges (bellpepper/r1cs.rs:443-461): n_rest_unpadded values (+ one spare element) from the circuit's hook
+inline std::vector<fe_t> synthesize_rest(ss_rest_hook synth, void* synth_user, const uint64_t* challenges, size_t num_challenges, size_t n_rest_unpadded) {
+  if (!synth) throw Error(SP_ERR_INTERNAL, "a circuit with verifier challenges needs its synthesize callback");
+  std::vector<fe_t> rest(n_rest_unpadded + 1);
+  if (synth(synth_user, challenges, num_challenges, u64p(rest.data())) != 0) throw Error(SP_ERR_INTERNAL, "SynthesisError: the circuit's synthesize callback failed");
+  return rest;
+}
+// the last num_extra entries of z = [W | 1 | public | challenges] (src/spartan.rs:246-253)
+inline std::vector<fe_t> z_tail(size_t num_extra, const std::vector<fe_t>& publics, const std::vector<fe_t>& challenges) {
+  std::vector<fe_t> tail(num_extra);
+  tail[0] = fe_one<S>();
+  std::copy(publics.begin(), publics.end(), tail.begin() + 1);
+  std::copy(challenges.begin(), challenges.end(), tail.begin() + 1 + publics.size());
+  return tail;
+}
+// the rest segment's commitment for one proof, on the calling thread (bellpepper/r1cs.rs:463-491): PCS::commit of a segment with values ...
+inline void commit_rest_values(sp_ctx* ctx, const sp_ck* key, const sp_table* W, const sp_dims& d, bool is_small, const fe_t* blinds, aff_t* out) {
+  ck(sp_hyrax_commit(ctx, key, W, d.num_shared + d.num_precommitted, d.num_rest, u64p(blinds), is_small ? 1 : 0, u64p(&out->x)), "commit rest");
+}
+// ... and commit_zeros (hyrax_pc.rs:305-319; h * blind per row) of one that is all padding
+inline void commit_rest_rows(sp_ctx* ctx, const sp_ck* key, const sp_table* W, const sp_dims& d, bool is_small, const fe_t* blinds, size_t rows_rest, aff_t* out) {
+  if (rows_rest && d.num_rest_unpadded == 0) ck(sp_fixed_base_mul_h(ctx, key, u64p(blinds), rows_rest, u64p(&out->x)), "commit_zeros");  // :467-469
+  else if (rows_rest) commit_rest_values(ctx, key, W, d, is_small, blinds, out);
+}
+inline void absorb_comm_W_rest(Tr& tr, const aff_t* rest_rows, size_t rows_rest) {
+  const std::vector<uint8_t> b = commitment_bytes(rest_rows, rows_rest);
+  tr.absorb("comm_W_rest", b.data(), b.size());
+}
+// combine_blinds (bellpepper/r1cs.rs:515-524): the blinds of the rows committed at prep time, then the rest rows'
+inline std::vector<fe_t> combine_blinds(const std::vector<fe_t>& r_W_fixed, const std::vector<fe_t>& r_W_rest) {
+  std::vector<fe_t> r_W = r_W_fixed;
+  r_W.insert(r_W.end(), r_W_rest.begin(), r_W_rest.end());
+  return r_W;
+}
+// an error exit between sp_fixed_base_mul_h_begin and _finish must not leave the context's one asynchronous fixed-base job outstanding
+struct FbJobGuard {
+  sp_ctx* ctx;
+  sp_fb_job*& job;
+  size_t n;
+  ~FbJobGuard() {
+    if (job) {
+      std::vector<uint64_t> sink(8 * n + 8);
+      (void)sp_fixed_base_mul_h_finish(ctx, job, sink.data());
+      job = nullptr;
+    }
+  }
+};
+// claim_inner_joint = claims_outer[0] + r claims_outer[1] + r^2 claims_outer[2]   (src/spartan.rs:311-315)
+inline fe_t joint_inner_claim(const fe_t claims_outer[3], const fe_t& r) {
+  return fe_add<S>(fe_add<S>(claims_outer[0], fe_mul<S>(r, claims_outer[1])), fe_mul<S>(fe_mul<S>(r, r), claims_outer[2]));
+}
+// eval_W = (eval_Z - r_y0 eval_X) / (1 - r_y0)   (src/spartan.rs:405-421); to_regular_instance: X = public_values ++ challenges (src/r1cs/mod.rs:1546-1549)
+inline fe_t eval_W_from(const fe_t& eval_Z, const fe_t* r_y, size_t num_rounds_y, const std::vector<fe_t>& publics, const std::vector<fe_t>& challenges) {
+  const fe_t eval_X = sparse_poly_evaluate(num_rounds_y - 1, z_tail(1 + publics.size() + challenges.size(), publics, challenges), r_y + 1);
+  const fe_t denom = fe_sub<S>(fe_one<S>(), r_y[0]);
+  if (fe_is_zero(denom)) throw Error(SP_ERR_DIVISION_BY_ZERO, "DivisionByZero");
+  return fe_mul<S>(fe_sub<S>(eval_Z, fe_mul<S>(r_y[0], eval_X)), fe_inv_vartime<S>(denom));
+}
+// the IPA's instance and first message in front of its challenge (ipa.rs:128-152): U = (comm_LZ, comm_eval_W), delta, beta
+inline void absorb_ipa_instance(Tr& tr, const aff_t& comm_LZ, const aff_t& comm_eval_W, const aff_t& delta, const aff_t& beta) {
+  uint8_t b[128];
+  point_bytes(comm_LZ, b);
+  point_bytes(comm_eval_W, b + 64);
+  tr.absorb("U", b, 128);
+  point_bytes(delta, b);
+  tr.absorb("delta", b, 64);
+  point_bytes(beta, b);
+  tr.absorb("beta", b, 64);
+}
+// a prove's wall-clock per phase from its seven time stamps (ms): witness_commit, matvec, outer, poly_abc, inner, pcs, total. mv_issue: the time spent
+// issuing the matrix-vector product inside the witness phase (the driver that issues it there books it with the product)
+inline void fill_phase_ms(double ms[8], double t_start, double t_wit, double t_mv, double t_outer, double t_abc, double t_inner, double t_end, double mv_issue = 0) {
+  ms[0] = t_wit - t_start - mv_issue;
+  ms[1] = t_mv - t_wit + mv_issue;
+  ms[2] = t_outer - t_mv;
+  ms[3] = t_abc - t_outer;
+  ms[4] = t_inner - t_abc;
+  ms[5] = t_end - t_inner;
+  ms[6] = t_end - t_start;
+}
 
 // <z_vec, ck> of the IPA check (ipa.rs:196-203) depends on nothing but the proof: a verifier starts its device part before the transcript work
 struct ZJob {

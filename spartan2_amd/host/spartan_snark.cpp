@@ -174,146 +174,21 @@ SpartanProverKey* setup(sp_ctx* ctx, const R1CSIntView& R) {
 
 static double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
-// SpartanSNARK::prep_prove (src/spartan.rs:176-216) behind its witness source. `fill_W` writes the witness segments into the zeroed table W (each segment
-// at its padded offset); everything after it - blinds drawn from the tape in the same order, commitments, tables, cached Az/Bz/Cz, scratch - is shared by
-// the sources: machine words from the frontend (prep_prove) or the SHA-256 witness kernel (prep_prove_sha256).
-static SpartanPrepSNARK* prep_prove_from(const SpartanProverKey& pk, bool is_small, Tape& tape, const std::function<void(sp_table* W)>& fill_W) {
-  const sp_dims& d = pk.dims;
-  auto* ps = new SpartanPrepSNARK();
-  ps->bg.set_spin_policy(&helper_may_spin);
-  ps->bg2.set_spin_policy(&helper_may_spin);
-  try {
-    sp_ctx* ctx = pk.ctx;
-    const size_t M = pk.num_vars, N = d.num_cons;
-    ps->is_small = is_small;
-    ps->key = &pk;
-    const double t_begin = now_ms();
-    double t_last = t_begin;
-    auto phase = [&](int k) {
-      const double t = now_ms();
-      ps->prep_ms[k] += t - t_last;
-      t_last = t;
-    };
-    {
-      const char* e = getenv("SPARTAN_LZ_DIRECT");
-      if (e && e[0] == '1') ps->flags |= FLAG_LZ_DIRECT;
-      e = getenv("SPARTAN_PREFIX_CACHE");
-      if (e && e[0] == '1') ps->flags |= FLAG_PREFIX_CACHE;
-    }
-    // shared_witness / precommitted_witness (bellpepper/r1cs.rs:306-409): each segment starts at its padded offset. The rest
-    // segment is filled here as well: without verifier challenges it does not change between proves.
-    // The words go to the device as they are (8 bytes a value) and become Montgomery-form elements there: sp_table_write_u64 (the reference hands the same
-    // machine words to msm_small, hyrax_pc.rs:266-292, and never builds wide scalars for the commitment either).
-    ck(sp_table_zeros(ctx, M, (size_t)-1, (size_t)-1, &ps->W), "alloc W");
-    fill_W(ps->W);
-    phase(0);
-    const size_t CW = DEFAULT_COMMITMENT_WIDTH;
-    ps->rows_shared = d.num_shared_unpadded ? (d.num_shared + CW - 1) / CW : 0;
-    ps->rows_precommitted = d.num_precommitted_unpadded ? (d.num_precommitted + CW - 1) / CW : 0;
-    ps->r_W_fixed.resize(ps->rows_shared + ps->rows_precommitted);  // PCS::blind (hyrax_pc.rs:192-205), shared first
-    for (auto& b : ps->r_W_fixed) b = tape.next();
-    ps->comm_W_fixed.resize(ps->r_W_fixed.size());
-    if (ps->rows_shared) {
-      ck(sp_hyrax_commit(ctx, pk.ck, ps->W, 0, d.num_shared, u64p(ps->r_W_fixed.data()), is_small ? 1 : 0, u64p(&ps->comm_W_fixed[0].x)), "commit shared");
-      ps->comm_shared_bytes = commitment_bytes(ps->comm_W_fixed.data(), ps->rows_shared);
-    }
-    if (ps->rows_precommitted) {
-      ck(sp_hyrax_commit(ctx, pk.ck, ps->W, d.num_shared, d.num_precommitted, u64p(ps->r_W_fixed.data() + ps->rows_shared), is_small ? 1 : 0,
-                         u64p(&ps->comm_W_fixed[ps->rows_shared].x)),
-         "commit precommitted");
-      ps->comm_pre_bytes = commitment_bytes(ps->comm_W_fixed.data() + ps->rows_shared, ps->rows_precommitted);
-    }
-    phase(1);
-    {
-      const size_t fixed = ps->comm_W_fixed.size(), rows_all = (M + CW - 1) / CW;
-      if (!(ps->flags & FLAG_LZ_DIRECT) && d.num_rest_unpadded == 0 && d.num_challenges == 0 && fixed >= 1 && fixed + 1 <= 512 && rows_all > 1) {
-        // WHEN they are built (SPARTAN_PREP_TABLES): the build is ~3 ms of device work (profiles/r06_prep_prove.md) that pays for itself from the second prove
-        // on a state onwards (50-100 us a prove) and slows whatever proves beside it. "lazy" (default): queued behind the FIRST prove on the state - a state
-        // that is proven once (the reference's own use: prep_prove, prove, drop) never pays, the bench's repeated proves get them from the third on;
-        // "prep": queued here; "sync": built here and waited for (round 5); "off": never.
-        const char* mode = getenv("SPARTAN_PREP_TABLES");
-        ps->lz_points.assign(ps->comm_W_fixed.begin(), ps->comm_W_fixed.end());
-        ps->lz_points.push_back(pk.gens[CW]);  // h
-        ps->lz_mode = !mode || !strcmp(mode, "lazy") ? 1 : (!strcmp(mode, "off") ? 0 : 2);
-        if (mode && !strcmp(mode, "sync")) ck(sp_fbtables_create(ctx, u64p(&ps->lz_points[0].x), ps->lz_points.size(), &ps->lz_tables), "tables of the committed rows");
-        else if (ps->lz_mode == 2) ck(sp_fbtables_create_async(ctx, u64p(&ps->lz_points[0].x), ps->lz_points.size(), &ps->lz_tables), "tables of the committed rows");
-      }
-    }
-    phase(2);
-    // multiply_vec_precommitted (src/r1cs/mod.rs:1112-1128): z = [W_cached | 0 ...]
-    ck(sp_table_zeros(ctx, 2 * M, (size_t)-1, (size_t)-1, &ps->z), "alloc z");
-    ck(sp_table_copy(ctx, ps->z, 0, ps->W, 0, d.num_shared + d.num_precommitted), "copy W");
-    ck(sp_table_set_len(ps->z, pk.num_cols, (size_t)-1, (size_t)-1), "z len");
-    for (sp_table** t : {&ps->caz, &ps->cbz, &ps->ccz, &ps->az, &ps->bz, &ps->cz}) ck(sp_table_zeros(ctx, N, (size_t)-1, (size_t)-1, t), "alloc Az");
-    ck(sp_multiply_vec(ctx, pk.S, ps->z, ps->caz, ps->cbz, ps->ccz), "multiply_vec_precommitted");
-    if (getenv("SPARTAN_PREP_TRACE")) ck(sp_ctx_synchronize(ctx), "sync");
-    phase(3);
-    ck(sp_table_zeros(ctx, N, (size_t)-1, (size_t)-1, &ps->rx), "alloc rx");
-    const char* no_p0 = getenv("SPARTAN_ROUND0_PRODUCTS");  // "0": round 1 of the outer sum-check evaluates straight from Az, Bz, Cz (A/B)
-    if (N >= 2 && !(no_p0 && no_p0[0] == '0')) {
-      ck(sp_table_zeros(ctx, N / 2, (size_t)-1, (size_t)-1, &ps->p0), "alloc round-0 products");
-      ck(sp_table_zeros(ctx, N / 2, (size_t)-1, (size_t)-1, &ps->p1), "alloc round-0 products");
-    }
-    ck(sp_table_zeros(ctx, 2 * M, (size_t)-1, (size_t)-1, &ps->abc), "alloc poly_ABC");
-    ck(sp_ctx_synchronize(ctx), "sync");
-    phase(4);
-    ps->prep_ms[6] = now_ms() - t_begin;
-    if (getenv("SPARTAN_PREP_TRACE"))
-      fprintf(stderr, "prep_prove: witness %.3f commit %.3f tables %.3f matvec %.3f scratch %.3f total %.3f ms\n", ps->prep_ms[0], ps->prep_ms[1], ps->prep_ms[2], ps->prep_ms[3],
-              ps->prep_ms[4], ps->prep_ms[6]);
-  } catch (...) {
-    delete ps;
-    throw;
-  }
-  return ps;
-}
-
-SpartanPrepSNARK* prep_prove(const SpartanProverKey& pk, const uint64_t* witness_u64, size_t n_witness, bool is_small, Tape& tape) {
-  const sp_dims& d = pk.dims;
-  if (n_witness != d.num_shared_unpadded + d.num_precommitted_unpadded + d.num_rest_unpadded) throw Error(SP_ERR_INVALID_WITNESS_LENGTH, "InvalidWitnessLength");
-  sp_ctx* ctx = pk.ctx;
-  return prep_prove_from(pk, is_small, tape, [&](sp_table* W) {
-    auto put = [&](size_t dst, size_t src, size_t cnt) { ck(sp_table_write_u64(ctx, W, dst, witness_u64 + src, cnt), "upload W"); };
-    put(0, 0, d.num_shared_unpadded);
-    put(d.num_shared, d.num_shared_unpadded, d.num_precommitted_unpadded);
-    // (with verifier challenges the rest segment is synthesized inside every prove, after the challenges are drawn: bellpepper/r1cs.rs:443-461)
-    if (d.num_challenges == 0) put(d.num_shared + d.num_precommitted, d.num_shared_unpadded + d.num_precommitted_unpadded, d.num_rest_unpadded);
-  });
-}
-
-// prep_prove for Sha256Circuit (benches/sha256_spartan.rs:78-136) with the witness generated on the device: the reference's prep_prove INCLUDES witness
-// synthesis (src/spartan.rs:176-216 -> precommitted_witness, bellpepper/r1cs.rs:359-409); here it is sp_sha256_witness on a plan made once per key.
-// The key is a sha256_spartan_circuit key (everything precommitted, 256 public digest bits) for the plan's message length; one key serves every message
-// of that length. out_publics: the 256 digest bits in the order the circuit allocates them (big-endian bit order), from the host's SHA-256.
-SpartanPrepSNARK* prep_prove_sha256(const SpartanProverKey& pk, const sp_sha256_plan* plan, const uint8_t* msg, size_t len, bool is_small, Tape& tape, uint64_t out_publics[256]) {
-  const sp_dims& d = pk.dims;
-  uint64_t info[5];
-  ck(sp_sha256_plan_info(plan, info), "plan info");
-  if (d.num_shared_unpadded != 0 || d.num_rest_unpadded != 0 || d.num_challenges != 0 || info[0] != d.num_precommitted_unpadded)
-    throw Error(SP_ERR_INVALID_WITNESS_LENGTH, "InvalidWitnessLength: the plan's variable count is not the key's");
-  if (len != info[3] || !info[4] || d.num_public != 256) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "the plan does not serve this message length / this key is not a SHA-256 digest circuit");
-  sp_ctx* ctx = pk.ctx;
-  uint8_t digest[32];
-  SpartanPrepSNARK* ps = prep_prove_from(pk, is_small, tape, [&](sp_table* W) {
-    sp_table* tabs[1] = {W};
-    ck(sp_sha256_witness(ctx, plan, msg, len, 1, tabs, d.num_shared, digest), "sha256 witness");
-  });
-  for (int i = 0; i < 256; ++i) out_publics[i] = (digest[i / 8] >> (7 - i % 8)) & 1u;
-  return ps;
-}
-
-// ---- prep_prove for `count` states of one key in one pass -------------------------------------------------------------------------------------------
-// SpartanSNARK::prep_prove (src/spartan.rs:176-216) restated over a batch, phase by phase: what prep_prove_from does per state is done here for all of
-// them - the witnesses (one sp_sha256_witness launch for all messages, or the words of each state), the blinds (from tape k, shared first), the
-// commitments (sp_hyrax_commit_batch per segment: one launch, one copy, one wait and one normalisation for all states), the tables block, the cached
-// products (one sp_multiply_vec per state, queued back to back; sp_multiply_vec_chunked - one walk over A, B, C per chunk of vectors - on request: it
-// was measured and does not win, see the constants below), the scratch, one synchronise. State k is word for word the state
-// prep_prove_from makes of witness k with tape k: group sums as canonical affine points and exact field sums, so neither depends on how the work was
-// grouped. Still per state: the allocations and the lz_tables block (the tables are built lazily, behind a state's first prove).
+// ---- SpartanSNARK::prep_prove (src/spartan.rs:176-216) for `count` states of one key in one pass -------------------------------------------------------
+// ONE driver behind every witness source and every count. `fill_W` writes the witness segments into the zeroed tables W[0 .. count) (each segment at its
+// padded offset): machine words from the frontend (prep_prove, prep_prove_batch) or the SHA-256 witness kernel (prep_prove_sha256, prep_prove_sha256_batch:
+// one launch for all messages). Everything after it is the reference's prep_prove restated phase by phase over the batch: the blinds (from tape k, shared
+// first), the commitments (sp_hyrax_commit_batch per segment: one launch, one copy, one wait and one normalisation for all states), the tables block, the
+// cached products (one sp_multiply_vec per state, queued back to back; sp_multiply_vec_chunked - one walk over A, B, C per chunk of vectors - on request: it
+// was measured and does not win, see the constants below), the scratch, one synchronise. State k is word for word the state a batch of one makes of
+// witness k with tape k: group sums as canonical affine points and exact field sums, so neither depends on how the work was grouped. Still per state:
+// the allocations and the lz_tables block (the tables are built lazily, behind a state's first prove).
+// A batch of one takes the per-state calls: there is nothing to share. That is prep_prove and prep_prove_sha256: `who` = "prep_prove" names the single
+// entry points, whose errors pass as they are and whose SPARTAN_PREP_TRACE line starts "prep_prove:"; any other `who` ("prep_prove_batch") prefixes an
+// error with itself and the state at fault and traces as "prep_prove_batch(count):" - at count 1 as well.
 // flags: SS_PREP_PER_STATE_COMMIT keeps one sp_hyrax_commit per state and segment, SS_PREP_PER_STATE_MATVEC one sp_multiply_vec per state,
 // SS_PREP_CHUNKED_MATVEC takes sp_multiply_vec_chunked (same states; there so that one process can compare the paths; with both product flags set
-// SS_PREP_PER_STATE_MATVEC wins). A batch of one takes the
-// per-state calls: there is nothing to share.
+// SS_PREP_PER_STATE_MATVEC wins).
 // What the driver takes by default was measured (profiles/prep_prove_batch.md, config 2, one process, legs alternating):
 //   commit: sp_hyrax_commit_batch beats one sp_hyrax_commit per state at every K >= 2 measured (1.15 against 2.37 ms at K = 4, 4.42 against 9.46 at
 //     K = 16): PREP_BATCH_COMMIT_MIN = 2, there is no K at which the loop wins.
@@ -324,8 +199,9 @@ enum : unsigned { SS_PREP_PER_STATE_COMMIT = 1, SS_PREP_PER_STATE_MATVEC = 2, SS
 static constexpr size_t PREP_BATCH_COMMIT_MIN = 2;
 static constexpr bool PREP_CHUNKED_MATVEC_DEFAULT = false;
 static std::vector<SpartanPrepSNARK*> prep_prove_batch_from(const SpartanProverKey& pk, size_t count, bool is_small, Tape* tapes, unsigned flags,
-                                                            const std::function<void(sp_table* const* W)>& fill_W, double* phase_ms) {
+                                                            const std::function<void(sp_table* const* W)>& fill_W, double* phase_ms, const char* who) {
   const sp_dims& d = pk.dims;
+  const bool single = !strcmp(who, "prep_prove");
   std::vector<std::unique_ptr<SpartanPrepSNARK>> st(count);
   size_t at = (size_t)-1;  // the state a per-state step is working on (names the state in an error)
   try {
@@ -339,14 +215,20 @@ static std::vector<SpartanPrepSNARK*> prep_prove_batch_from(const SpartanProverK
       ms[k] += t - t_last;
       t_last = t;
     };
-    unsigned state_flags = 0;
-    {
-      const char* e = getenv("SPARTAN_LZ_DIRECT");
-      if (e && e[0] == '1') state_flags |= FLAG_LZ_DIRECT;
-      e = getenv("SPARTAN_PREFIX_CACHE");
-      if (e && e[0] == '1') state_flags |= FLAG_PREFIX_CACHE;
-    }
-    // 1. witness
+    // the environment, read here and nowhere else in prep
+    const auto is = [](const char* e, char c) { return e && e[0] == c; };
+    const unsigned state_flags = (is(getenv("SPARTAN_LZ_DIRECT"), '1') ? FLAG_LZ_DIRECT : 0u) | (is(getenv("SPARTAN_PREFIX_CACHE"), '1') ? FLAG_PREFIX_CACHE : 0u);
+    // WHEN the FixedBaseMul tables of the committed rows are built (SPARTAN_PREP_TABLES): the build is ~3 ms of device work (profiles/r06_prep_prove.md) that
+    // pays for itself from the second prove on a state onwards (50-100 us a prove) and slows whatever proves beside it. "lazy" (default): queued behind the
+    // FIRST prove on the state - a state that is proven once (the reference's own use: prep_prove, prove, drop) never pays, the bench's repeated proves get
+    // them from the third on; "prep": queued here; "sync": built here and waited for (round 5); "off": never.
+    const char* tables_mode = getenv("SPARTAN_PREP_TABLES");
+    const bool trace = getenv("SPARTAN_PREP_TRACE") != nullptr;
+    const bool round0_products = !is(getenv("SPARTAN_ROUND0_PRODUCTS"), '0');  // "0": round 1 of the outer sum-check evaluates straight from Az, Bz, Cz (A/B)
+    // 1. witness: shared_witness / precommitted_witness (bellpepper/r1cs.rs:306-409), each segment at its padded offset. The rest segment is filled here as
+    // well: without verifier challenges it does not change between proves. Machine words go to the device as they are (8 bytes a value) and become
+    // Montgomery-form elements there: sp_table_write_u64 (the reference hands the same words to msm_small, hyrax_pc.rs:266-292, and never builds wide
+    // scalars for the commitment either).
     std::vector<sp_table*> Ws(count);
     for (at = 0; at < count; ++at) {
       st[at].reset(new SpartanPrepSNARK());
@@ -399,12 +281,12 @@ static std::vector<SpartanPrepSNARK*> prep_prove_batch_from(const SpartanProverK
         (seg == 0 ? st[k]->comm_shared_bytes : st[k]->comm_pre_bytes) = commitment_bytes(st[k]->comm_W_fixed.data() + first, rows);
     }
     phase(1);
-    // 4. tables (see prep_prove_from)
+    // 4. tables of the committed rows and h (SpartanPrepSNARK::lz_tables)
     for (at = 0; at < count; ++at) {
       SpartanPrepSNARK* ps = st[at].get();
       const size_t fixed = ps->comm_W_fixed.size(), rows_all = (M + CW - 1) / CW;
       if (!(ps->flags & FLAG_LZ_DIRECT) && d.num_rest_unpadded == 0 && d.num_challenges == 0 && fixed >= 1 && fixed + 1 <= 512 && rows_all > 1) {
-        const char* mode = getenv("SPARTAN_PREP_TABLES");
+        const char* mode = tables_mode;
         ps->lz_points.assign(ps->comm_W_fixed.begin(), ps->comm_W_fixed.end());
         ps->lz_points.push_back(pk.gens[CW]);  // h
         ps->lz_mode = !mode || !strcmp(mode, "lazy") ? 1 : (!strcmp(mode, "off") ? 0 : 2);
@@ -431,14 +313,13 @@ static std::vector<SpartanPrepSNARK*> prep_prove_batch_from(const SpartanProverK
       for (at = 0; at < count; ++at) ck(sp_multiply_vec(ctx, pk.S, st[at]->z, st[at]->caz, st[at]->cbz, st[at]->ccz), "multiply_vec_precommitted");
     }
     at = (size_t)-1;
-    if (getenv("SPARTAN_PREP_TRACE")) ck(sp_ctx_synchronize(ctx), "sync");
+    if (trace) ck(sp_ctx_synchronize(ctx), "sync");
     phase(3);
     // 6. scratch
-    const char* no_p0 = getenv("SPARTAN_ROUND0_PRODUCTS");
     for (at = 0; at < count; ++at) {
       SpartanPrepSNARK* ps = st[at].get();
       ck(sp_table_zeros(ctx, N, (size_t)-1, (size_t)-1, &ps->rx), "alloc rx");
-      if (N >= 2 && !(no_p0 && no_p0[0] == '0')) {
+      if (N >= 2 && round0_products) {
         ck(sp_table_zeros(ctx, N / 2, (size_t)-1, (size_t)-1, &ps->p0), "alloc round-0 products");
         ck(sp_table_zeros(ctx, N / 2, (size_t)-1, (size_t)-1, &ps->p1), "alloc round-0 products");
       }
@@ -451,15 +332,56 @@ static std::vector<SpartanPrepSNARK*> prep_prove_batch_from(const SpartanProverK
     for (size_t k = 0; k < count; ++k)
       for (int i = 0; i < 8; ++i) st[k]->prep_ms[i] = ms[i] / (double)count;
     if (phase_ms) memcpy(phase_ms, ms, sizeof ms);
-    if (getenv("SPARTAN_PREP_TRACE"))
-      fprintf(stderr, "prep_prove_batch(%zu): witness %.3f commit %.3f tables %.3f matvec %.3f scratch %.3f total %.3f ms\n", count, ms[0], ms[1], ms[2], ms[3], ms[4], ms[6]);
+    if (trace) {
+      const std::string name = single ? std::string(who) : std::string(who) + "(" + std::to_string(count) + ")";
+      fprintf(stderr, "%s: witness %.3f commit %.3f tables %.3f matvec %.3f scratch %.3f total %.3f ms\n", name.c_str(), ms[0], ms[1], ms[2], ms[3], ms[4], ms[6]);
+    }
   } catch (const Error& e) {
     // every state made so far goes with `st`
-    throw Error(e.code, "prep_prove_batch: " + (at == (size_t)-1 ? std::string() : "state " + std::to_string(at) + ": ") + e.what());
+    if (single) throw;
+    throw Error(e.code, std::string(who) + ": " + (at == (size_t)-1 ? std::string() : "state " + std::to_string(at) + ": ") + e.what());
   }
   std::vector<SpartanPrepSNARK*> out(count);
   for (size_t k = 0; k < count; ++k) out[k] = st[k].release();
   return out;
+}
+
+// the witness words of `count` states from the frontend: witnesses_u64[k] = shared | precommitted | rest, unpadded
+static void upload_witnesses(const SpartanProverKey& pk, sp_table* const* W, const uint64_t* const* witnesses_u64, size_t count) {
+  const sp_dims& d = pk.dims;
+  for (size_t k = 0; k < count; ++k) {
+    auto put = [&](size_t dst, size_t src, size_t cnt) { ck(sp_table_write_u64(pk.ctx, W[k], dst, witnesses_u64[k] + src, cnt), "upload W"); };
+    put(0, 0, d.num_shared_unpadded);
+    put(d.num_shared, d.num_shared_unpadded, d.num_precommitted_unpadded);
+    // (with verifier challenges the rest segment is synthesized inside every prove, after the challenges are drawn: bellpepper/r1cs.rs:443-461)
+    if (d.num_challenges == 0) put(d.num_shared + d.num_precommitted, d.num_shared_unpadded + d.num_precommitted_unpadded, d.num_rest_unpadded);
+  }
+}
+
+SpartanPrepSNARK* prep_prove(const SpartanProverKey& pk, const uint64_t* witness_u64, size_t n_witness, bool is_small, Tape& tape) {
+  const sp_dims& d = pk.dims;
+  if (n_witness != d.num_shared_unpadded + d.num_precommitted_unpadded + d.num_rest_unpadded) throw Error(SP_ERR_INVALID_WITNESS_LENGTH, "InvalidWitnessLength");
+  return prep_prove_batch_from(pk, 1, is_small, &tape, 0, [&](sp_table* const* W) { upload_witnesses(pk, W, &witness_u64, 1); }, nullptr, "prep_prove")[0];
+}
+
+// prep_prove for Sha256Circuit (benches/sha256_spartan.rs:78-136) with the witness generated on the device: the reference's prep_prove INCLUDES witness
+// synthesis (src/spartan.rs:176-216 -> precommitted_witness, bellpepper/r1cs.rs:359-409); here it is sp_sha256_witness on a plan made once per key.
+// The key is a sha256_spartan_circuit key (everything precommitted, 256 public digest bits) for the plan's message length; one key serves every message
+// of that length. out_publics: the 256 digest bits in the order the circuit allocates them (big-endian bit order), from the host's SHA-256.
+SpartanPrepSNARK* prep_prove_sha256(const SpartanProverKey& pk, const sp_sha256_plan* plan, const uint8_t* msg, size_t len, bool is_small, Tape& tape, uint64_t out_publics[256]) {
+  const sp_dims& d = pk.dims;
+  uint64_t info[5];
+  ck(sp_sha256_plan_info(plan, info), "plan info");
+  if (d.num_shared_unpadded != 0 || d.num_rest_unpadded != 0 || d.num_challenges != 0 || info[0] != d.num_precommitted_unpadded)
+    throw Error(SP_ERR_INVALID_WITNESS_LENGTH, "InvalidWitnessLength: the plan's variable count is not the key's");
+  if (len != info[3] || !info[4] || d.num_public != 256) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "the plan does not serve this message length / this key is not a SHA-256 digest circuit");
+  sp_ctx* ctx = pk.ctx;
+  uint8_t digest[32];
+  SpartanPrepSNARK* ps = prep_prove_batch_from(pk, 1, is_small, &tape, 0, [&](sp_table* const* W) {
+    ck(sp_sha256_witness(ctx, plan, msg, len, 1, W, d.num_shared, digest), "sha256 witness");
+  }, nullptr, "prep_prove")[0];
+  for (int i = 0; i < 256; ++i) out_publics[i] = (digest[i / 8] >> (7 - i % 8)) & 1u;
+  return ps;
 }
 
 std::vector<SpartanPrepSNARK*> prep_prove_batch(const SpartanProverKey& pk, const uint64_t* const* witnesses_u64, size_t n_witness, size_t count, bool is_small, Tape* tapes,
@@ -470,15 +392,7 @@ std::vector<SpartanPrepSNARK*> prep_prove_batch(const SpartanProverKey& pk, cons
   }
   if (n_witness != d.num_shared_unpadded + d.num_precommitted_unpadded + d.num_rest_unpadded)
     throw Error(SP_ERR_INVALID_WITNESS_LENGTH, "prep_prove_batch: state 0: InvalidWitnessLength");
-  sp_ctx* ctx = pk.ctx;
-  return prep_prove_batch_from(pk, count, is_small, tapes, flags, [&](sp_table* const* W) {
-    for (size_t k = 0; k < count; ++k) {
-      auto put = [&](size_t dst, size_t src, size_t cnt) { ck(sp_table_write_u64(ctx, W[k], dst, witnesses_u64[k] + src, cnt), "upload W"); };
-      put(0, 0, d.num_shared_unpadded);
-      put(d.num_shared, d.num_shared_unpadded, d.num_precommitted_unpadded);
-      if (d.num_challenges == 0) put(d.num_shared + d.num_precommitted, d.num_shared_unpadded + d.num_precommitted_unpadded, d.num_rest_unpadded);
-    }
-  }, phase_ms);
+  return prep_prove_batch_from(pk, count, is_small, tapes, flags, [&](sp_table* const* W) { upload_witnesses(pk, W, witnesses_u64, count); }, phase_ms, "prep_prove_batch");
 }
 
 std::vector<SpartanPrepSNARK*> prep_prove_sha256_batch(const SpartanProverKey& pk, const sp_sha256_plan* plan, const uint8_t* msgs, size_t len, size_t count, bool is_small,
@@ -494,17 +408,361 @@ std::vector<SpartanPrepSNARK*> prep_prove_sha256_batch(const SpartanProverKey& p
   std::vector<uint8_t> digests(32 * count);
   std::vector<SpartanPrepSNARK*> out = prep_prove_batch_from(pk, count, is_small, tapes, flags, [&](sp_table* const* W) {
     ck(sp_sha256_witness(ctx, plan, msgs, len, count, W, d.num_shared, digests.data()), "sha256 witness");
-  }, phase_ms);
+  }, phase_ms, "prep_prove_batch");
   for (size_t k = 0; k < count; ++k)
     for (int i = 0; i < 256; ++i) out_publics[256 * k + i] = (digests[32 * k + i / 8] >> (7 - i % 8)) & 1u;
   return out;
 }
 
 
+// ---- prove's helper jobs ---------------------------------------------------------------------------------------------------------------------------
+// What prove() hands to the two helper threads of its prep state (SpartanPrepSNARK::bg, bg2), as types of their own: each holds what its job reads and
+// writes, run() is the job. prove() constructs them on its stack, submits [&job] { job.run(); } and joins through the guards below on every exit path.
+
+// the transcript up to the rest commitment, as a state to adopt or clone (absorb_instance_prefix)
+static sp_transcript* instance_prefix(sp_ctx* ctx, const SpartanProverKey& pk, const SpartanPrepSNARK& ps, const fe_t* publics, size_t npub) {
+  Tr t0(ctx, "SpartanSNARK");
+  absorb_instance_prefix(t0, pk.vk_digest, publics, npub, ps.comm_shared_bytes, ps.comm_pre_bytes);
+  sp_transcript* t = t0.t;
+  t0.t = nullptr;
+  return t;
+}
+
+// ONE job for the second helper, submitted before anything else, carries the host chains nothing on the proving thread depends on until much later:
+//   (1) the transcript prefix (src/spartan.rs:226-236, bellpepper/r1cs.rs:422-427): new + vk + public_values + comm_W_shared + comm_W_precommitted -
+//       about 300 Keccak blocks at config 2, ~45 us. Re-hashed in every prove, as the reference does (FLAG_PREFIX_CACHE keeps the sponge state
+//       across proves instead). Needed when comm_W_rest is absorbed, i.e. after commit_zeros has come back from the device: `prefix_ready`.
+//   (2) the IPA mask d_vec (ipa.rs:139-145) and the blinds of delta and beta, which do not depend on the transcript: 2048 wide reductions from their
+//       tape position, ~70 us. Needed when delta's MSM is issued (a third of the way into the outer sum-check): `dvec_ready`.
+//   (3) the blind's term of comm_eval_W (src/spartan.rs:423-437): blind_eval_W is the next block of the tape, h_s * blind a host walk of 32 additions
+//       that otherwise stands between the inner sum-check's last round and the opening's transcript; with it h_s * r_beta, the blind's term of
+//       beta = <R, d> g_s + r_beta h_s (ipa.rs:148-149): `eval_W_term_ready`.
+// The first helper stays free for the opening's job, which is posted the moment comm_W is complete.
+struct PrefixJob {
+  sp_ctx* ctx;
+  SpartanPrepSNARK* ps;
+  const SpartanProverKey* pk;
+  const fe_t* publics;
+  size_t npub;
+  bool prefix_cached;
+  Tape peek;  // at d_vec: behind the rest-row blinds (drawn by then) and blind_eval_W (then d_vec, r_delta, r_beta)
+  fe_t* dvec;
+  size_t n_ipa;
+  fe_t blind_eval_W;  // peeked from its block of the tape
+  // what the job delivers
+  fe_t r_delta, r_beta, eval_W_term_blind;
+  aff_t eval_W_term, beta_term;  // h_s * blind_eval_W, h_s * r_beta (valid once eval_W_term_ready is set)
+  std::atomic<int> prefix_ready{0}, dvec_ready{0}, eval_W_term_ready{0};
+  void run() {
+    struct Flags {  // whatever happens in here, a waiter must not spin for ever (an exception resurfaces at the next wait())
+      std::atomic<int>*a, *b;
+      ~Flags() {
+        a->store(1, std::memory_order_release);
+        b->store(1, std::memory_order_release);
+      }
+    } flags{&prefix_ready, &dvec_ready};
+    if (!prefix_cached) {
+      sp_transcript_free(ps->tr_fresh);
+      ps->tr_fresh = nullptr;
+      ps->tr_fresh = instance_prefix(ctx, *pk, *ps, publics, npub);
+    }
+    prefix_ready.store(1, std::memory_order_release);
+    for (size_t i = 0; i < n_ipa; ++i) dvec[i] = peek.next();
+    r_delta = peek.next();  // ipa.rs:146: the blind of delta follows d_vec on the tape
+    r_beta = peek.next();   // then beta's
+    dvec_ready.store(1, std::memory_order_release);
+    // (both blind terms of the opening's one-value commitments: comm_eval_W above and beta = <R, d> g_s + r_beta h_s, ipa.rs:148-149)
+    aff_t two[2];
+    const fe_t bl[2] = {blind_eval_W, r_beta};
+    if (sp_fixed_base_mul_h(ctx, pk->ck_s, u64p(bl), 2, u64p(&two[0].x)) == SP_OK) {
+      eval_W_term = two[0];
+      eval_W_term_blind = blind_eval_W;
+      beta_term = two[1];
+      eval_W_term_ready.store(1, std::memory_order_release);
+    }
+  }
+};
+struct PrefixJoin {  // publics must outlive the job on every exit path
+  Background& b;
+  ~PrefixJoin() { b.wait_nothrow(); }
+};
+
+// The first helper's job, posted the moment comm_W is complete: comm_W's transcript encoding (64 B per row, Montgomery -> canonical) and the Keccak blocks
+// of absorb("poly_com", ..), the first absorb after the inner sum-check's last squeeze (hyrax_pc.rs:387-400). With `ahead` the same job then issues
+// delta's MSM and computes comm_LZ = sum_i L[i] comm_W[i] (= commit(L . W; <L, r_W>), hyrax_pc.rs:430-455, by the homomorphism of the commitment) as
+// soon as the inner sum-check has bound the row variables: the MSM runs under the remaining rounds instead of after them.
+struct LzAhead {
+  std::atomic<int> state{0};  // 0: row challenges not drawn yet, 1: drawn, 2: abandoned
+  std::atomic<int> rows_known{0};  // how many of them r[] holds so far (the helper expands eq(r, .) a level per challenge, as they arrive)
+  size_t nvr = 0;
+  fe_t r[24];
+  sp_msm_job* job = nullptr;
+  sp_vec_job* vec = nullptr;
+  fe_t r_LZ;
+  std::atomic<int> delta_state{0};  // 0: delta's MSM not issued yet, 1: issued, 2: abandoned
+  sp_msm_job* delta_job = nullptr;
+  fe_t r_delta;
+  aff_t delta;
+  bool delta_done = false;
+  std::atomic<int> early_done{0};  // poly_com prepared and delta finished: what the PCS phase needs first (1 = done, 2 = gave up)
+  aff_t comm_LZ;                   // the tables path (SpartanPrepSNARK::lz_tables): the helper delivers comm_LZ itself
+  bool have_comm_LZ = false;
+  // a helper that may not spin sleeps on this pair; the owner notifies after each state change (a notify without a sleeper is a user-space check)
+  std::mutex mu;
+  std::condition_variable cv;
+  void publish(std::atomic<int>& flag, int v) {
+    flag.store(v, std::memory_order_release);
+    cv.notify_one();
+  }
+  // what the job reads: comm_W and its blinds, the key, the tables of the fixed rows + h (non-null: usable, every other row of comm_W is h * blind,
+  // commit_zeros), d_vec and r_delta as the second helper's job delivers them (*dvr set)
+  sp_ctx* ctx = nullptr;
+  const aff_t* rows = nullptr;
+  size_t nrows = 0;
+  SpartanPrepSNARK* psp = nullptr;
+  const fe_t* blinds = nullptr;
+  bool ahead = false;  // false: the job ends with poly_com
+  const sp_ck* key = nullptr;
+  size_t cols = 0;
+  const sp_fbtables* tabs = nullptr;
+  size_t nfixed = 0;
+  const fe_t* dv = nullptr;
+  size_t dn = 0;
+  const std::atomic<int>* dvr = nullptr;
+  const fe_t* rda = nullptr;
+  void run() {
+    const std::vector<uint8_t> b = commitment_bytes(rows, nrows);
+    ck(sp_transcript_preabsorb((const uint8_t*)"poly_com", 8, b.data(), b.size(), &psp->poly_com), "poly_com (prepare)");
+    if (!ahead) return;
+    ck(sp_ctx_bind_thread(ctx), "helper thread: device");  // a new thread starts on device 0; the context may live on another GPU
+    ck(sp_points_upload(ctx, u64p(&rows[0].x), nrows, &psp->comm_pts), "comm_W (upload)");
+    const auto t0 = std::chrono::steady_clock::now();
+    // sleeps until the owner publishes the state (helper_may_spin above)
+    auto wait_for = [&](std::atomic<int>& flag) {
+      int st;
+      while ((st = flag.load(std::memory_order_acquire)) == 0) {
+        if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(20)) return 2;  // the prover never got there
+        if (!helper_may_spin()) {
+          std::unique_lock<std::mutex> lk(mu);  // woken by publish(); the timeout covers a notify that raced the predicate
+          cv.wait_for(lk, std::chrono::microseconds(100), [&] { return flag.load(std::memory_order_acquire) != 0; });
+        } else {
+          sp_relax();
+        }
+      }
+      return st;
+    };
+    // delta (ipa.rs:147): issued from here once the outer sum-check has left its streaming rounds (the owner publishes delta_state from its
+    // challenge observer): the MSM then runs under the resident tail kernel, which leaves the device idle, instead of beside the first rounds
+    // of the inner sum-check (measured there: k_eval_quad_stream_lowhi 32 us against 18 us alone, profiles/r04_kernel_stats.md)
+    if (wait_for(delta_state) != 1) return;
+    while (dvr->load(std::memory_order_acquire) == 0) sp_relax();  // d_vec, r_delta (the second helper's job, posted first thing in the prove: long done)
+    r_delta = *rda;
+    ck(sp_msm_ck_begin(ctx, key, u64p(dv), dn, &delta_job), "delta (begin)");
+    {
+      sp_msm_job* j = delta_job;
+      delta_job = nullptr;  // finish() consumes the job whatever it returns
+      ck(sp_msm_ck_finish(ctx, key, j, u64p(&r_delta), u64p(&delta.x)), "delta (finish)");
+    }
+    delta_done = true;
+    early_done.store(1, std::memory_order_release);
+    if (tabs && nvr >= 1 && nrows == ((size_t)1 << nvr)) {
+      // comm_LZ = sum_{fixed rows} L_i comm_W[i] + (sum_{zero rows} L_i blind_i) h, L = eq(r_rows, .): one multi_mul over the prepared tables. Its ~100 us
+      // of dependent point additions are the critical path of the opening, so everything in front of the launch is kept off the last row challenge:
+      // eq(r, .) is expanded a level per challenge as the inner sum-check draws them (the observer counts them in rows_known), and what the last
+      // challenge r leaves to do is the last level (2^(nvr-1) products) and h's scalar, (1 - r) S0 + r S1 with S_c = sum over the zero rows of parity c
+      // of P[i >> 1] blind_i taken one level up; <L, r_W> for z_delta follows the launch. (All of it at once behind the last challenge was ~40 us.)
+      std::vector<fe_t> P(1, fe_one<S>());
+      for (size_t known = 0; known + 1 < nvr; ++known) {
+        const auto w0 = std::chrono::steady_clock::now();
+        while ((size_t)rows_known.load(std::memory_order_acquire) <= known) {
+          if (state.load(std::memory_order_acquire) == 2 || std::chrono::steady_clock::now() - w0 > std::chrono::seconds(20)) return;
+          if (!helper_may_spin()) {
+            std::unique_lock<std::mutex> lk(mu);
+            cv.wait_for(lk, std::chrono::microseconds(50), [&] { return (size_t)rows_known.load(std::memory_order_acquire) > known; });
+          } else {
+            sp_relax();
+          }
+        }
+        const fe_t rk = r[known];
+        std::vector<fe_t> Q(2 * P.size());
+        for (size_t i = 0; i < P.size(); ++i) {  // the new variable is the index LSB (eq.rs:66-76)
+          const fe_t hi = fe_mul<S>(P[i], rk);
+          Q[2 * i + 1] = hi;
+          Q[2 * i] = fe_sub<S>(P[i], hi);
+        }
+        P.swap(Q);
+      }
+      fe_t S0 = fe_zero(), S1 = fe_zero();
+      for (size_t i = nfixed; i < nrows; ++i) {
+        const fe_t t = fe_mul<S>(P[i >> 1], blinds[i]);
+        if (i & 1) S1 = fe_add<S>(S1, t);
+        else S0 = fe_add<S>(S0, t);
+      }
+      if (wait_for(state) != 1) return;
+      const fe_t rl = r[nvr - 1];
+      bool launched = false;
+      if (nfixed + 1 < 1024) {  // the last level on the device (k_multi_mul_coop EXPAND): the launch goes out before this thread forms it for r_LZ
+        const fe_t s01[2] = {S0, S1};
+        ck(sp_fbtables_multi_mul_begin_eq(ctx, tabs, u64p(P.data()), nfixed, u64p(s01), u64p(&rl)), "comm_LZ (begin)");
+        ck(sp_rowmat_vec_eq_begin_with(ctx, psp->W, u64p(r), nvr, cols, dn == cols ? u64p(dv) : nullptr, &vec), "bind_with_delayed (begin)");
+        launched = true;
+      }
+      std::vector<fe_t> sc(nfixed + 1);
+      for (size_t h = 0; h < P.size(); ++h) {
+        const fe_t hi = fe_mul<S>(P[h], rl), lo = fe_sub<S>(P[h], hi);
+        if (2 * h < nfixed) sc[2 * h] = lo;
+        if (2 * h + 1 < nfixed) sc[2 * h + 1] = hi;
+      }
+      const fe_t hs = fe_add<S>(S0, fe_mul<S>(rl, fe_sub<S>(S1, S0)));
+      sc[nfixed] = hs;
+      if (!launched) {
+        ck(sp_fbtables_multi_mul_begin(ctx, tabs, u64p(sc.data()), sc.size()), "comm_LZ (begin)");
+        ck(sp_rowmat_vec_eq_begin_with(ctx, psp->W, u64p(r), nvr, cols, dn == cols ? u64p(dv) : nullptr, &vec), "bind_with_delayed (begin)");
+      }
+      fe_t acc = hs;  // r_LZ = <L, r_W> (hyrax_pc.rs:446-455)
+      for (size_t i = 0; i < nfixed; ++i) acc = fe_add<S>(acc, fe_mul<S>(sc[i], blinds[i]));
+      r_LZ = acc;
+      ck(sp_fbtables_multi_mul_finish(ctx, u64p(&comm_LZ.x)), "comm_LZ (finish)");
+      have_comm_LZ = true;
+      return;
+    }
+    if (wait_for(state) != 1) return;
+    const size_t hb = nvr / 2, lb = nvr - hb;
+    ck(sp_msm_eq_begin(ctx, psp->comm_pts, u64p(r), nvr, &job), "comm_LZ (begin)");
+    ck(sp_rowmat_vec_eq_begin_with(ctx, psp->W, u64p(r), nvr, cols, dn == cols ? u64p(dv) : nullptr, &vec), "bind_with_delayed (begin)");
+    // r_LZ = <L, r_W> with L = eq(r) = left (x) right: 2^nvr + 2^(nvr/2) products instead of 2 * 2^nvr
+    const std::vector<fe_t> left = eq_evals_host(r, hb), right = eq_evals_host(r + hb, lb);
+    fe_t acc = fe_zero();
+    for (size_t a = 0; a < left.size(); ++a) {
+      fe_t inner = fe_zero();
+      for (size_t c2 = 0; c2 < right.size(); ++c2) inner = fe_add<S>(inner, fe_mul<S>(right[c2], blinds[a * right.size() + c2]));
+      acc = fe_add<S>(acc, fe_mul<S>(left[a], inner));
+    }
+    r_LZ = acc;
+  }
+};
+struct BgJoin {  // comm_W, r_W and the LzAhead must outlive the job on every exit path
+  Background& b;
+  std::atomic<int>&st, &st2;
+  sp_ctx* ctx;
+  sp_msm_job *&j1, *&j2;
+  sp_vec_job*& v1;
+  ~BgJoin() {
+    int zero = 0;
+    st2.compare_exchange_strong(zero, 2);
+    zero = 0;
+    st.compare_exchange_strong(zero, 2);
+    b.wait_nothrow();
+    // an abandoned prove (error exit) still owns whatever the helper had started: finish the jobs to release them
+    uint64_t sink[8];
+    if (j1) sp_msm_job_finish(ctx, j1, sink);
+    if (j2) sp_msm_job_finish(ctx, j2, sink);
+    if (v1) {
+      std::vector<uint64_t> big(4 * 2048);
+      sp_rowmat_vec_eq_finish(ctx, v1, big.data());
+    }
+    j1 = j2 = nullptr;
+    v1 = nullptr;
+  }
+};
+// evals_rx started four rounds before r_x is complete (sp_eq_table_begin builds the half tables of the first ell - 4 coordinates on a stream of
+// its own; sp_eq_table_finish behind the last challenge is then one launch): the outer sum-check's challenge observer
+struct EqObs {
+  sp_ctx* ctx;
+  size_t ell;
+  fe_t r[24];
+  LzAhead* lz;  // non-null: delta's MSM is the helper's to issue (see there)
+  int rc = 0;
+  bool begun = false;
+  static void fn(void* u, size_t round, const uint64_t r[4]) {
+    EqObs* o = (EqObs*)u;
+    if (o->lz && round + delta_rounds_before_end() == o->ell) o->lz->publish(o->lz->delta_state, 1);
+    if (round + 4 >= o->ell) return;  // the last four coordinates (the rounds the host runs itself after the hand-over) are applied by sp_eq_table_finish
+    memcpy(&o->r[round], r, 32);
+    if (round + 5 == o->ell) {
+      o->rc = sp_eq_table_begin(o->ctx, u64p(o->r), o->ell - 4, o->ell);
+      o->begun = o->rc == 0;
+    }
+  }
+};
+
+// <R, d> (ipa.rs:148) with R = eq(point[nvr..]) = left (x) right: the partial sums T[b] = sum_a left[a] d[a |right| + b] need only `left`, whose
+// variables are bound hb rounds after the row variables - the second helper computes them under the remaining rounds and the prover finishes with
+// |right| products instead of |R| + |left| after the last round
+struct IpAhead {
+  size_t first = 0, hb = 0, nright = 0;  // left = eq(r_y[first .. first + hb))
+  fe_t left_r[16], right_r[16];
+  std::vector<fe_t> T;
+  bool submitted = false;
+  // ... and once the last challenge is drawn the same job finishes <R, d> and beta = <R, d> ck_c + r_beta h_c (ipa.rs:148-149) beside the prover's
+  // own work on eval_W; it waits for that challenge with a short bounded spin
+  std::atomic<int> right_ready{0};
+  size_t nright_vars = 0, last_round = 0;
+  fe_t r_beta, ip;
+  aff_t beta;
+  bool beta_ready = false;
+  sp_ctx* ctx = nullptr;
+  const sp_ck* ck_s = nullptr;
+  const aff_t* beta_term = nullptr;           // h_s * r_beta from the first helper job ...
+  const std::atomic<int>* term_ready = nullptr;  // ... valid when this is set
+  const fe_t* dvec = nullptr;
+  void run() {
+    const std::vector<fe_t> left = eq_evals_host(left_r, hb);
+    T.assign(nright, fe_zero());
+    for (size_t a = 0; a < left.size(); ++a)
+      for (size_t b = 0; b < nright; ++b) T[b] = fe_add<S>(T[b], fe_mul<S>(left[a], dvec[a * nright + b]));
+    const auto t0 = std::chrono::steady_clock::now();
+    while (right_ready.load(std::memory_order_acquire) == 0) {
+      if (std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(150)) return;  // (the prover finishes <R, d> and beta itself; a helper does not sit on a CPU of the quota)
+      sp_relax();
+    }
+    const std::vector<fe_t> right = eq_evals_host(right_r, nright_vars);
+    fe_t acc = fe_zero();
+    for (size_t b = 0; b < right.size(); ++b) acc = fe_add<S>(acc, fe_mul<S>(right[b], T[b]));
+    ip = acc;
+    if (term_ready->load(std::memory_order_acquire)) ck(sp_hyrax_commit_small_with_term(ctx, ck_s, u64p(&ip), 1, u64p(&beta_term->x), u64p(&beta.x)), "beta");
+    else ck(sp_hyrax_commit_small(ctx, ck_s, u64p(&ip), 1, u64p(&r_beta), u64p(&beta.x)), "beta");
+    beta_ready = true;
+  }
+};
+// the inner sum-check's challenge observer: r_y[0] selects W against (1, X); r_y[1 ..= nvr] are the row variables of W (MSB first): once they are drawn
+// the first helper can start comm_LZ; the column variables go to the IpAhead, whose job is posted when `left` is complete
+struct Obs {
+  LzAhead* lz;
+  bool on;
+  IpAhead* ipa;
+  Background* bg2;
+  static void fn(void* u, size_t round, const uint64_t r[4]) {
+    Obs* o = (Obs*)u;
+    if (!o->on || round == 0) return;
+    if (round <= o->lz->nvr) {
+      memcpy(&o->lz->r[round - 1], r, 32);
+      o->lz->rows_known.store((int)round, std::memory_order_release);
+      if (round == o->lz->nvr) o->lz->publish(o->lz->state, 1);
+      return;
+    }
+    IpAhead* ip = o->ipa;
+    if (!ip->hb || round < ip->first) return;
+    if (round >= ip->first + ip->hb) {
+      memcpy(&ip->right_r[round - ip->first - ip->hb], r, 32);
+      if (round == ip->last_round) ip->right_ready.store(1, std::memory_order_release);
+      return;
+    }
+    memcpy(&ip->left_r[round - ip->first], r, 32);
+    if (round + 1 == ip->first + ip->hb) {
+      o->bg2->submit([ip] { ip->run(); });
+      ip->submitted = true;
+    }
+  }
+};
+struct IpJoin {  // the IpAhead and dvec outlive the job on every exit path
+  Background& b;
+  ~IpJoin() { b.wait_nothrow(); }
+};
+
 // SpartanSNARK::prove (src/spartan.rs:219-466)
 // `synth`: circuit.synthesize(.., Some(&challenges)) for circuits with verifier challenges (bellpepper/r1cs.rs:443-461): receives the challenges and
 // writes the num_rest_unpadded values of the rest segment (Montgomery limbs); non-zero return = SynthesisError
-typedef int (*ss_rest_hook)(void* user, const uint64_t* challenges, size_t num_challenges, uint64_t* out_rest);
 ProofBuf prove_reference_order(const SpartanProverKey& pk, SpartanPrepSNARK& ps, const uint64_t* publics_u64, size_t npub, Tape& tape, PhaseTimes* pt, ss_rest_hook synth,
                                       void* synth_user);
 ProofBuf prove(const SpartanProverKey& pk, SpartanPrepSNARK& ps, const uint64_t* publics_u64, size_t npub, Tape& tape, PhaseTimes* pt, ss_rest_hook synth = nullptr,
@@ -532,104 +790,28 @@ ProofBuf prove(const SpartanProverKey& pk, SpartanPrepSNARK& ps, const uint64_t*
   for (auto& b : r_W_rest) b = tape.next();
   lap("rest_blinds");
   sp_fb_job* rest_job = nullptr;
-  struct FbJobGuard {  // an error exit between begin and finish must not leave the context's one asynchronous fixed-base job outstanding
-    sp_ctx* ctx;
-    sp_fb_job*& job;
-    size_t n;
-    ~FbJobGuard() {
-      if (job) {
-        std::vector<uint64_t> sink(8 * n + 8);
-        (void)sp_fixed_base_mul_h_finish(ctx, job, sink.data());
-        job = nullptr;
-      }
-    }
-  } rest_job_guard{ctx, rest_job, rows_rest};
+  FbJobGuard rest_job_guard{ctx, rest_job, rows_rest};
   if (rows_rest && d.num_rest_unpadded == 0) ck(sp_fixed_base_mul_h_begin(ctx, pk.ck, u64p(r_W_rest.data()), rows_rest, &rest_job), "commit_zeros (begin)");
   lap("commit_zeros_begin");
-  std::vector<fe_t> publics(npub);
-  for (size_t i = 0; i < npub; ++i) publics[i] = fe_from_u64<S>(publics_u64[i]);
+  const std::vector<fe_t> publics = publics_from_u64(publics_u64, npub);
   lap("publics");
 
-  // ONE job for the second helper, submitted before anything else, carries the two host chains nothing on this thread depends on until much later:
-  //   (1) the transcript prefix (src/spartan.rs:226-236, bellpepper/r1cs.rs:422-427): new + vk + public_values + comm_W_shared + comm_W_precommitted -
-  //       about 300 Keccak blocks at config 2, ~45 us. Re-hashed in every prove, as the reference does (FLAG_PREFIX_CACHE keeps the sponge state
-  //       across proves instead). Needed when comm_W_rest is absorbed, i.e. after commit_zeros has come back from the device: `prefix_ready`.
-  //   (2) the IPA mask d_vec (ipa.rs:139-145) and the blinds of delta and beta, which do not depend on the transcript: 2048 wide reductions from their
-  //       tape position, ~70 us. Needed when delta's MSM is issued (a third of the way into the outer sum-check): `dvec_ready`.
-  // The first helper stays free for the opening's job, which is posted the moment comm_W is complete.
+  // the second helper's job (PrefixJob): the transcript prefix, d_vec and the blinds, the two blind terms
   const size_t n_ipa = M < W_ ? M : W_;
   const std::unique_ptr<fe_t[]> dvec_store(new fe_t[n_ipa]);  // (not value-initialised: the helper's draw writes every element; a zeroed vector was 12 us here)
   fe_t* const dvec = dvec_store.get();
-  fe_t r_delta_ahead, r_beta_ahead, eval_W_term_blind;
-  aff_t eval_W_term, beta_term;  // h_s * blind_eval_W, h_s * r_beta (valid once eval_W_term_ready is set)
-  std::atomic<int> prefix_ready{0}, dvec_ready{0}, eval_W_term_ready{0};
   const bool prefix_cached = (ps.flags & FLAG_PREFIX_CACHE) != 0;
   if (prefix_cached) {
     if (!ps.tr_prefix) {
-      Tr t0(ctx, "SpartanSNARK");
-      t0.absorb("vk", pk.vk_digest, 32);
-      t0.absorb_scalars("public_values", publics.data(), npub);
-      if (ps.rows_shared) t0.absorb("comm_W_shared", ps.comm_shared_bytes.data(), ps.comm_shared_bytes.size());
-      if (ps.rows_precommitted) t0.absorb("comm_W_precommitted", ps.comm_pre_bytes.data(), ps.comm_pre_bytes.size());
-      ps.tr_prefix = t0.t;
-      t0.t = nullptr;
+      ps.tr_prefix = instance_prefix(ctx, pk, ps, publics.data(), npub);
       ps.tr_publics = publics;
     } else if (ps.tr_publics.size() != publics.size() || memcmp(ps.tr_publics.data(), publics.data(), publics.size() * sizeof(fe_t)) != 0) {
       throw Error(SP_ERR_INTERNAL, "public values changed between proves on one prep state");
     }
   }
-  {
-    SpartanPrepSNARK* psp = &ps;
-    const SpartanProverKey* pkp = &pk;
-    const fe_t* pub = publics.data();
-    // tape order: the rest-row blinds (drawn below), blind_eval_W, then d_vec, r_delta, r_beta
-    Tape peek{tape.bytes, tape.blocks, tape.pos + 1};  // (the rest-row blinds have been drawn above)
-    fe_t* dv = dvec;
-    const size_t dn = n_ipa;
-    fe_t *rd = &r_delta_ahead, *rb = &r_beta_ahead;
-    std::atomic<int>*pr = &prefix_ready, *dr = &dvec_ready;
-    // (3) the blind's term of comm_eval_W (src/spartan.rs:423-437): blind_eval_W is the next block of the tape, h_s * blind a host walk of 32 additions
-    //     that otherwise stands between the inner sum-check's last round and the opening's transcript
-    const fe_t bew = fe_from_uniform<S>(tape.bytes + 64 * (tape.pos < tape.blocks ? tape.pos : 0));
-    aff_t* ewt = &eval_W_term;
-    fe_t* ewb = &eval_W_term_blind;
-    std::atomic<int>* ewr = &eval_W_term_ready;
-    aff_t* btt = &beta_term;
-    ps.bg2.submit([ctx, psp, pkp, pub, npub, prefix_cached, peek, dv, dn, rd, rb, pr, dr, bew, ewt, ewb, ewr, btt]() mutable {
-      struct Flags {  // whatever happens in here, a waiter must not spin for ever (an exception resurfaces at the next wait())
-        std::atomic<int>*a, *b;
-        ~Flags() {
-          a->store(1, std::memory_order_release);
-          b->store(1, std::memory_order_release);
-        }
-      } flags{pr, dr};
-      if (!prefix_cached) {
-        sp_transcript_free(psp->tr_fresh);
-        psp->tr_fresh = nullptr;
-        Tr t0(ctx, "SpartanSNARK");
-        t0.absorb("vk", pkp->vk_digest, 32);
-        t0.absorb_scalars("public_values", pub, npub);
-        if (psp->rows_shared) t0.absorb("comm_W_shared", psp->comm_shared_bytes.data(), psp->comm_shared_bytes.size());
-        if (psp->rows_precommitted) t0.absorb("comm_W_precommitted", psp->comm_pre_bytes.data(), psp->comm_pre_bytes.size());
-        psp->tr_fresh = t0.t;
-        t0.t = nullptr;
-      }
-      pr->store(1, std::memory_order_release);
-      for (size_t i = 0; i < dn; ++i) dv[i] = peek.next();
-      *rd = peek.next();  // ipa.rs:146: the blind of delta follows d_vec on the tape
-      *rb = peek.next();  // then beta's
-      dr->store(1, std::memory_order_release);
-      // (both blind terms of the opening's one-value commitments: comm_eval_W above and beta = <R, d> g_s + r_beta h_s, ipa.rs:148-149)
-      aff_t two[2];
-      const fe_t bl[2] = {bew, *rb};
-      if (sp_fixed_base_mul_h(ctx, pkp->ck_s, u64p(bl), 2, u64p(&two[0].x)) == SP_OK) {
-        *ewt = two[0];
-        *ewb = bew;
-        *btt = two[1];
-        ewr->store(1, std::memory_order_release);
-      }
-    });
-  }
+  PrefixJob pre{ctx, &ps, &pk, publics.data(), npub, prefix_cached, Tape{tape.bytes, tape.blocks, tape.pos + 1}, dvec, n_ipa,
+                fe_from_uniform<S>(tape.bytes + 64 * (tape.pos < tape.blocks ? tape.pos : 0))};
+  ps.bg2.submit([&pre] { pre.run(); });
   lap("helper_submit");
   // a flag the second helper's job raises; if the helper has not even begun the job 30 us after it was posted, the job runs here (Background::try_steal)
   auto await_flag = [&ps](std::atomic<int>& flag) {
@@ -638,17 +820,14 @@ ProofBuf prove(const SpartanProverKey& pk, SpartanPrepSNARK& ps, const uint64_t*
       sp_relax();
     }
   };
-  struct PrefixJoin {  // publics must outlive the job on every exit path
-    Background& b;
-    ~PrefixJoin() { b.wait_nothrow(); }
-  } prefix_join{ps.bg2};
+  PrefixJoin prefix_join{ps.bg2};
   lap("transcript_prefix");
   Tr tr(nullptr, Tr::Adopt{});
   auto acquire_transcript = [&] {
     if (tr.t) return;
     if (prefix_cached) ck(sp_transcript_clone(ps.tr_prefix, &tr.t), "transcript_clone");
     else {
-      await_flag(prefix_ready);
+      await_flag(pre.prefix_ready);
       tr.t = ps.tr_fresh;
       ps.tr_fresh = nullptr;
       if (!tr.t) {
@@ -659,13 +838,11 @@ ProofBuf prove(const SpartanProverKey& pk, SpartanPrepSNARK& ps, const uint64_t*
   };
   // verifier challenges (bellpepper/r1cs.rs:429-431) and the rest of the witness that depends on them (:443-461): squeezed right after the
   // precommitted commitment, before anything that needs z
-  std::vector<fe_t> challenges(d.num_challenges);
+  std::vector<fe_t> challenges;
   if (d.num_challenges) {
-    if (!synth) throw Error(SP_ERR_INTERNAL, "a circuit with verifier challenges needs its synthesize callback");
     acquire_transcript();
-    for (auto& c : challenges) c = tr.squeeze("challenge");
-    std::vector<fe_t> rest(d.num_rest_unpadded + 1);
-    if (synth(synth_user, u64p(challenges.data()), challenges.size(), u64p(rest.data())) != 0) throw Error(SP_ERR_INTERNAL, "SynthesisError: the circuit's synthesize callback failed");
+    challenges = squeeze_challenges(tr, d.num_challenges);
+    const std::vector<fe_t> rest = synthesize_rest(synth, synth_user, u64p(challenges.data()), challenges.size(), d.num_rest_unpadded);
     if (d.num_rest_unpadded) ck(sp_table_write(ctx, ps.W, d.num_shared + d.num_precommitted, u64p(rest.data()), d.num_rest_unpadded), "W rest");
   }
 
@@ -678,10 +855,7 @@ ProofBuf prove(const SpartanProverKey& pk, SpartanPrepSNARK& ps, const uint64_t*
   const size_t z_fixed = d.num_rest_unpadded ? d.num_shared + d.num_precommitted : M;
   if (M > z_fixed) ck(sp_table_copy(ctx, ps.z, z_fixed, ps.W, z_fixed, M - z_fixed), "z <- W rest");
   {
-    std::vector<fe_t> tail(pk.num_extra);
-    tail[0] = fe_one<S>();
-    std::copy(publics.begin(), publics.end(), tail.begin() + 1);
-    std::copy(challenges.begin(), challenges.end(), tail.begin() + 1 + npub);
+    const std::vector<fe_t> tail = z_tail(pk.num_extra, publics, challenges);
     if (tail.size() <= 2048) ck(sp_table_write_async(ctx, ps.z, M, u64p(tail.data()), tail.size()), "z tail");  // no synchronisation in front of the matrix-vector product
     else ck(sp_table_write(ctx, ps.z, M, u64p(tail.data()), tail.size()), "z tail");
   }
@@ -708,209 +882,42 @@ ProofBuf prove(const SpartanProverKey& pk, SpartanPrepSNARK& ps, const uint64_t*
     rest_job = nullptr;  // finish() consumes the job whatever it returns
     ck(sp_fixed_base_mul_h_finish(ctx, j, u64p(&comm_W[rows_pre].x)), "commit_zeros (finish)");
   }
-  else if (rows_rest)
-    ck(sp_hyrax_commit(ctx, pk.ck, ps.W, d.num_shared + d.num_precommitted, d.num_rest, u64p(r_W_rest.data()), ps.is_small ? 1 : 0, u64p(&comm_W[rows_pre].x)),
-       "commit rest");
+  else if (rows_rest) commit_rest_values(ctx, pk.ck, ps.W, d, ps.is_small, r_W_rest.data(), comm_W.data() + rows_pre);
   lap("commit_zeros_finish");
   acquire_transcript();
   lap("prefix_join");
-  {
-    std::vector<uint8_t> b = commitment_bytes(comm_W.data() + rows_pre, rows_rest);
-    tr.absorb("comm_W_rest", b.data(), b.size());
-  }
+  absorb_comm_W_rest(tr, comm_W.data() + rows_pre, rows_rest);
   lap("absorb_comm_W_rest");
-  std::vector<fe_t> r_W = ps.r_W_fixed;  // combine_blinds (bellpepper/r1cs.rs:515-524)
-  r_W.insert(r_W.end(), r_W_rest.begin(), r_W_rest.end());
-  // comm_W is complete: its transcript encoding (64 B per row, Montgomery -> canonical) and the Keccak blocks of absorb("poly_com", ..), the
-  // first absorb after the inner sum-check's last squeeze (hyrax_pc.rs:387-400), are computed on the helper thread from here on
+  const std::vector<fe_t> r_W = combine_blinds(ps.r_W_fixed, r_W_rest);
+  // comm_W is complete: the first helper's job (LzAhead) from here on
   ps.bg.wait();  // (idle: nothing has been posted to the first helper in this prove yet)
   sp_absorb_state_free(ps.poly_com);
   ps.poly_com = nullptr;
-  // The same helper then computes comm_LZ = sum_i L[i] comm_W[i] (= commit(L . W; <L, r_W>), hyrax_pc.rs:430-455, by the homomorphism of the
-  // commitment) as soon as the inner sum-check has bound the row variables: the MSM runs under the remaining rounds instead of after them.
   const size_t lz_rows = (M + W_ - 1) / W_, lz_nvr = log2_ceil(lz_rows);
   const bool lz_direct = (ps.flags & FLAG_LZ_DIRECT) != 0;  // the reference's own order (bind W with L first, then the MSM over the key)
-  struct LzAhead {
-    std::atomic<int> state{0};  // 0: row challenges not drawn yet, 1: drawn, 2: abandoned
-    std::atomic<int> rows_known{0};  // how many of them r[] holds so far (the helper expands eq(r, .) a level per challenge, as they arrive)
-    size_t nvr = 0;
-    fe_t r[24];
-    sp_msm_job* job = nullptr;
-    sp_vec_job* vec = nullptr;
-    fe_t r_LZ;
-    std::atomic<int> delta_state{0};  // 0: delta's MSM not issued yet, 1: issued, 2: abandoned
-    sp_msm_job* delta_job = nullptr;
-    fe_t r_delta;
-    aff_t delta;
-    bool delta_done = false;
-    std::atomic<int> early_done{0};  // poly_com prepared and delta finished: what the PCS phase needs first (1 = done, 2 = gave up)
-    aff_t comm_LZ;                   // the tables path (SpartanPrepSNARK::lz_tables): the helper delivers comm_LZ itself
-    bool have_comm_LZ = false;
-    // a helper that may not spin sleeps on this pair; the owner notifies after each state change (a notify without a sleeper is a user-space check)
-    std::mutex mu;
-    std::condition_variable cv;
-    void publish(std::atomic<int>& flag, int v) {
-      flag.store(v, std::memory_order_release);
-      cv.notify_one();
-    }
-  } lz;
+  LzAhead lz;
   // (lz.r_delta is set by the opening's job once d_vec and the blinds are drawn: dvec_ready)
   lz.nvr = lz_nvr;
   const bool lz_ahead = !lz_direct && lz_nvr > 0 && lz_nvr <= 20 && comm_W.size() == ((size_t)1 << lz_nvr) && r_W.size() == comm_W.size();
   const size_t lz_cols = (size_t)1 << (log2_ceil(M) - lz_nvr);
   // (tables whose build - queued by prep_prove a moment ago - has not ended are not waited for: this prove takes the MSM over the row commitments)
   const bool lz_tables_path = lz_ahead && ps.lz_tables && rest_job_used && ps.comm_W_fixed.size() + rows_rest == comm_W.size() && sp_fbtables_ready(ps.lz_tables, 0) == 1;
-  {
-    const aff_t* rows = comm_W.data();
-    const size_t nrows = comm_W.size();
-    SpartanPrepSNARK* psp = &ps;
-    const fe_t* blinds = r_W.data();
-    LzAhead* lzp = lz_ahead ? &lz : nullptr;
-    const sp_ck* key = pk.ck;
-    const size_t cols = lz_cols;
-    // tables of the fixed rows + h: usable when every other row of comm_W is h * blind (commit_zeros)
-    const sp_fbtables* tabs = lz_tables_path ? ps.lz_tables : nullptr;
-    const size_t nfixed = ps.comm_W_fixed.size();
-    const fe_t* dv = dvec;
-    const size_t dn = n_ipa;
-    std::atomic<int>* dvr = &dvec_ready;
-    const fe_t* rda = &r_delta_ahead;
-    ps.bg.submit([ctx, rows, nrows, psp, blinds, lzp, key, cols, tabs, nfixed, dv, dn, dvr, rda] {
-      const std::vector<uint8_t> b = commitment_bytes(rows, nrows);
-      ck(sp_transcript_preabsorb((const uint8_t*)"poly_com", 8, b.data(), b.size(), &psp->poly_com), "poly_com (prepare)");
-      if (!lzp) return;
-      ck(sp_ctx_bind_thread(ctx), "helper thread: device");  // a new thread starts on device 0; the context may live on another GPU
-      ck(sp_points_upload(ctx, u64p(&rows[0].x), nrows, &psp->comm_pts), "comm_W (upload)");
-      const auto t0 = std::chrono::steady_clock::now();
-      // sleeps until the owner publishes the state (helper_may_spin above)
-      auto wait_for = [&](std::atomic<int>& flag) {
-        int st;
-        while ((st = flag.load(std::memory_order_acquire)) == 0) {
-          if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(20)) return 2;  // the prover never got there
-          if (!helper_may_spin()) {
-            std::unique_lock<std::mutex> lk(lzp->mu);  // woken by publish(); the timeout covers a notify that raced the predicate
-            lzp->cv.wait_for(lk, std::chrono::microseconds(100), [&] { return flag.load(std::memory_order_acquire) != 0; });
-          } else {
-            sp_relax();
-          }
-        }
-        return st;
-      };
-      // delta (ipa.rs:147): issued from here once the outer sum-check has left its streaming rounds (the owner publishes delta_state from its
-      // challenge observer): the MSM then runs under the resident tail kernel, which leaves the device idle, instead of beside the first rounds
-      // of the inner sum-check (measured there: k_eval_quad_stream_lowhi 32 us against 18 us alone, profiles/r04_kernel_stats.md)
-      if (wait_for(lzp->delta_state) != 1) return;
-      while (dvr->load(std::memory_order_acquire) == 0) sp_relax();  // d_vec, r_delta (the second helper's job, posted first thing in the prove: long done)
-      lzp->r_delta = *rda;
-      ck(sp_msm_ck_begin(ctx, key, u64p(dv), dn, &lzp->delta_job), "delta (begin)");
-      {
-        sp_msm_job* j = lzp->delta_job;
-        lzp->delta_job = nullptr;  // finish() consumes the job whatever it returns
-        ck(sp_msm_ck_finish(ctx, key, j, u64p(&lzp->r_delta), u64p(&lzp->delta.x)), "delta (finish)");
-      }
-      lzp->delta_done = true;
-      lzp->early_done.store(1, std::memory_order_release);
-      if (tabs && lzp->nvr >= 1 && nrows == ((size_t)1 << lzp->nvr)) {
-        // comm_LZ = sum_{fixed rows} L_i comm_W[i] + (sum_{zero rows} L_i blind_i) h, L = eq(r_rows, .): one multi_mul over the prepared tables. Its ~100 us
-        // of dependent point additions are the critical path of the opening, so everything in front of the launch is kept off the last row challenge:
-        // eq(r, .) is expanded a level per challenge as the inner sum-check draws them (the observer counts them in rows_known), and what the last
-        // challenge r leaves to do is the last level (2^(nvr-1) products) and h's scalar, (1 - r) S0 + r S1 with S_c = sum over the zero rows of parity c
-        // of P[i >> 1] blind_i taken one level up; <L, r_W> for z_delta follows the launch. (All of it at once behind the last challenge was ~40 us.)
-        const size_t nvr = lzp->nvr;
-        std::vector<fe_t> P(1, fe_one<S>());
-        for (size_t known = 0; known + 1 < nvr; ++known) {
-          const auto w0 = std::chrono::steady_clock::now();
-          while ((size_t)lzp->rows_known.load(std::memory_order_acquire) <= known) {
-            if (lzp->state.load(std::memory_order_acquire) == 2 || std::chrono::steady_clock::now() - w0 > std::chrono::seconds(20)) return;
-            if (!helper_may_spin()) {
-              std::unique_lock<std::mutex> lk(lzp->mu);
-              lzp->cv.wait_for(lk, std::chrono::microseconds(50), [&] { return (size_t)lzp->rows_known.load(std::memory_order_acquire) > known; });
-            } else {
-              sp_relax();
-            }
-          }
-          const fe_t rk = lzp->r[known];
-          std::vector<fe_t> Q(2 * P.size());
-          for (size_t i = 0; i < P.size(); ++i) {  // the new variable is the index LSB (eq.rs:66-76)
-            const fe_t hi = fe_mul<S>(P[i], rk);
-            Q[2 * i + 1] = hi;
-            Q[2 * i] = fe_sub<S>(P[i], hi);
-          }
-          P.swap(Q);
-        }
-        fe_t S0 = fe_zero(), S1 = fe_zero();
-        for (size_t i = nfixed; i < nrows; ++i) {
-          const fe_t t = fe_mul<S>(P[i >> 1], blinds[i]);
-          if (i & 1) S1 = fe_add<S>(S1, t);
-          else S0 = fe_add<S>(S0, t);
-        }
-        if (wait_for(lzp->state) != 1) return;
-        const fe_t rl = lzp->r[nvr - 1];
-        bool launched = false;
-        if (nfixed + 1 < 1024) {  // the last level on the device (k_multi_mul_coop EXPAND): the launch goes out before this thread forms it for r_LZ
-          const fe_t s01[2] = {S0, S1};
-          ck(sp_fbtables_multi_mul_begin_eq(ctx, tabs, u64p(P.data()), nfixed, u64p(s01), u64p(&rl)), "comm_LZ (begin)");
-          ck(sp_rowmat_vec_eq_begin_with(ctx, psp->W, u64p(lzp->r), lzp->nvr, cols, dn == cols ? u64p(dv) : nullptr, &lzp->vec), "bind_with_delayed (begin)");
-          launched = true;
-        }
-        std::vector<fe_t> sc(nfixed + 1);
-        for (size_t h = 0; h < P.size(); ++h) {
-          const fe_t hi = fe_mul<S>(P[h], rl), lo = fe_sub<S>(P[h], hi);
-          if (2 * h < nfixed) sc[2 * h] = lo;
-          if (2 * h + 1 < nfixed) sc[2 * h + 1] = hi;
-        }
-        const fe_t hs = fe_add<S>(S0, fe_mul<S>(rl, fe_sub<S>(S1, S0)));
-        sc[nfixed] = hs;
-        if (!launched) {
-          ck(sp_fbtables_multi_mul_begin(ctx, tabs, u64p(sc.data()), sc.size()), "comm_LZ (begin)");
-          ck(sp_rowmat_vec_eq_begin_with(ctx, psp->W, u64p(lzp->r), lzp->nvr, cols, dn == cols ? u64p(dv) : nullptr, &lzp->vec), "bind_with_delayed (begin)");
-        }
-        fe_t acc = hs;  // r_LZ = <L, r_W> (hyrax_pc.rs:446-455)
-        for (size_t i = 0; i < nfixed; ++i) acc = fe_add<S>(acc, fe_mul<S>(sc[i], blinds[i]));
-        lzp->r_LZ = acc;
-        ck(sp_fbtables_multi_mul_finish(ctx, u64p(&lzp->comm_LZ.x)), "comm_LZ (finish)");
-        lzp->have_comm_LZ = true;
-        return;
-      }
-      if (wait_for(lzp->state) != 1) return;
-      const size_t hb = lzp->nvr / 2, lb = lzp->nvr - hb;
-      ck(sp_msm_eq_begin(ctx, psp->comm_pts, u64p(lzp->r), lzp->nvr, &lzp->job), "comm_LZ (begin)");
-      ck(sp_rowmat_vec_eq_begin_with(ctx, psp->W, u64p(lzp->r), lzp->nvr, cols, dn == cols ? u64p(dv) : nullptr, &lzp->vec), "bind_with_delayed (begin)");
-      // r_LZ = <L, r_W> with L = eq(r) = left (x) right: 2^nvr + 2^(nvr/2) products instead of 2 * 2^nvr
-      const std::vector<fe_t> left = eq_evals_host(lzp->r, hb), right = eq_evals_host(lzp->r + hb, lb);
-      fe_t acc = fe_zero();
-      for (size_t a = 0; a < left.size(); ++a) {
-        fe_t inner = fe_zero();
-        for (size_t c2 = 0; c2 < right.size(); ++c2) inner = fe_add<S>(inner, fe_mul<S>(right[c2], blinds[a * right.size() + c2]));
-        acc = fe_add<S>(acc, fe_mul<S>(left[a], inner));
-      }
-      lzp->r_LZ = acc;
-    });
-  }
-  struct BgJoin {  // comm_W, r_W and lz must outlive the job on every exit path
-    Background& b;
-    std::atomic<int>&st, &st2;
-    sp_ctx* ctx;
-    sp_msm_job *&j1, *&j2;
-    sp_vec_job*& v1;
-    ~BgJoin() {
-      int zero = 0;
-      st2.compare_exchange_strong(zero, 2);
-      zero = 0;
-      st.compare_exchange_strong(zero, 2);
-      b.wait_nothrow();
-      // an abandoned prove (error exit) still owns whatever the helper had started: finish the jobs to release them
-      uint64_t sink[8];
-      if (j1) sp_msm_job_finish(ctx, j1, sink);
-      if (j2) sp_msm_job_finish(ctx, j2, sink);
-      if (v1) {
-        std::vector<uint64_t> big(4 * 2048);
-        sp_rowmat_vec_eq_finish(ctx, v1, big.data());
-      }
-      j1 = j2 = nullptr;
-      v1 = nullptr;
-    }
-  } bg_join{ps.bg, lz.state, lz.delta_state, ctx, lz.job, lz.delta_job, lz.vec};
+  lz.ctx = ctx;
+  lz.rows = comm_W.data();
+  lz.nrows = comm_W.size();
+  lz.psp = &ps;
+  lz.blinds = r_W.data();
+  lz.ahead = lz_ahead;
+  lz.key = pk.ck;
+  lz.cols = lz_cols;
+  lz.tabs = lz_tables_path ? ps.lz_tables : nullptr;
+  lz.nfixed = ps.comm_W_fixed.size();
+  lz.dv = dvec;
+  lz.dn = n_ipa;
+  lz.dvr = &pre.dvec_ready;
+  lz.rda = &pre.r_delta;
+  ps.bg.submit([&lz] { lz.run(); });
+  BgJoin bg_join{ps.bg, lz.state, lz.delta_state, ctx, lz.job, lz.delta_job, lz.vec};
   const double t_wit = now_ms();
 
   const size_t num_rounds_x = log2_ceil(N), num_rounds_y = log2_ceil(M) + 1;
@@ -921,33 +928,12 @@ ProofBuf prove(const SpartanProverKey& pk, SpartanPrepSNARK& ps, const uint64_t*
   const double t_mv = now_ms();
 
   ProofBuf proof;
-  for (const aff_t& a : comm_W) proof.pp(a);
-  for (const fe_t& f : publics) proof.pf(f);
-  for (const fe_t& f : challenges) proof.pf(f);  // SplitR1CSInstance carries them (src/r1cs/mod.rs:1423-1437)
+  proof.header(comm_W, publics, challenges);
   // outer sum-check (src/spartan.rs:291-310)
   std::vector<fe_t> outer_polys(3 * num_rounds_x), r_x(num_rounds_x);
   fe_t claims_outer[3];
   const fe_t zero = fe_zero();
-  // evals_rx started four rounds before r_x is complete (sp_eq_table_begin builds the half tables of the first ell - 4 coordinates on a stream of
-  // its own; sp_eq_table_finish behind the last challenge is then one launch).
-  struct EqObs {
-    sp_ctx* ctx;
-    size_t ell;
-    fe_t r[24];
-    LzAhead* lz;  // non-null: delta's MSM is the helper's to issue (see there)
-    int rc = 0;
-    bool begun = false;
-    static void fn(void* u, size_t round, const uint64_t r[4]) {
-      EqObs* o = (EqObs*)u;
-      if (o->lz && round + delta_rounds_before_end() == o->ell) o->lz->publish(o->lz->delta_state, 1);
-      if (round + 4 >= o->ell) return;  // the last four coordinates (the rounds the host runs itself after the hand-over) are applied by sp_eq_table_finish
-      memcpy(&o->r[round], r, 32);
-      if (round + 5 == o->ell) {
-        o->rc = sp_eq_table_begin(o->ctx, u64p(o->r), o->ell - 4, o->ell);
-        o->begun = o->rc == 0;
-      }
-    }
-  } eq_obs{ctx, num_rounds_x, {}, lz_ahead ? &lz : nullptr};
+  EqObs eq_obs{ctx, num_rounds_x, {}, lz_ahead ? &lz : nullptr};
   const bool use_eq_obs = num_rounds_x >= 12 && num_rounds_x <= 20;
   if (use_eq_obs)
     ck(sp_sumcheck_cubic3_observed(ctx, u64p(&zero), u64p(tau.data()), num_rounds_x, ps.az, ps.bz, ps.cz, ps.p0, ps.p0 ? ps.p1 : nullptr, tr.t, &EqObs::fn, &eq_obs,
@@ -964,19 +950,18 @@ ProofBuf prove(const SpartanProverKey& pk, SpartanPrepSNARK& ps, const uint64_t*
   if (eq_obs.rc) throw Error(eq_obs.rc, std::string("evals_rx (begin): ") + sp_last_error());
   if (lz_ahead) lz.publish(lz.delta_state, 1);  // (a sum-check of fewer than 15 rounds, or one without the observer, has not done it)
   tr.absorb_scalars("claims_outer", claims_outer, 3);
-  for (const fe_t& f : outer_polys) proof.pf(f);
-  for (int i = 0; i < 3; ++i) proof.pf(claims_outer[i]);
+  proof.outer(outer_polys.data(), num_rounds_x, claims_outer);
   const double t_outer = now_ms();
 
   const fe_t r = tr.squeeze("r");
-  const fe_t claim_inner_joint = fe_add<S>(fe_add<S>(claims_outer[0], fe_mul<S>(r, claims_outer[1])), fe_mul<S>(fe_mul<S>(r, r), claims_outer[2]));
+  const fe_t claim_inner_joint = joint_inner_claim(claims_outer, r);
   // evals_rx + bind_and_prepare_poly_ABC (src/spartan.rs:316-322)
   ck(sp_eq_table_finish(ctx, u64p(r_x.data()), num_rounds_x, ps.rx), "evals_rx");  // (= sp_eq_table_into when nothing was begun)
   ck(sp_poly_abc(ctx, pk.S, ps.rx, u64p(&r), 2 * M, ps.abc), "poly_ABC");
   const double t_abc = now_ms();
 
   sp_msm_job* delta_job = nullptr;
-  await_flag(dvec_ready);  // d_vec, r_delta, r_beta from here on
+  await_flag(pre.dvec_ready);  // d_vec, r_delta, r_beta from here on
   if (!lz_ahead) ck(sp_msm_ck_begin(ctx, pk.ck, u64p(dvec), n_ipa, &delta_job), "delta (begin)");
   // inner sum-check. The reference runs round 0 by hand on the compact vectors (src/spartan.rs:323-384); that round is
   // value-identical to a generic prove_quad round on the 2M-long tables with (lo_eff, hi_eff) = (M, num_extra).
@@ -984,30 +969,12 @@ ProofBuf prove(const SpartanProverKey& pk, SpartanPrepSNARK& ps, const uint64_t*
   ck(sp_table_set_len(ps.z, 2 * M, M, pk.num_extra), "z len");
   std::vector<fe_t> inner_polys(2 * num_rounds_y), r_y(num_rounds_y);
   fe_t claims_inner[2];
-  // r_y[0] selects W against (1, X); r_y[1 ..= nvr] are the row variables of W (MSB first): once they are drawn the helper can start comm_LZ
-  // <R, d> (ipa.rs:148) with R = eq(point[nvr..]) = left (x) right: the partial sums T[b] = sum_a left[a] d[a |right| + b] need only `left`, whose
-  // variables are bound hb rounds after the row variables - the second helper computes them under the remaining rounds and the prover finishes with
-  // |right| products instead of |R| + |left| after the last round
-  struct IpAhead {
-    size_t first = 0, hb = 0, nright = 0;  // left = eq(r_y[first .. first + hb))
-    fe_t left_r[16], right_r[16];
-    std::vector<fe_t> T;
-    bool submitted = false;
-    // ... and once the last challenge is drawn the same job finishes <R, d> and beta = <R, d> ck_c + r_beta h_c (ipa.rs:148-149) beside the prover's
-    // own work on eval_W; it waits for that challenge with a short bounded spin
-    std::atomic<int> right_ready{0};
-    size_t nright_vars = 0, last_round = 0;
-    fe_t r_beta, ip;
-    aff_t beta;
-    bool beta_ready = false;
-    sp_ctx* ctx = nullptr;
-    const sp_ck* ck_s = nullptr;
-    const aff_t* beta_term = nullptr;           // h_s * r_beta from the first helper job ...
-    const std::atomic<int>* term_ready = nullptr;  // ... valid when this is set
-  } ipa;
-  ipa.beta_term = &beta_term;
-  ipa.term_ready = &eval_W_term_ready;
-  ipa.r_beta = r_beta_ahead;
+  // the row variables go to the first helper (comm_LZ), the column variables to the second (<R, d>, beta): Obs, IpAhead
+  IpAhead ipa;
+  ipa.beta_term = &pre.beta_term;
+  ipa.term_ready = &pre.eval_W_term_ready;
+  ipa.r_beta = pre.r_beta;
+  ipa.dvec = dvec;
   ipa.ctx = ctx;
   ipa.ck_s = pk.ck_s;
   if (lz_ahead) {
@@ -1020,71 +987,13 @@ ProofBuf prove(const SpartanProverKey& pk, SpartanPrepSNARK& ps, const uint64_t*
     if (ipa.nright_vars > 16) ipa.hb = 0;
     if (ipa.hb == 0 || ipa.hb > 16 || (((size_t)1 << ipa.hb) * ipa.nright) != n_ipa) ipa.hb = 0;  // (not this shape: the prover computes <R, d> itself)
   }
-  struct Obs {
-    decltype(lz)* lz;
-    bool on;
-    IpAhead* ipa;
-    Background* bg2;
-    const fe_t* dvec;
-    static void fn(void* u, size_t round, const uint64_t r[4]) {
-      Obs* o = (Obs*)u;
-      if (!o->on || round == 0) return;
-      if (round <= o->lz->nvr) {
-        memcpy(&o->lz->r[round - 1], r, 32);
-        o->lz->rows_known.store((int)round, std::memory_order_release);
-        if (round == o->lz->nvr) o->lz->publish(o->lz->state, 1);
-        return;
-      }
-      IpAhead* ip = o->ipa;
-      if (!ip->hb || round < ip->first) return;
-      if (round >= ip->first + ip->hb) {
-        memcpy(&ip->right_r[round - ip->first - ip->hb], r, 32);
-        if (round == ip->last_round) ip->right_ready.store(1, std::memory_order_release);
-        return;
-      }
-      memcpy(&ip->left_r[round - ip->first], r, 32);
-      if (round + 1 == ip->first + ip->hb) {
-        const fe_t* dv = o->dvec;
-        o->bg2->submit([ip, dv] {
-          const std::vector<fe_t> left = eq_evals_host(ip->left_r, ip->hb);
-          ip->T.assign(ip->nright, fe_zero());
-          for (size_t a = 0; a < left.size(); ++a)
-            for (size_t b = 0; b < ip->nright; ++b) ip->T[b] = fe_add<S>(ip->T[b], fe_mul<S>(left[a], dv[a * ip->nright + b]));
-          const auto t0 = std::chrono::steady_clock::now();
-          while (ip->right_ready.load(std::memory_order_acquire) == 0) {
-            if (std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(150)) return;  // (the prover finishes <R, d> and beta itself; a helper does not sit on a CPU of the quota)
-            sp_relax();
-          }
-          const std::vector<fe_t> right = eq_evals_host(ip->right_r, ip->nright_vars);
-          fe_t acc = fe_zero();
-          for (size_t b = 0; b < right.size(); ++b) acc = fe_add<S>(acc, fe_mul<S>(right[b], ip->T[b]));
-          ip->ip = acc;
-          if (ip->term_ready->load(std::memory_order_acquire)) ck(sp_hyrax_commit_small_with_term(ip->ctx, ip->ck_s, u64p(&ip->ip), 1, u64p(&ip->beta_term->x), u64p(&ip->beta.x)), "beta");
-          else ck(sp_hyrax_commit_small(ip->ctx, ip->ck_s, u64p(&ip->ip), 1, u64p(&ip->r_beta), u64p(&ip->beta.x)), "beta");
-          ip->beta_ready = true;
-        });
-        ip->submitted = true;
-      }
-    }
-  } obs{&lz, lz_ahead, &ipa, &ps.bg2, dvec};
-  struct IpJoin {  // ipa and dvec outlive the job on every exit path
-    Background& b;
-    ~IpJoin() { b.wait_nothrow(); }
-  } ip_join{ps.bg2};
+  Obs obs{&lz, lz_ahead, &ipa, &ps.bg2};
+  IpJoin ip_join{ps.bg2};
   ck(sp_sumcheck_quad_observed(ctx, u64p(&claim_inner_joint), num_rounds_y, ps.abc, ps.z, tr.t, &Obs::fn, &obs, u64p(inner_polys.data()), u64p(r_y.data()),
                                u64p(claims_inner)),
      "inner sum-check");
-  for (const fe_t& f : inner_polys) proof.pf(f);
-  const fe_t eval_Z = claims_inner[1];
-  // eval_W = (eval_Z - r_y0 eval_X) / (1 - r_y0)   (src/spartan.rs:411-421)
-  std::vector<fe_t> X;
-  X.push_back(fe_one<S>());
-  X.insert(X.end(), publics.begin(), publics.end());
-  X.insert(X.end(), challenges.begin(), challenges.end());  // to_regular_instance: X = public_values ++ challenges (src/r1cs/mod.rs:1546-1549)
-  const fe_t eval_X = sparse_poly_evaluate(num_rounds_y - 1, X, r_y.data() + 1);
-  const fe_t denom = fe_sub<S>(fe_one<S>(), r_y[0]);
-  if (fe_is_zero(denom)) throw Error(SP_ERR_DIVISION_BY_ZERO, "DivisionByZero");
-  const fe_t eval_W = fe_mul<S>(fe_sub<S>(eval_Z, fe_mul<S>(r_y[0], eval_X)), fe_inv_vartime<S>(denom));
+  proof.inner(inner_polys.data(), num_rounds_y);
+  const fe_t eval_W = eval_W_from(claims_inner[1], r_y.data(), num_rounds_y, publics, challenges);
   lap("inner+eval_W");
   const double t_inner = now_ms();
 
@@ -1137,8 +1046,8 @@ ProofBuf prove(const SpartanProverKey& pk, SpartanPrepSNARK& ps, const uint64_t*
     for (size_t i = 0; i < L.size(); ++i) r_LZ = fe_add<S>(r_LZ, fe_mul<S>(L[i], r_W[i]));
   }
   aff_t comm_eval_W;
-  if (eval_W_term_ready.load(std::memory_order_acquire) && memcmp(&eval_W_term_blind, &blind_eval_W, sizeof(fe_t)) == 0)
-    ck(sp_hyrax_commit_small_with_term(ctx, pk.ck_s, u64p(&eval_W), 1, u64p(&eval_W_term.x), u64p(&comm_eval_W.x)), "commit eval_W");
+  if (pre.eval_W_term_ready.load(std::memory_order_acquire) && memcmp(&pre.eval_W_term_blind, &blind_eval_W, sizeof(fe_t)) == 0)
+    ck(sp_hyrax_commit_small_with_term(ctx, pk.ck_s, u64p(&eval_W), 1, u64p(&pre.eval_W_term.x), u64p(&comm_eval_W.x)), "commit eval_W");
   else
     ck(sp_hyrax_commit_small(ctx, pk.ck_s, u64p(&eval_W), 1, u64p(&blind_eval_W), u64p(&comm_eval_W.x)), "commit eval_W");
   lap("comm_eval_W");
@@ -1198,19 +1107,7 @@ ProofBuf prove(const SpartanProverKey& pk, SpartanPrepSNARK& ps, const uint64_t*
   } else if (lz_job && lz_ahead) ck(sp_msm_job_finish(ctx, lz_job, u64p(&comm_LZ.x)), "comm_LZ (finish)");  // the blinds are inside the row commitments
   else if (lz_job) ck(sp_msm_ck_finish(ctx, pk.ck, lz_job, u64p(&r_LZ), u64p(&comm_LZ.x)), "comm_LZ (finish)");
   lap("comm_LZ_finish");
-  {
-    uint8_t b[128];
-    point_bytes(comm_LZ, b);
-    point_bytes(comm_eval_W, b + 64);
-    tr.absorb("U", b, 128);
-  }
-  {
-    uint8_t b[64];
-    point_bytes(delta, b);
-    tr.absorb("delta", b, 64);
-    point_bytes(beta, b);
-    tr.absorb("beta", b, 64);
-  }
+  absorb_ipa_instance(tr, comm_LZ, comm_eval_W, delta, beta);
   const fe_t rr = tr.squeeze("r");
   proof.pp(delta);
   proof.pp(beta);
@@ -1250,15 +1147,7 @@ ProofBuf prove(const SpartanProverKey& pk, SpartanPrepSNARK& ps, const uint64_t*
   proof.pf(fe_add<S>(fe_mul<S>(rr, blind_eval_W), r_beta));
   lap("z_vec");
   const double t_end = now_ms();
-  if (pt) {
-    pt->ms[0] = t_wit - t_start - t_mv_issue;  // the matrix-vector product is issued inside the witness phase and runs under it
-    pt->ms[1] = t_mv - t_wit + t_mv_issue;
-    pt->ms[2] = t_outer - t_mv;
-    pt->ms[3] = t_abc - t_outer;
-    pt->ms[4] = t_inner - t_abc;
-    pt->ms[5] = t_end - t_inner;
-    pt->ms[6] = t_end - t_start;
-  }
+  if (pt) fill_phase_ms(pt->ms, t_start, t_wit, t_mv, t_outer, t_abc, t_inner, t_end, t_mv_issue);  // the matrix-vector product is issued inside the witness phase and runs under it
   ps.queue_lz_tables(ctx);
   return proof;
 }
@@ -1284,22 +1173,15 @@ ProofBuf prove_reference_order(const SpartanProverKey& pk, SpartanPrepSNARK& ps,
     fprintf(stderr, "ref lap %-28s %.3f ms\n", name, t - t_lap);
     t_lap = t;
   };
-  std::vector<fe_t> publics(npub);
-  for (size_t i = 0; i < npub; ++i) publics[i] = fe_from_u64<S>(publics_u64[i]);
-  // :226-236 transcript, vk, public values
+  const std::vector<fe_t> publics = publics_from_u64(publics_u64, npub);
+  // :226-236 transcript, vk, public values; r1cs_instance_and_witness (src/bellpepper/r1cs.rs:411-540)
   Tr tr(ctx, "SpartanSNARK");
   ck(sp_transcript_set_async(tr.t, 1), "transcript");  // (the shim's TranscriptEngine: long absorbs hashed beside the caller's next calls)
-  tr.absorb("vk", pk.vk_digest, 32);
-  tr.absorb_scalars("public_values", publics.data(), npub);
-  // r1cs_instance_and_witness (src/bellpepper/r1cs.rs:411-540)
-  if (ps.rows_shared) tr.absorb("comm_W_shared", ps.comm_shared_bytes.data(), ps.comm_shared_bytes.size());
-  if (ps.rows_precommitted) tr.absorb("comm_W_precommitted", ps.comm_pre_bytes.data(), ps.comm_pre_bytes.size());
-  std::vector<fe_t> challenges(d.num_challenges);
+  absorb_instance_prefix(tr, pk.vk_digest, publics.data(), npub, ps.comm_shared_bytes, ps.comm_pre_bytes);
+  std::vector<fe_t> challenges;
   if (d.num_challenges) {
-    if (!synth) throw Error(SP_ERR_INTERNAL, "a circuit with verifier challenges needs its synthesize callback");
-    for (auto& c : challenges) c = tr.squeeze("challenge");
-    std::vector<fe_t> rest(d.num_rest_unpadded + 1);
-    if (synth(synth_user, u64p(challenges.data()), challenges.size(), u64p(rest.data())) != 0) throw Error(SP_ERR_INTERNAL, "SynthesisError: the circuit's synthesize callback failed");
+    challenges = squeeze_challenges(tr, d.num_challenges);
+    const std::vector<fe_t> rest = synthesize_rest(synth, synth_user, u64p(challenges.data()), challenges.size(), d.num_rest_unpadded);
     if (d.num_rest_unpadded) ck(sp_table_write(ctx, ps.W, d.num_shared + d.num_precommitted, u64p(rest.data()), d.num_rest_unpadded), "W rest");
   }
   lap("transcript prefix");
@@ -1308,17 +1190,11 @@ ProofBuf prove_reference_order(const SpartanProverKey& pk, SpartanPrepSNARK& ps,
   for (auto& b : r_W_rest) b = tape.next();  // PCS::blind (r1cs.rs:466)
   std::vector<aff_t> comm_W(rows_pre + rows_rest);
   std::copy(ps.comm_W_fixed.begin(), ps.comm_W_fixed.end(), comm_W.begin());
-  if (rows_rest && d.num_rest_unpadded == 0) ck(sp_fixed_base_mul_h(ctx, pk.ck, u64p(r_W_rest.data()), rows_rest, u64p(&comm_W[rows_pre].x)), "commit_zeros");  // :467-469
-  else if (rows_rest)
-    ck(sp_hyrax_commit(ctx, pk.ck, ps.W, d.num_shared + d.num_precommitted, d.num_rest, u64p(r_W_rest.data()), ps.is_small ? 1 : 0, u64p(&comm_W[rows_pre].x)), "commit rest");
+  commit_rest_rows(ctx, pk.ck, ps.W, d, ps.is_small, r_W_rest.data(), rows_rest, comm_W.data() + rows_pre);
   lap("commit rest rows");
-  {
-    std::vector<uint8_t> b = commitment_bytes(comm_W.data() + rows_pre, rows_rest);
-    tr.absorb("comm_W_rest", b.data(), b.size());
-  }
+  absorb_comm_W_rest(tr, comm_W.data() + rows_pre, rows_rest);
   lap("absorb comm_W_rest");
-  std::vector<fe_t> r_W = ps.r_W_fixed;  // combine_blinds (r1cs.rs:515-524)
-  r_W.insert(r_W.end(), r_W_rest.begin(), r_W_rest.end());
+  const std::vector<fe_t> r_W = combine_blinds(ps.r_W_fixed, r_W_rest);
   // The shim's r1cs_instance_and_witness wrapper ends by announcing the opening PCS::prove will be asked for (sp_hyrax_prove_announce): commitment, blinds
   // and the IPA's randomness exist here — the reference draws that randomness inside InnerProductArgumentLinear::prove from OsRng; with the injected
   // tape it is the cols + 2 blocks behind blind_eval_W's one — and the library starts the opening's transcript-independent parts under the sum-checks.
@@ -1346,10 +1222,7 @@ ProofBuf prove_reference_order(const SpartanProverKey& pk, SpartanPrepSNARK& ps,
   ck(sp_table_copy(ctx, ps.z, 0, ps.W, 0, M), "z <- W");
   {
     ck(sp_table_zero(ctx, ps.z, M, M), "clear z high half");
-    std::vector<fe_t> tail(pk.num_extra);
-    tail[0] = fe_one<S>();
-    std::copy(publics.begin(), publics.end(), tail.begin() + 1);
-    std::copy(challenges.begin(), challenges.end(), tail.begin() + 1 + npub);
+    const std::vector<fe_t> tail = z_tail(pk.num_extra, publics, challenges);
     if (tail.size() <= 2048) ck(sp_table_write_async(ctx, ps.z, M, u64p(tail.data()), tail.size()), "z tail");
     else ck(sp_table_write(ctx, ps.z, M, u64p(tail.data()), tail.size()), "z tail");
   }
@@ -1365,9 +1238,7 @@ ProofBuf prove_reference_order(const SpartanProverKey& pk, SpartanPrepSNARK& ps,
   lap("multiply_vec_incremental");
   const double t_mv = now_ms();
   ProofBuf proof;
-  for (const aff_t& a : comm_W) proof.pp(a);
-  for (const fe_t& f : publics) proof.pf(f);
-  for (const fe_t& f : challenges) proof.pf(f);
+  proof.header(comm_W, publics, challenges);
   // :291-310 outer sum-check
   std::vector<fe_t> outer_polys(3 * num_rounds_x), r_x(num_rounds_x);
   fe_t claims_outer[3];
@@ -1375,12 +1246,11 @@ ProofBuf prove_reference_order(const SpartanProverKey& pk, SpartanPrepSNARK& ps,
   ck(sp_sumcheck_cubic3(ctx, u64p(&zero), u64p(tau.data()), num_rounds_x, ps.az, ps.bz, ps.cz, tr.t, u64p(outer_polys.data()), u64p(r_x.data()), u64p(claims_outer)),
      "outer sum-check");
   tr.absorb_scalars("claims_outer", claims_outer, 3);
-  for (const fe_t& f : outer_polys) proof.pf(f);
-  for (int i = 0; i < 3; ++i) proof.pf(claims_outer[i]);
+  proof.outer(outer_polys.data(), num_rounds_x, claims_outer);
   const double t_outer = now_ms();
   // :311-322 r, evals_rx, bind_and_prepare_poly_ABC
   const fe_t r = tr.squeeze("r");
-  const fe_t claim_inner_joint = fe_add<S>(fe_add<S>(claims_outer[0], fe_mul<S>(r, claims_outer[1])), fe_mul<S>(fe_mul<S>(r, r), claims_outer[2]));
+  const fe_t claim_inner_joint = joint_inner_claim(claims_outer, r);
   ck(sp_eq_table_into(ctx, u64p(r_x.data()), num_rounds_x, ps.rx), "evals_rx");
   ck(sp_poly_abc(ctx, pk.S, ps.rx, u64p(&r), 2 * M, ps.abc), "poly_ABC");
   const double t_abc = now_ms();
@@ -1390,17 +1260,9 @@ ProofBuf prove_reference_order(const SpartanProverKey& pk, SpartanPrepSNARK& ps,
   std::vector<fe_t> inner_polys(2 * num_rounds_y), r_y(num_rounds_y);
   fe_t claims_inner[2];
   ck(sp_sumcheck_quad(ctx, u64p(&claim_inner_joint), num_rounds_y, ps.abc, ps.z, tr.t, u64p(inner_polys.data()), u64p(r_y.data()), u64p(claims_inner)), "inner sum-check");
-  for (const fe_t& f : inner_polys) proof.pf(f);
+  proof.inner(inner_polys.data(), num_rounds_y);
   // :405-421 eval_W
-  const fe_t eval_Z = claims_inner[1];
-  std::vector<fe_t> X;
-  X.push_back(fe_one<S>());
-  X.insert(X.end(), publics.begin(), publics.end());
-  X.insert(X.end(), challenges.begin(), challenges.end());
-  const fe_t eval_X = sparse_poly_evaluate(num_rounds_y - 1, X, r_y.data() + 1);
-  const fe_t denom = fe_sub<S>(fe_one<S>(), r_y[0]);
-  if (fe_is_zero(denom)) throw Error(SP_ERR_DIVISION_BY_ZERO, "DivisionByZero");
-  const fe_t eval_W = fe_mul<S>(fe_sub<S>(eval_Z, fe_mul<S>(r_y[0], eval_X)), fe_inv_vartime<S>(denom));
+  const fe_t eval_W = eval_W_from(claims_inner[1], r_y.data(), num_rounds_y, publics, challenges);
   lap("eval_W");
   const double t_inner = now_ms();
   // :423-436 blind, commit to eval_W, PCS::prove
@@ -1421,15 +1283,7 @@ ProofBuf prove_reference_order(const SpartanProverKey& pk, SpartanPrepSNARK& ps,
   tape.skip(cols + 2);
   proof.words.insert(proof.words.end(), arg.begin(), arg.end());
   const double t_end = now_ms();
-  if (pt) {
-    pt->ms[0] = t_wit - t_start;
-    pt->ms[1] = t_mv - t_wit;
-    pt->ms[2] = t_outer - t_mv;
-    pt->ms[3] = t_abc - t_outer;
-    pt->ms[4] = t_inner - t_abc;
-    pt->ms[5] = t_end - t_inner;
-    pt->ms[6] = t_end - t_start;
-  }
+  if (pt) fill_phase_ms(pt->ms, t_start, t_wit, t_mv, t_outer, t_abc, t_inner, t_end);
   ps.queue_lz_tables(ctx);
   return proof;
 }
@@ -1526,6 +1380,7 @@ static void prove_batch_chunk(const SpartanProverKey& pk, SpartanPrepSNARK* cons
     t_last = t;
   };
   const size_t rows_rest = (d.num_rest + W_ - 1) / W_;
+  const std::vector<fe_t> no_challenges;  // (prove_batch refuses circuits with verifier challenges)
   const bool batch_abc = !(flags & SS_BATCH_PER_PROOF_POLYABC) && ((flags & SS_BATCH_BATCHED_POLYABC) || count >= BATCH_POLYABC_MIN);
   const bool batch_rest = rows_rest && !(flags & SS_BATCH_PER_PROOF_REST_COMMIT) && ((flags & SS_BATCH_BATCHED_REST_COMMIT) || count >= BATCH_REST_COMMIT_MIN);
   const bool opening_ahead =
@@ -1534,14 +1389,10 @@ static void prove_batch_chunk(const SpartanProverKey& pk, SpartanPrepSNARK* cons
   each([&](Item& it, size_t k) {
     it.ps = pss[k];
     it.tape = &tapes[k];
-    it.publics.resize(npub);
-    for (size_t i = 0; i < npub; ++i) it.publics[i] = fe_from_u64<S>(publics_u64[k * npub + i]);
+    it.publics = publics_from_u64(publics_u64 + k * npub, npub);
     it.tr.reset(new Tr(ctx, "SpartanSNARK"));
     ck(sp_transcript_set_async(it.tr->t, 1), "transcript");
-    it.tr->absorb("vk", pk.vk_digest, 32);
-    it.tr->absorb_scalars("public_values", it.publics.data(), npub);
-    if (it.ps->rows_shared) it.tr->absorb("comm_W_shared", it.ps->comm_shared_bytes.data(), it.ps->comm_shared_bytes.size());
-    if (it.ps->rows_precommitted) it.tr->absorb("comm_W_precommitted", it.ps->comm_pre_bytes.data(), it.ps->comm_pre_bytes.size());
+    absorb_instance_prefix(*it.tr, pk.vk_digest, it.publics.data(), npub, it.ps->comm_shared_bytes, it.ps->comm_pre_bytes);
   });
   // PCS::blind (r1cs.rs:466)
   each([&](Item& it, size_t) {
@@ -1554,11 +1405,7 @@ static void prove_batch_chunk(const SpartanProverKey& pk, SpartanPrepSNARK* cons
     const size_t rows_pre = ps.comm_W_fixed.size();
     it.comm_W.resize(rows_pre + rows_rest);
     std::copy(ps.comm_W_fixed.begin(), ps.comm_W_fixed.end(), it.comm_W.begin());
-    if (batch_rest) return;
-    if (rows_rest && d.num_rest_unpadded == 0) ck(sp_fixed_base_mul_h(ctx, pk.ck, u64p(it.r_W_rest.data()), rows_rest, u64p(&it.comm_W[rows_pre].x)), "commit_zeros");
-    else if (rows_rest)
-      ck(sp_hyrax_commit(ctx, pk.ck, ps.W, d.num_shared + d.num_precommitted, d.num_rest, u64p(it.r_W_rest.data()), ps.is_small ? 1 : 0, u64p(&it.comm_W[rows_pre].x)),
-         "commit rest");
+    if (!batch_rest) commit_rest_rows(ctx, pk.ck, ps.W, d, ps.is_small, it.r_W_rest.data(), rows_rest, it.comm_W.data() + rows_pre);
   });
   if (batch_rest && d.num_rest_unpadded == 0) {
     // commit_zeros of every proof in ONE call: the same base h and the same words per scalar, count x rows_rest blinds
@@ -1579,15 +1426,11 @@ static void prove_batch_chunk(const SpartanProverKey& pk, SpartanPrepSNARK* cons
     ck(sp_hyrax_commit_batch(ctx, pk.ck, count, Ws.data(), d.num_shared + d.num_precommitted, d.num_rest, bl.data(), outs.data()), "prove_batch: commit rest");
   }
   each([&](Item& it, size_t) {
-    SpartanPrepSNARK& ps = *it.ps;
-    const size_t rows_pre = ps.comm_W_fixed.size();
-    std::vector<uint8_t> b = commitment_bytes(it.comm_W.data() + rows_pre, rows_rest);
-    it.tr->absorb("comm_W_rest", b.data(), b.size());
-    it.r_W = ps.r_W_fixed;
-    it.r_W.insert(it.r_W.end(), it.r_W_rest.begin(), it.r_W_rest.end());
+    absorb_comm_W_rest(*it.tr, it.comm_W.data() + it.ps->comm_W_fixed.size(), rows_rest);
+    it.r_W = combine_blinds(it.ps->r_W_fixed, it.r_W_rest);
   });
   // The opening, begun ahead: comm_W and its blinds are complete, and the IPA's randomness is the tape's blocks behind blind_eval_W's (the one draw
-  // between here and PCS::prove), as prove's announcement takes them. The pointers are checked against the tape's position when the opening comes.
+  // between here and PCS::prove), as prove_reference_order's announcement takes them. The pointers are checked against the tape's position when the opening comes.
   const size_t num_rows = (M + W_ - 1) / W_, cols = M / num_rows, rows_W = items[0].comm_W.size();
   std::vector<const uint64_t*> comms(count), blinds(count);
   std::vector<const sp_table*> polys(count);
@@ -1618,9 +1461,7 @@ static void prove_batch_chunk(const SpartanProverKey& pk, SpartanPrepSNARK* cons
     ck(sp_table_set_len(ps.z, 2 * M, (size_t)-1, (size_t)-1), "z len");
     ck(sp_table_copy(ctx, ps.z, 0, ps.W, 0, M), "z <- W");
     ck(sp_table_zero(ctx, ps.z, M, M), "clear z high half");
-    std::vector<fe_t> tail(pk.num_extra);
-    tail[0] = fe_one<S>();
-    std::copy(it.publics.begin(), it.publics.end(), tail.begin() + 1);
+    const std::vector<fe_t> tail = z_tail(pk.num_extra, it.publics, no_challenges);
     // (the staged asynchronous write reuses a few pinned slots behind events; `tail` dies with this statement, so the plain write it is)
     ck(sp_table_write(ctx, ps.z, M, u64p(tail.data()), tail.size()), "z tail");
     ck(sp_table_set_len(ps.z, pk.num_cols, (size_t)-1, (size_t)-1), "z len");
@@ -1636,10 +1477,7 @@ static void prove_batch_chunk(const SpartanProverKey& pk, SpartanPrepSNARK* cons
     ck(sp_multiply_vec_incremental(ctx, pk.S, ps.z, ps.caz, ps.cbz, ps.ccz, ps.az, ps.bz, ps.cz), "multiply_vec_incremental");
   });
   phase(1);
-  each([&](Item& it, size_t) {
-    for (const aff_t& a : it.comm_W) it.proof.pp(a);
-    for (const fe_t& f : it.publics) it.proof.pf(f);
-  });
+  each([&](Item& it, size_t) { it.proof.header(it.comm_W, it.publics, no_challenges); });
   // :291-310 outer sum-check, all proofs in lockstep
   std::vector<sp_table*> tA(count), tB(count), tC(count);
   std::vector<sp_transcript*> trs(count);
@@ -1656,15 +1494,14 @@ static void prove_batch_chunk(const SpartanProverKey& pk, SpartanPrepSNARK* cons
   each([&](Item& it, size_t k) {
     for (int i = 0; i < 3; ++i) it.claims_outer[i] = outer_final[3 * k + i];
     it.tr->absorb_scalars("claims_outer", it.claims_outer, 3);
-    for (size_t i = 0; i < 3 * num_rounds_x; ++i) it.proof.pf(outer_polys[k * 3 * num_rounds_x + i]);
-    for (int i = 0; i < 3; ++i) it.proof.pf(it.claims_outer[i]);
+    it.proof.outer(&outer_polys[k * 3 * num_rounds_x], num_rounds_x, it.claims_outer);
   });
   phase(2);
   // :311-322 r, evals_rx, bind_and_prepare_poly_ABC
   each([&](Item& it, size_t k) {
     SpartanPrepSNARK& ps = *it.ps;
     it.r = it.tr->squeeze("r");
-    claims[k] = fe_add<S>(fe_add<S>(it.claims_outer[0], fe_mul<S>(it.r, it.claims_outer[1])), fe_mul<S>(fe_mul<S>(it.r, it.r), it.claims_outer[2]));
+    claims[k] = joint_inner_claim(it.claims_outer, it.r);
     if (batch_abc) return;
     ck(sp_eq_table_into(ctx, u64p(&r_x[k * num_rounds_x]), num_rounds_x, ps.rx), "evals_rx");
     ck(sp_poly_abc(ctx, pk.S, ps.rx, u64p(&it.r), 2 * M, ps.abc), "poly_ABC");
@@ -1695,16 +1532,9 @@ static void prove_batch_chunk(const SpartanProverKey& pk, SpartanPrepSNARK* cons
   std::vector<fe_t> eval_W(count);
   // :405-421 eval_W
   each([&](Item& it, size_t k) {
-    for (size_t i = 0; i < 2 * num_rounds_y; ++i) it.proof.pf(inner_polys[k * 2 * num_rounds_y + i]);
+    it.proof.inner(&inner_polys[k * 2 * num_rounds_y], num_rounds_y);
     it.r_y.assign(r_y.begin() + k * num_rounds_y, r_y.begin() + (k + 1) * num_rounds_y);
-    const fe_t eval_Z = inner_final[2 * k + 1];
-    std::vector<fe_t> X;
-    X.push_back(fe_one<S>());
-    X.insert(X.end(), it.publics.begin(), it.publics.end());
-    const fe_t eval_X = sparse_poly_evaluate(num_rounds_y - 1, X, it.r_y.data() + 1);
-    const fe_t denom = fe_sub<S>(fe_one<S>(), it.r_y[0]);
-    if (fe_is_zero(denom)) throw Error(SP_ERR_DIVISION_BY_ZERO, "DivisionByZero");
-    eval_W[k] = fe_mul<S>(fe_sub<S>(eval_Z, fe_mul<S>(it.r_y[0], eval_X)), fe_inv_vartime<S>(denom));
+    eval_W[k] = eval_W_from(inner_final[2 * k + 1], it.r_y.data(), num_rounds_y, it.publics, no_challenges);
   });
   phase(4);
   // :423-436 blind, commit to eval_W, PCS::prove. Per proof: the blind and the commitment of eval_W (a host walk of two table
@@ -1790,7 +1620,7 @@ std::vector<ProofBuf> prove_batch(const SpartanProverKey& pk, SpartanPrepSNARK* 
 }
 
 // ---- R1CSShape::is_sat (src/r1cs/mod.rs:358-394) on a prepared state ----------------------------------------------------------------------------
-// z = [W | 1 | X] formed as prove forms it (src/spartan.rs:246-253) but in a table of its own, the row check on the device (sp_shape_is_sat), then
+// z = [W | 1 | X] with the tail prove writes (z_tail; src/spartan.rs:246-253) but in a table of its own, the row check on the device (sp_shape_is_sat), then
 // `res_comm` (:379): PCS::commit of the rows committed at prep_prove - shared, then precommitted - with the stored blinds and the state's is_small,
 // compared with comm_W_fixed (or with `expect_comm`, the same number of rows, when the caller holds the commitment it wants checked). For circuits with
 // verifier challenges the caller supplies them - its last prove's, or any: the constraints hold for every challenge - and the rest witness comes
@@ -1806,15 +1636,13 @@ bool is_sat(const SpartanProverKey& pk, SpartanPrepSNARK& ps, const uint64_t* pu
   ck(sp_ctx_bind_thread(ctx), "device");
   if (!ps.sat_z) ck(sp_table_zeros(ctx, pk.num_cols, (size_t)-1, (size_t)-1, &ps.sat_z), "alloc z (is_sat)");
   ck(sp_table_copy(ctx, ps.sat_z, 0, ps.W, 0, M), "z <- W");
+  std::vector<fe_t> ch(d.num_challenges);
+  if (d.num_challenges) memcpy(ch.data(), challenges, d.num_challenges * sizeof(fe_t));
   if (d.num_challenges) {  // circuit.synthesize(.., Some(&challenges)) (bellpepper/r1cs.rs:443-461); the rest segment goes into z, not into W
-    std::vector<fe_t> rest(d.num_rest_unpadded + 1);
-    if (synth(synth_user, challenges, d.num_challenges, u64p(rest.data())) != 0) throw Error(SP_ERR_INTERNAL, "SynthesisError: the circuit's synthesize callback failed");
+    const std::vector<fe_t> rest = synthesize_rest(synth, synth_user, challenges, d.num_challenges, d.num_rest_unpadded);
     if (d.num_rest_unpadded) ck(sp_table_write(ctx, ps.sat_z, fixed, u64p(rest.data()), d.num_rest_unpadded), "z rest");
   }
-  std::vector<fe_t> tail(pk.num_extra);
-  tail[0] = fe_one<S>();
-  for (size_t i = 0; i < npub; ++i) tail[1 + i] = fe_from_u64<S>(publics_u64[i]);
-  if (d.num_challenges) memcpy(&tail[1 + npub], challenges, d.num_challenges * sizeof(fe_t));
+  const std::vector<fe_t> tail = z_tail(pk.num_extra, publics_from_u64(publics_u64, npub), ch);
   ck(sp_table_write(ctx, ps.sat_z, M, u64p(tail.data()), tail.size()), "z tail");
   ck(sp_shape_is_sat(ctx, pk.S, ps.sat_z, nullptr, nullptr, report), "shape_is_sat");
   // res_comm

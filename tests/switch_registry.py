@@ -66,7 +66,7 @@ _ENTRIES = [
            "walk order of the short columns: unsorted, or sorted inside windows of POLYABC_WINDOW columns"),
     Switch("POLYABC_WINDOW", "4096", PATH, {"1": _child(SWITCHED), "777": _child(SWITCHED)}, "spartan2_amd/csrc/capi_sparse.hip:454",
            "window of POLYABC_ORDER=window (read only with it); any value > 0. 777 leaves the last window partly full."),
-    Switch("ROUND0_PRODUCTS", "1", PATH, {"0": _child(SWITCHED)}, "spartan2_amd/host/spartan_snark.cpp:233",
+    Switch("ROUND0_PRODUCTS", "1", PATH, {"0": _child(SWITCHED)}, "spartan2_amd/host/spartan_snark.cpp:227",
            "outer round 1 evaluated straight from Az, Bz, Cz instead of the products of the matrix-vector pass"),
     Switch("TAIL_LOG2", "16", PATH, {"10": _child(SWITCHED), "15": _child(SWITCHED)}, "spartan2_amd/csrc/capi_core.hip:1013",
            "table length from which the resident sum-check tail takes over, clamped to 2^10..2^16"),
@@ -81,18 +81,18 @@ _ENTRIES = [
     Switch("BATCHED_AHEAD", "1", PATH, {"0": _child(SWITCHED)}, "spartan2_amd/csrc/capi_core.hip:2168", "batched rounds never queued ahead of the round hook"),
     Switch("HOST_SC", "1", PATH, {"0": _child(SWITCHED)}, "spartan2_amd/host/neutronnova_zk.cpp:947",
            "relaxed-Spartan sum-checks of the verifier-circuit instance on the device"),
-    Switch("PREFIX_CACHE", "0", PATH, {"1": _child(SWITCHED)}, "spartan2_amd/host/spartan_snark.cpp:177", "FLAG_PREFIX_CACHE: the transcript prefix kept per prep"),
-    Switch("DELTA_ROUNDS_LEFT", "17", PATH, {"1": _child(SWITCHED), "64": _child(SWITCHED)}, "spartan2_amd/host/spartan_snark.cpp:53",
+    Switch("PREFIX_CACHE", "0", PATH, {"1": _child(SWITCHED)}, "spartan2_amd/host/spartan_snark.cpp:220", "FLAG_PREFIX_CACHE: the transcript prefix kept per prep"),
+    Switch("DELTA_ROUNDS_LEFT", "17", PATH, {"1": _child(SWITCHED), "64": _child(SWITCHED)}, "spartan2_amd/host/spartan_snark.cpp:71",
            "inner-sum-check rounds left when the opening's delta MSM is issued (>= 1); above the round count it falls through to the publish"),
     Switch("ZVEC_ARMED", "1", PATH, {"0": _child(SWITCHED)}, "spartan2_amd/csrc/capi_group.hip:1523", "z_vec launched behind the scale, not armed ahead"),
     Switch("WALK_GROUPS", "1", PATH, {"0": _child(SWITCHED)}, "spartan2_amd/csrc/capi_group.hip:1860", "multi-mul walks joined once on the device"),
     Switch("HOST_T16", "1", PATH, {"0": _child(SWITCHED)}, "spartan2_amd/csrc/capi_group.hip:441", "no host copies of the 16-bit-window tables: the split commitments are refused and the verifier circuit's round commitments take the device walk"),
-    Switch("LZ_DIRECT", "0", PATH, {"1": (Cover(DRIVER_PATHS, 'monkeypatch.setenv("SPARTAN_LZ_DIRECT", "1")'),)}, "spartan2_amd/host/spartan_snark.cpp:175",
+    Switch("LZ_DIRECT", "0", PATH, {"1": (Cover(DRIVER_PATHS, 'monkeypatch.setenv("SPARTAN_LZ_DIRECT", "1")'),)}, "spartan2_amd/host/spartan_snark.cpp:220",
            "comm_LZ in the reference's order"),
     Switch("MAIL_DEV", "1", PATH, {"0": (Cover(DRIVER_PATHS, 'monkeypatch.setenv("SPARTAN_MAIL_DEV", "0")'),)}, "spartan2_amd/csrc/capi_core.hip:217",
            "mailbox in host memory (read when a context is created)"),
     Switch("PREP_TABLES", "lazy", PATH, {v: (Cover(DRIVER_PATHS, 'for mode in ("off", "sync", "prep"):'),) for v in ("off", "sync", "prep")},
-           "spartan2_amd/host/spartan_snark.cpp:215", "when the row tables of the prepared witness are built (read at every prep)"),
+           "spartan2_amd/host/spartan_snark.cpp:225", "when the row tables of the prepared witness are built (read at every prep)"),
     Switch("KEY_TABLES", "1", PATH,
            {"0": (Cover(DRIVER_PATHS, 'monkeypatch.setenv("SPARTAN_KEY_TABLES", "0")'),
                   Cover("tests/test_gpu_group.py::test_hyrax_prove_is_the_oracles_pcs_prove", '(16, "0")'))},
@@ -110,12 +110,12 @@ _ENTRIES = [
     Switch("WALKERS_IDLE", "0", SCHEDULING, {"1": _child(SCHEDULING_RUN)}, "spartan2_amd/csrc/walk_pool.hpp:153", "walkers in SCHED_IDLE"),
     Switch("HOST_T16_THP", "1", SCHEDULING, {"0": _child(SCHEDULING_RUN)}, "spartan2_amd/csrc/capi_group.hip:465", "no huge pages for the host tables"),
     # ---- trace -----------------------------------------------------------------------------------------------------------------------------------------
-    Switch("HOST_LAPS", "unset", TRACE, {"1": _child(TRACE_RUN), "2": _child(SWITCHED)}, "spartan2_amd/host/spartan_snark.cpp:1028 and ten more",
+    Switch("HOST_LAPS", "unset", TRACE, {"1": _child(TRACE_RUN), "2": _child(SWITCHED)}, "spartan2_amd/host/spartan_snark.cpp:1168 and ten more",
            "laps on stderr; some sites take any value, others only 1 or 2 (batched rounds); adds stream_sync calls mid-path"),
-    Switch("PREP_TRACE", "unset", TRACE, {"1": _child(TRACE_RUN)}, "spartan2_amd/host/spartan_snark.cpp:230", "prep phases on stderr, one synchronise"),
+    Switch("PREP_TRACE", "unset", TRACE, {"1": _child(TRACE_RUN)}, "spartan2_amd/host/spartan_snark.cpp:226", "prep phases on stderr, one synchronise"),
     Switch("ROUND_TRACE", "0", TRACE, {"1": _child(TRACE_RUN, SWITCHED)}, "spartan2_amd/csrc/capi_core.hip:1002", "one line per sum-check round"),
     Switch("SLOWPATH_LOG", "unset", TRACE, {"1": _child(TRACE_RUN)}, "spartan2_amd/csrc/capi_core.hip:27", "waits that fell back to the slow path"),
-    Switch("SLOW_PROVE_MS", "0", TRACE, {"0.001": _child(TRACE_RUN)}, "spartan2_amd/host/spartan_snark.cpp:1537", "phases of proves slower than t ms"),
+    Switch("SLOW_PROVE_MS", "0", TRACE, {"0.001": _child(TRACE_RUN)}, "spartan2_amd/host/spartan_snark.cpp:2350", "phases of proves slower than t ms"),
 ]
 
 SWITCHES = {s.name: s for s in _ENTRIES}

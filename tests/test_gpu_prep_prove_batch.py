@@ -2,6 +2,11 @@
 commitments through sp_hyrax_commit_batch and, on request, the cached products through sp_multiply_vec_chunked. State k must be WORD FOR WORD the state the CPU
 oracle's prep_prove makes of witness k with tape k - commitment rows, cached Az / Bz / Cz, tape blocks used - and must prove, alone and in a batch,
 to the oracle's proof. The per-state flags and the loop of single calls give the same states."""
+import os
+import re
+import subprocess
+import sys
+
 import numpy as np
 import pytest
 
@@ -199,3 +204,69 @@ def test_a_wrong_witness_names_its_state_and_the_key_stays_usable(ctx):
     assert gsp.prep_prove_batch(prep_tapes, witnesses=insts) == prep_used
     check_exports(gsp, exports)
     gsp.close()
+
+
+def test_prep_prove_on_a_short_tape_fails_as_it_always_did_and_the_key_stays_usable(ctx):
+    """prep_prove is the count-1 case of the batch driver: its errors still carry no batch prefix (code and message recorded before the two drivers
+    became one), and the same entry point through ss_prep_prove_batch with count 1 still names the state"""
+    inst = frontend.synthetic_circuit(witness_seed=0, **SYNTHETIC["5x7"])
+    tape = ol.make_tape(4900, 1024)
+    osp = ol.OracleSpartan(inst)
+    used = osp.prep_prove(tape)
+    assert used > 0
+    gsp = host.SpartanSNARK(ctx, inst)
+    with pytest.raises(hip.SpartanHipError) as e:
+        gsp.prep_prove(tape[:0])
+    assert str(e.value) == "rc=-5: random tape exhausted"
+    assert gsp.ps is None
+    with pytest.raises(hip.SpartanHipError) as e:
+        gsp.prep_prove_batch([tape[:0]], witnesses=[inst])
+    assert str(e.value) == "rc=-5: prep_prove_batch: state 0: random tape exhausted"
+    assert gsp.prep_prove(tape) == used
+    for g, w in zip(gsp.prep_export(), osp.prep_export()):
+        assert (g == w).all()
+    ptape = ol.make_tape(4901, 4096)
+    words, pused, _ = gsp.prove(ptape)
+    want, want_used, _ = osp.prove(ptape)
+    assert pused == want_used and (words == want).all()
+    gsp.close()
+
+
+_TRACE_CHILD = """
+import ctypes, sys
+sys.path.insert(0, {root!r}); sys.path.insert(0, {tests!r})
+import numpy as np
+import oracle_lib as ol
+from spartan2_amd import frontend, hip, host
+ctx = hip.Context(0)
+inst = frontend.synthetic_circuit(n_groups=5, seed=7, num_public=2)
+gsp = host.SpartanSNARK(ctx, inst)
+tape = ol.make_tape(4910, 1024)
+sys.stderr.write("single\\n"); sys.stderr.flush()
+gsp.prep_prove(tape)
+sys.stderr.write("batch of one\\n"); sys.stderr.flush()
+w = np.ascontiguousarray(inst.witness, dtype=np.uint64)
+wptr = (hip.c_u64p * 1)(hip.p64(w))
+tptr = (hip.c_u8p * 1)(hip.p8(tape))
+tblk = (ctypes.c_size_t * 1)(tape.shape[0])
+pss = (ctypes.c_void_p * 1)()
+rc = host.lib().ss_prep_prove_batch(gsp.pk, wptr, ctypes.c_size_t(len(w)), ctypes.c_size_t(1), 1, tptr, tblk, None, pss, None)
+assert rc == 0, host.lib().ss_last_error()
+host.lib().ss_prep_free(ctypes.c_void_p(pss[0]))
+gsp.close(); ctx.close()
+"""
+
+
+def test_the_prep_trace_lines_of_the_single_and_the_count_one_batch_entry_points():
+    """SPARTAN_PREP_TRACE=1 in a child process (the lines go to the C library's stderr): ss_prep_prove prints the `prep_prove:` line, ss_prep_prove_batch with count 1 the
+    `prep_prove_batch(1):` line - the forms recorded before the two drivers became one"""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = _TRACE_CHILD.format(root=root, tests=os.path.join(root, "tests"))
+    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, SPARTAN_PREP_TRACE="1"), capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-1500:]
+    num = r"\d+\.\d{3}"
+    phases = rf"witness {num} commit {num} tables {num} matvec {num} scratch {num} total {num} ms"
+    lines = [l for l in r.stderr.splitlines() if l.startswith(("single", "batch of one", "prep_prove"))]
+    assert len(lines) == 4 and lines[0] == "single" and lines[2] == "batch of one", lines
+    assert re.fullmatch(rf"prep_prove: {phases}", lines[1]), lines[1]
+    assert re.fullmatch(rf"prep_prove_batch\(1\): {phases}", lines[3]), lines[3]

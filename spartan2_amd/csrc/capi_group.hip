@@ -954,13 +954,8 @@ int sp_hyrax_commit_batch(sp_ctx* c, const sp_ck* ck, size_t count, const sp_tab
   char* drow = (char*)c->workspace(sp_ctx::WS_COMMIT_ROWS, chunk_rows * (sizeof(jac_t) + 4));  // [row sums | flags]: one copy
   if (!canon || !drow) return SP_ERR_NO_DEVICE;
   const size_t pinned_bytes = chunk_rows * (sizeof(jac_t) + 4);
-  if (c->h_opening_bytes < pinned_bytes) {  // the batched opening's pinned buffer (grow-only; cleared below once the row sums are copied out, as that call clears it)
-    if (c->h_opening) hipHostFree(c->h_opening);
-    c->h_opening = nullptr;
-    c->h_opening_bytes = 0;
-    SP_HIP(hipHostMalloc(&c->h_opening, pinned_bytes + pinned_bytes / 4));
-    c->h_opening_bytes = pinned_bytes + pinned_bytes / 4;
-  }
+  // the batched opening's pinned buffer (grow-only; cleared below once the row sums are copied out, as that call clears it)
+  if (int rc_pin = sp::opening_pinned_reserve(c, pinned_bytes)) return rc_pin;
   std::vector<jac_t> all_rows(total);
   bool blinds_done = false;
   std::vector<jac_t> hb;
@@ -2561,18 +2556,8 @@ static int announce_impl(sp_ctx* c, const sp_ck* ck, const uint64_t* comm_rows_a
       S->failed = true;
     else
       S->delta_launched = true;
-    static const char* b = "poly_commitment_begin";  // HyraxCommitment::to_transcript_bytes (hyrax_pc.rs:714-729)
-    static const char* e = "poly_commitment_end";
     S->hashed.init();
-    S->hashed.update(reinterpret_cast<const uint8_t*>("poly_com"), 8);
-    S->hashed.update(reinterpret_cast<const uint8_t*>(b), strlen(b));
-    uint8_t buf[64 * 16];
-    for (size_t i = 0; i < S->comm.size(); i += 16) {
-      const size_t m = S->comm.size() - i < 16 ? S->comm.size() - i : 16;
-      for (size_t k = 0; k < m; ++k) hp_point_bytes(S->comm[i + k], buf + 64 * k);
-      S->hashed.update(buf, 64 * m);
-    }
-    S->hashed.update(reinterpret_cast<const uint8_t*>(e), strlen(e));
+    sp::absorb_commitment(S->hashed, S->comm.data(), S->comm.size());
     for (size_t i = 0; i < S->cols; ++i) S->dvec[i] = fe_from_uniform<spk::SF>(S->rng.data() + 64 * i);
     // the mask vector to the device, behind delta's walk on the auxiliary stream (needed when the IPA's challenge is drawn: z_vec = r LZ + d)
     fe_t* stage = reinterpret_cast<fe_t*>(c->h_pinned_vec) + c->h_pinned_vec_cols;
@@ -2658,19 +2643,7 @@ int sp_hyrax_prove(sp_ctx* c, const sp_ck* ck, const sp_ck* ck_eval, sp_transcri
   }
   if (!hashed_ahead) {
     sp::Keccak256State* hp = &hashed;
-    c->pcs_worker->submit([hp, comm, rows] {
-      static const char* b = "poly_commitment_begin";  // HyraxCommitment::to_transcript_bytes (hyrax_pc.rs:714-729)
-      static const char* e = "poly_commitment_end";
-      hp->update(reinterpret_cast<const uint8_t*>("poly_com"), 8);
-      hp->update(reinterpret_cast<const uint8_t*>(b), strlen(b));
-      uint8_t buf[64 * 16];
-      for (size_t i = 0; i < rows; i += 16) {
-        const size_t m = rows - i < 16 ? rows - i : 16;
-        for (size_t k = 0; k < m; ++k) hp_point_bytes(comm[i + k], buf + 64 * k);
-        hp->update(buf, 64 * m);
-      }
-      hp->update(reinterpret_cast<const uint8_t*>(e), strlen(e));
-    });
+    c->pcs_worker->submit([hp, comm, rows] { sp::absorb_commitment(*hp, comm, rows); });
   }
   // beta = ck_c <R, d> + h r_beta (ipa.rs:149) is two table walks on the host, ~11 us each. With the helper thread polling (an announced opening keeps it
   // so) and not busy with the commitment's hashing, h's walk runs beside this thread's compare / <R, d> and ck_c's beside its collection of the two device
@@ -2867,20 +2840,8 @@ int sp_hyrax_prove(sp_ctx* c, const sp_ck* ck, const sp_ck* ck_eval, sp_transcri
   lap("join hashing");
   tr->t.h = hashed;
   // (5) InnerProductArgumentLinear::prove, transcript part (ipa.rs:132-158)
-  {
-    static const char* ds = "inner product argument (linear)";
-    tr->t.dom_sep(reinterpret_cast<const uint8_t*>(ds), strlen(ds));
-    uint8_t b[128];
-    hp_point_bytes(comm_LZ, b);
-    hp_point_bytes(comm_eval, b + 64);
-    tr->t.absorb(reinterpret_cast<const uint8_t*>("U"), 1, b, 128);
-    hp_point_bytes(delta, b);
-    tr->t.absorb(reinterpret_cast<const uint8_t*>("delta"), 5, b, 64);
-    hp_point_bytes(beta, b);
-    tr->t.absorb(reinterpret_cast<const uint8_t*>("beta"), 4, b, 64);
-  }
   fe_t rr;
-  if (!tr->t.squeeze<SF>(reinterpret_cast<const uint8_t*>("r"), 1, &rr)) return fail(SP_ERR_INTERNAL_TRANSCRIPT, "transcript round counter overflow");
+  if (!sp::ipa_transcript(tr->t, comm_LZ, comm_eval, delta, beta, &rr)) return fail(SP_ERR_INTERNAL_TRANSCRIPT, "transcript round counter overflow");
   // (6) z_vec = r * LZ + d, z_delta = r * r_LZ + r_delta, z_beta = r * blind_eval + r_beta (ipa.rs:160-168)
   memcpy(out, &delta, sizeof(aff_t));
   memcpy(out + 8, &beta, sizeof(aff_t));
@@ -3198,4 +3159,39 @@ namespace sp {
 jac_t ck_table_mul_host(const sp_ck* ck, size_t t, const fe_t& scalar) { return ck_mul_host(ck, t, scalar); }
 void eq_evals_host(const fe_t* r, size_t k, fe_t* out) { eq_table_host(r, k, out); }
 void point_transcript_bytes(const aff_t& a, uint8_t out[64]) { hp_point_bytes(a, out); }
+void absorb_commitment(Keccak256State& h, const aff_t* comm, size_t rows) {
+  static const char* b = "poly_commitment_begin";
+  static const char* e = "poly_commitment_end";
+  h.update(reinterpret_cast<const uint8_t*>("poly_com"), 8);
+  h.update(reinterpret_cast<const uint8_t*>(b), strlen(b));
+  uint8_t buf[64 * 16];
+  for (size_t i = 0; i < rows; i += 16) {
+    const size_t m = rows - i < 16 ? rows - i : 16;
+    for (size_t k = 0; k < m; ++k) hp_point_bytes(comm[i + k], buf + 64 * k);
+    h.update(buf, 64 * m);
+  }
+  h.update(reinterpret_cast<const uint8_t*>(e), strlen(e));
+}
+bool ipa_transcript(Transcript& t, const aff_t& comm_LZ, const aff_t& comm_eval, const aff_t& delta, const aff_t& beta, fe_t* r) {
+  static const char* ds = "inner product argument (linear)";
+  t.dom_sep(reinterpret_cast<const uint8_t*>(ds), strlen(ds));
+  uint8_t b[128];
+  hp_point_bytes(comm_LZ, b);
+  hp_point_bytes(comm_eval, b + 64);
+  t.absorb(reinterpret_cast<const uint8_t*>("U"), 1, b, 128);
+  hp_point_bytes(delta, b);
+  t.absorb(reinterpret_cast<const uint8_t*>("delta"), 5, b, 64);
+  hp_point_bytes(beta, b);
+  t.absorb(reinterpret_cast<const uint8_t*>("beta"), 4, b, 64);
+  return t.squeeze<spk::SF>(reinterpret_cast<const uint8_t*>("r"), 1, r);
+}
+int opening_pinned_reserve(sp_ctx* c, size_t bytes) {
+  if (c->h_opening_bytes >= bytes) return SP_OK;
+  if (c->h_opening) hipHostFree(c->h_opening);
+  c->h_opening = nullptr;
+  c->h_opening_bytes = 0;
+  SP_HIP(hipHostMalloc(&c->h_opening, bytes + bytes / 4));
+  c->h_opening_bytes = bytes + bytes / 4;
+  return SP_OK;
+}
 }  // namespace sp

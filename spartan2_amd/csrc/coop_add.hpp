@@ -1,5 +1,5 @@
 // The block-cooperative point addition of the latency kernels (CoopAdd / xyzz_add_block4) and the XYZZ shuffle, shared by the translation units that walk
-// window tables (kernels_msm.hpp in capi_group.hip, kernels_opening_batch.hpp in capi_opening_batch.hip).
+// window tables (kernels_msm.hpp in capi_group.hip, kernels_opening_batch.hpp, the one header of both forms of the batched opening, in capi_opening_batch.hip).
 #pragma once
 #include "curve.hpp"
 #include "device_utils.hpp"

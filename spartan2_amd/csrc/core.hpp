@@ -235,7 +235,8 @@ struct sp_ctx {
   size_t h_pcs_bytes = 0;
   hipEvent_t pcs_ev = nullptr;
   sp::Worker* pcs_worker = nullptr;
-  // sp_hyrax_prove_batch (capi_opening_batch.hip): pinned staging of its uploads and landing buffer of its results, grow-only, and its event
+  // sp_hyrax_prove_batch and the same opening begun ahead (capi_opening_batch.hip, one Plan of the buffers for both): pinned staging of the uploads and
+  // landing buffer of the results, grown by sp::opening_pinned_reserve alone (group_common.hpp; sp_hyrax_commit_batch lands its row sums here too), and its event
   void* h_opening = nullptr;
   size_t h_opening_bytes = 0;
   hipEvent_t opening_ev = nullptr;
@@ -256,7 +257,7 @@ struct sp_ctx {
          WS_SAT_PRODUCTS, WS_SAT_BITMAP, WS_SAT_SUMMARY,  // sp_shape_is_sat / sp_r1cs_residual: Az | Bz | Cz, failure bitmaps, (count, first) pairs
          WS_MATEVAL_PARTIALS, WS_MATEVAL_TICKETS, WS_MATEVAL_OUT,  // sp_shape_matrix_evals_batched: block sums, arrival counters, the 3 results per pair
          WS_LOCKSTEP_EQ, WS_LOCKSTEP_PARTIALS, WS_LOCKSTEP_PARAMS,  // the lockstep sum-checks: eq pyramids per instance, block partials, taus / (lo_eff, hi_eff) per round
-         WS_OPENING_BLOCKS, WS_OPENING_VECS, WS_OPENING_PARAMS, WS_OPENING_WALK,  // sp_hyrax_prove_batch: uniform blocks | d, LZ, z | instances, points | tickets, block sums, results
+         WS_OPENING_BLOCKS, WS_OPENING_VECS, WS_OPENING_PARAMS, WS_OPENING_WALK,  // the batched opening's Plan (capi_opening_batch.hip): uniform blocks | d, LZ, z | instances, points | tickets, block sums, results, <R, d> block sums
          WS_POLYABC_BATCH_EQ, WS_POLYABC_BATCH_PYRAMIDS, WS_POLYABC_BATCH_PARTIALS, WS_POLYABC_BATCH_TICKETS,  // sp_poly_abc_batch: a chunk's interleaved eq tables, its eq pyramids, the long columns' partial triples, their arrival counters
          WS_PER_LANE,
          WS_SLOTS = 2 * WS_PER_LANE };  // lane 1 = the auxiliary stream used by asynchronous MSM jobs

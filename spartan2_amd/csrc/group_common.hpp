@@ -85,6 +85,12 @@ int ck_key_tables(sp_ctx* c, const sp_ck* ck);  // 0 = ready, 1 = not available 
 jac_t ck_table_mul_host(const sp_ck* ck, size_t t, const fe_t& scalar);  // table t of a key (t = n_tables - 1: h) times a scalar
 void eq_evals_host(const fe_t* r, size_t k, fe_t* out);                 // eq table of k variables, r[0] on the index MSB (2^k elements)
 void point_transcript_bytes(const aff_t& a, uint8_t out[64]);            // x BE || y BE (src/provider/traits.rs:288-305)
+// transcript.absorb(b"poly_com", comm) (hyrax_pc.rs:410) into a sponge the caller chose: "poly_com", then HyraxCommitment::to_transcript_bytes (:714-729)
+void absorb_commitment(Keccak256State& h, const aff_t* comm, size_t rows);
+// InnerProductArgumentLinear::prove's transcript part (ipa.rs:132-158): the dom-sep, U = comm_LZ || comm_eval, delta, beta, the squeeze of r; false =
+// the round counter overflowed
+bool ipa_transcript(Transcript& t, const aff_t& comm_LZ, const aff_t& comm_eval, const aff_t& delta, const aff_t& beta, fe_t* r);
+int opening_pinned_reserve(sp_ctx* c, size_t bytes);  // c->h_opening holds at least `bytes` (grow-only, a quarter of headroom)
 // capi_pippenger.hip: the general (multi-block) Pippenger for caller-supplied bases; window = 0 -> pippenger_window(n)
 int pippenger_window(size_t n);
 int msm_pippenger(sp_ctx* c, const fe_t* d_canon, const aff_t* d_bases, size_t n, bool full_width, int window, jac_t* result);

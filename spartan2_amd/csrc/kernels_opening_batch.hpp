@@ -1,12 +1,14 @@
 // Kernels of sp_hyrax_prove_batch (capi_opening_batch.hip): `count` instances of HyraxPCS::prove (hyrax_pc.rs:387-478) with
 // InnerProductArgumentLinear::prove (ipa.rs:125-170) inside, on ONE commitment key, every device stage ONE launch with the instance on blockIdx.y:
 //   k_ob_mask     d_k = from_uniform(blocks_k) (ipa.rs:139-145) written once, and the block sums of <R_k, d_k>, R_k = eq(column point k) (:148)
+//   k_ob_dvec     k_ob_mask's first half, d_k alone: a batch opened ahead draws the mask vectors before the evaluation point exists
+//   k_ob_ip       its second half, the block sums of <R_k, d_k> from the stored d_k once the point is known (the same sums, block by block)
 //   k_ob_rowmat   LZ_k = L_k^T W_k (bind_with_delayed, hyrax_pc.rs:38-54), L_k = eq(row point k) formed in LDS from the point
 //   k_ob_walk     the table walk over one key's window tables for 2 count scalar vectors: delta_k = <d_k, ck> + r_delta_k h (ipa.rs:147), reduced
 //                 from the uniform blocks as k_multi_mul_wide's raw64 form does, and comm_LZ_k = <LZ_k, ck> + r_LZ_k h (hyrax_pc.rs:454-455)
 //   k_ob_z        z_vec_k = r_k LZ_k + d_k (ipa.rs:160-163)
 // k_ob_walk takes a vector base, so that one launch covers the delta vectors alone (base 0) or the comm_LZ vectors alone (base count): a batch opened
-// ahead (sp_hyrax_prove_batch_begin / _rows / _finish) walks them at different times. Its two halves of k_ob_mask are in kernels_opening_ahead.hpp.
+// ahead (sp_hyrax_prove_batch_begin / _rows / _finish) walks them at different times.
 // The walk is k_multi_mul_wide (kernels_msm.hpp) with the per-block item layout, CoopAdd / xyzz_add_block4 and the last-block join unchanged; what is
 // new is the indexing: vector v = blockIdx.y has its own scalars, block-sum area, ticket and result, and the result is a plain store into device
 // memory that the host fetches with one copy for all vectors. Results are group elements compared as canonical affine points and exact field
@@ -22,7 +24,7 @@ constexpr int OB_WALK_ITEMS = 1024;       // (scalar, digit) items per block of 
 constexpr int OB_WALK_MAX_BLOCKS = 128;   // block sums the last block of a vector joins in one pass: 4096 scalars
 constexpr int OB_ROW_BITS_MAX = 10;       // row variables whose eq table fits the block's LDS copy
 constexpr int OB_RMV_COLS = 8, OB_RMV_THREADS = 512, OB_RMV_ROWS_PER_PASS = OB_RMV_THREADS / OB_RMV_COLS;
-constexpr int OB_STREAM_THREADS = 256;    // k_ob_mask / k_ob_z: one element a thread
+constexpr int OB_STREAM_THREADS = 256;    // k_ob_mask / k_ob_dvec / k_ob_ip / k_ob_z: one element a thread
 
 // one instance, as the kernels see it (a small device array, uploaded once per call; the two blinds make it mask material: wiped with the blocks)
 struct ObInst {
@@ -46,10 +48,21 @@ __device__ __forceinline__ fe_t ob_eq_at(const fe_t* __restrict__ p, int k, unsi
   return w;
 }
 
+// ip_part[instance][block] = the sum of the block's 256 terms: an LDS tree over halves 128, 64 .. 1 (exact field sums: the order shows in no result)
+__device__ __forceinline__ void ob_block_sum(fe_t term, fe_t* __restrict__ ip_part) {
+  __shared__ fe_t s[OB_STREAM_THREADS];
+  s[threadIdx.x] = term;
+  __syncthreads();
+  for (int off = OB_STREAM_THREADS / 2; off >= 1; off >>= 1) {
+    if ((int)threadIdx.x < off) s[threadIdx.x] = fe_add<SF>(s[threadIdx.x], s[threadIdx.x + off]);
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) ip_part[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = s[0];
+}
+
 // grid (ceil(cols / 256), count): d[k][i] and ip_part[k][block] = sum over the block's columns of R_k[i] d_k[i]; the host adds the <= 16 block sums
 __global__ void __launch_bounds__(OB_STREAM_THREADS) k_ob_mask(const ObInst* __restrict__ inst, unsigned cols, int nvr, int ncv, fe_t* __restrict__ d,
                                                                fe_t* __restrict__ ip_part) {
-  __shared__ fe_t s[OB_STREAM_THREADS];
   const ObInst& I = inst[blockIdx.y];
   const unsigned i = blockIdx.x * OB_STREAM_THREADS + threadIdx.x;
   fe_t term = fe_zero();
@@ -58,13 +71,24 @@ __global__ void __launch_bounds__(OB_STREAM_THREADS) k_ob_mask(const ObInst* __r
     d[(size_t)blockIdx.y * cols + i] = di;
     term = fe_mul<SF>(ob_eq_at(I.point + nvr, ncv, i), di);
   }
-  s[threadIdx.x] = term;
-  __syncthreads();
-  for (int off = OB_STREAM_THREADS / 2; off >= 1; off >>= 1) {
-    if ((int)threadIdx.x < off) s[threadIdx.x] = fe_add<SF>(s[threadIdx.x], s[threadIdx.x + off]);
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) ip_part[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = s[0];
+  ob_block_sum(term, ip_part);
+}
+
+// grid (ceil(cols / 256), count): d[k][i] alone, for a caller that does not know R yet
+__global__ void __launch_bounds__(OB_STREAM_THREADS) k_ob_dvec(const ObInst* __restrict__ inst, unsigned cols, fe_t* __restrict__ d) {
+  const unsigned i = blockIdx.x * OB_STREAM_THREADS + threadIdx.x;
+  if (i >= cols) return;
+  d[(size_t)blockIdx.y * cols + i] = fe_from_uniform<SF>(inst[blockIdx.y].blocks + 64 * (size_t)i);
+}
+
+// grid (ceil(cols / 256), count): ip_part[k][block] as k_ob_mask forms it, d as k_ob_dvec left it
+__global__ void __launch_bounds__(OB_STREAM_THREADS) k_ob_ip(const ObInst* __restrict__ inst, unsigned cols, int nvr, int ncv, const fe_t* __restrict__ d,
+                                                             fe_t* __restrict__ ip_part) {
+  const ObInst& I = inst[blockIdx.y];
+  const unsigned i = blockIdx.x * OB_STREAM_THREADS + threadIdx.x;
+  fe_t term = fe_zero();
+  if (i < cols) term = fe_mul<SF>(ob_eq_at(I.point + nvr, ncv, i), d[(size_t)blockIdx.y * cols + i]);
+  ob_block_sum(term, ip_part);
 }
 
 // grid (ceil(cols / 8), count), 512 threads: k_rowmat_vec_tall's shape (kernels_bulk.hpp) - lane = (row-lane 0..7, column 0..7), a wave reads eight

@@ -13,7 +13,7 @@ import spill_report  # noqa: E402
 from spartan2_amd import hip, host  # noqa: E402
 
 KERNELS_HEADER = os.path.join(ROOT, "spartan2_amd", "csrc", "kernels_opening_batch.hpp")
-STREAMING = ("k_ob_mask", "k_ob_rowmat", "k_ob_z")
+STREAMING = ("k_ob_mask", "k_ob_dvec", "k_ob_ip", "k_ob_rowmat", "k_ob_z")
 WALK = "k_ob_walk"
 
 

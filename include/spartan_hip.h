@@ -357,6 +357,24 @@ int sp_msm_shared_weights(sp_ctx* ctx, const uint64_t* weights, size_t n, const 
 /* the same on the context's auxiliary stream and its workspaces: callable from a helper thread beside the owner's calls on the main stream (fold_commitments,
  * src/neutronnova_zk.rs:1204-1211, beside fold_witnesses / the layer folds: the group work needs the weights alone) */
 int sp_msm_shared_weights_aux(sp_ctx* ctx, const uint64_t* weights, size_t n, const uint64_t* bases_rows_aff, size_t rows, uint64_t* out_rows_aff);
+/* `groups` shared-weights MSMs of one shape in one pass (the commitment folds of several proofs of one key): weights [groups][n], bases [groups][rows][n],
+ * out [groups][rows]; out[g][r] is word for word what sp_msm_shared_weights(ctx, weights + 4 n g, n, bases of group g, rows, ..) writes. One upload, one
+ * sign fold and one digit sort for all groups, bucket and window sums in chunks of whole groups of at most sp_msm_shared_weights_group_rows() rows a
+ * launch, one window Horner pass (host threads up to 128 rows in all, one launch above), one copy back, one synchronisation. Below 64 rows in all the
+ * single call's latency form runs once per group. Null arguments are refused (SP_ERR_INVALID_INPUT_LENGTH) before anything is touched; groups == 0 or
+ * rows == 0 does nothing; n == 0 zeroes the output. _aux: the auxiliary stream and its workspaces, as sp_msm_shared_weights_aux.
+ * sp_msm_shared_weights_group_rows(): the rows one bucket launch takes at most (where the groups are cut into chunks). */
+int sp_msm_shared_weights_grouped(sp_ctx* ctx, const uint64_t* weights, size_t n, const uint64_t* bases_rows_aff, size_t rows, size_t groups, uint64_t* out_rows_aff);
+int sp_msm_shared_weights_grouped_aux(sp_ctx* ctx, const uint64_t* weights, size_t n, const uint64_t* bases_rows_aff, size_t rows, size_t groups, uint64_t* out_rows_aff);
+size_t sp_msm_shared_weights_group_rows(void);
+/* the same as sp_msm_shared_weights_grouped with the side that runs the window Horner forced, for measuring where the threshold lies (same words either
+ * way): flags = 0 by row count, SP_MSM_GROUPED_HORNER_HOST = host threads, SP_MSM_GROUPED_HORNER_DEVICE = one launch; another value is refused. While
+ * the context's timing is on (sp_ctx_reset_stats), a whole grouped call and a whole sp_msm_shared_weights call are bracketed by two events on their stream:
+ * sp_ctx_kernel_stats classes "msm_grouped_call" / "msm_shared_weights_call" (first upload to last copy back, host-side tails included). */
+#define SP_MSM_GROUPED_HORNER_HOST 1u
+#define SP_MSM_GROUPED_HORNER_DEVICE 2u
+int sp_msm_shared_weights_grouped_opts(sp_ctx* ctx, const uint64_t* weights, size_t n, const uint64_t* bases_rows_aff, size_t rows, size_t groups, uint64_t* out_rows_aff,
+                                       unsigned flags);
 /* vartime_scalar_mul (src/provider/msm.rs:779-867, width-5 wNAF) of n points by ONE scalar: out[i] = scalar * points[i]. The call site is the
  * two-term fold with a unit weight (hyrax_pc.rs:757-776): see sp_fold_commitments2. Few points run on the host side of the library (a dependent
  * chain of ~300 group operations: one CPU core finishes it 40x sooner than one GPU lane), many on the device, one lane per point. */

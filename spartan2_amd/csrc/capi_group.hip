@@ -260,6 +260,71 @@ int sp_fold_tables(sp_ctx* c, const sp_table* const* Ws, size_t n, const uint64_
   return SP_OK;
 }
 
+// The window Horner of `rows` rows on the host: acc = 2^8 acc + W_w, high to low (msm.rs:150-175), ~60 us a row, spread over the process's polling threads
+// from four rows on. ws = [rows][windows] window sums, res = one point per row.
+static void horner_rows_host(const std::vector<jac_t>& ws, int windows, size_t rows, std::vector<jac_t>& res) {
+  auto horner = [&](size_t r) {
+    jac_t acc = jac_identity();
+    for (int w = windows - 1; w >= 0; --w) {
+      for (int k = 0; k < spk::MSM_C; ++k) acc = jac_dbl(acc);
+      acc = jac_add(acc, ws[r * windows + w]);
+    }
+    res[r] = acc;
+  };
+  unsigned nt = std::thread::hardware_concurrency();
+  if (nt > 8) nt = 8;
+  if (nt > rows) nt = (unsigned)rows;
+  sp::WalkPool& pool = sp::WalkPool::get();
+  if (rows >= 4 && pool.walkers() > 0) {
+    // on the process's polling threads (no thread is created inside a prove: eight clones and eight 8 MiB stack mappings a call take the address
+    // space's lock against every page fault of the process)
+    struct H {
+      decltype(horner)* f;
+      size_t rows;
+    } h{&horner, rows};
+    pool.keep_hot(2000);
+    pool.run((unsigned)std::min<size_t>(rows, (size_t)pool.walkers() + 1), [](void* a, unsigned p, unsigned np) {
+      H& x = *static_cast<H*>(a);
+      for (size_t r = x.rows * p / np; r < x.rows * (p + 1) / np; ++r) (*x.f)(r);
+    }, &h);
+  } else if (rows < 4 || nt < 2) {
+    for (size_t r = 0; r < rows; ++r) horner(r);
+  } else {  // ~60 us per row: the 16-row commitment fold of a NeutronNova batch would spend a millisecond here on one core
+    std::vector<std::thread> th;
+    for (unsigned k = 0; k < nt; ++k)
+      th.emplace_back([&, k] {
+        for (size_t r = k; r < rows; r += nt) horner(r);
+      });
+    for (auto& t : th) t.join();
+  }
+}
+
+// A whole call between two events on its stream (sp_ctx_kernel_stats class `what`), recorded only while the context's timing is on: from the first
+// upload to the last copy back, host-side tails (window Horner, waits) included - what a caller of the entry point waits for, as the device's clock saw it.
+struct CallEvents {
+  sp_ctx* c;
+  hipStream_t st;
+  const char* what;
+  hipEvent_t a = nullptr, b = nullptr;
+  CallEvents(sp_ctx* c_, hipStream_t st_, const char* what_) : c(c_), st(st_), what(what_) {
+    if (!c->timing || (!c->timing_only.empty() && c->timing_only != what)) return;
+    {
+      std::lock_guard<std::mutex> l(c->stats_mu);
+      a = c->get_event();
+      b = c->get_event();
+    }
+    hipEventRecord(a, st);
+  }
+  ~CallEvents() {
+    if (!a) return;
+    hipEventRecord(b, st);
+    std::lock_guard<std::mutex> l(c->stats_mu);
+    sp::KStat& s = c->stats[what];
+    s.pending.emplace_back(a, b);
+    s.launches += 1;
+  }
+};
+
 // lane 0: the context's main stream and workspaces (the owner's thread); lane 1: the auxiliary stream and its workspaces - callable from a helper thread
 // beside the owner's calls on the main stream (sp_msm_shared_weights_aux: the commitment fold of a NIFS beside its witness and layer folds)
 static int msm_shared_weights_on(sp_ctx* c, int lane, const uint64_t* weights, size_t n, const uint64_t* bases_rows, size_t rows, uint64_t* out_rows_aff) {
@@ -283,6 +348,7 @@ static int msm_shared_weights_on(sp_ctx* c, int lane, const uint64_t* weights, s
     fprintf(stderr, "msm_shared_weights lap %-20s %8.3f ms\n", what, t - t_lap);
     t_lap = t;
   };
+  CallEvents whole(c, st, "msm_shared_weights_call");
   fe_t* canon;
   int rc;
   if ((rc = upload_canonical(c, weights, n, &canon, lane))) return rc;
@@ -325,40 +391,7 @@ static int msm_shared_weights_on(sp_ctx* c, int lane, const uint64_t* weights, s
     std::vector<jac_t> ws(rows * windows);
     SP_HIP(hipMemcpyAsync(ws.data(), wsum, ws.size() * sizeof(jac_t), hipMemcpyDeviceToHost, st));
     SP_HIP(sp::stream_sync(st));
-    auto horner = [&](size_t r) {
-      jac_t acc = jac_identity();
-      for (int w = windows - 1; w >= 0; --w) {
-        for (int k = 0; k < spk::MSM_C; ++k) acc = jac_dbl(acc);
-        acc = jac_add(acc, ws[r * windows + w]);
-      }
-      res[r] = acc;
-    };
-    unsigned nt = std::thread::hardware_concurrency();
-    if (nt > 8) nt = 8;
-    if (nt > rows) nt = (unsigned)rows;
-    sp::WalkPool& pool = sp::WalkPool::get();
-    if (rows >= 4 && pool.walkers() > 0) {
-      // on the process's polling threads (no thread is created inside a prove: eight clones and eight 8 MiB stack mappings a call take the address
-      // space's lock against every page fault of the process)
-      struct H {
-        decltype(horner)* f;
-        size_t rows;
-      } h{&horner, rows};
-      pool.keep_hot(2000);
-      pool.run((unsigned)std::min<size_t>(rows, (size_t)pool.walkers() + 1), [](void* a, unsigned p, unsigned np) {
-        H& x = *static_cast<H*>(a);
-        for (size_t r = x.rows * p / np; r < x.rows * (p + 1) / np; ++r) (*x.f)(r);
-      }, &h);
-    } else if (rows < 4 || nt < 2) {
-      for (size_t r = 0; r < rows; ++r) horner(r);
-    } else {  // ~60 us per row: the 16-row commitment fold of a NeutronNova batch would spend a millisecond here on one core
-      std::vector<std::thread> th;
-      for (unsigned k = 0; k < nt; ++k)
-        th.emplace_back([&, k] {
-          for (size_t r = k; r < rows; r += nt) horner(r);
-        });
-      for (auto& t : th) t.join();
-    }
+    horner_rows_host(ws, windows, rows, res);
   } else {
     hipLaunchKernelGGL(spk::k_msm_horner_rows, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, st, wsum, windows, rows, drows);
     SP_HIP(hipMemcpyAsync(res.data(), drows, rows * sizeof(jac_t), hipMemcpyDeviceToHost, st));
@@ -378,6 +411,99 @@ int sp_msm_shared_weights(sp_ctx* c, const uint64_t* weights, size_t n, const ui
 int sp_msm_shared_weights_aux(sp_ctx* c, const uint64_t* weights, size_t n, const uint64_t* bases_rows, size_t rows, uint64_t* out_rows_aff) {
   return msm_shared_weights_on(c, 1, weights, n, bases_rows, rows, out_rows_aff);
 }
+
+// sp_msm_shared_weights for `groups` weight vectors, each over its own `rows` base rows (the commitment folds of several proofs of one key): one upload, the
+// sign fold and the digit sort of all groups in one launch each, bucket sums / window sums per chunk of whole groups (at most MSM_GROUP_ROWS rows a launch:
+// the bucket workspace of config 5's single call), ONE Horner pass (a launch, or host threads up to MSM_GROUP_HOST_HORNER_ROWS rows), one copy back and one
+// synchronisation for the whole call. Below 64 rows in all the latency form of the single call is the right one: it runs once per group. Results are
+// canonical affine points, so both forms write the same words. horner: 0 = by row count, SP_MSM_GROUPED_HORNER_HOST / _DEVICE = that side at every size.
+static const size_t MSM_GROUP_ROWS = 512;
+// The window Horner is a chain of 256 doublings: one lane per row on the device takes ~2.4 ms whatever the row count, the host's threads ~7 us a row in all.
+// Measured at 16 rows x 32 weights a group (tools/nn_verify_batch_timing.py through sp_msm_shared_weights_grouped_opts; profiles/nn_verify_batch.md): 64 rows
+// 1.43 ms against 2.66, 128 rows 1.85 against 2.75, 256 rows 2.85 against 3.06, 512 rows 7.74 against 3.75. Up to 128 rows the host runs it (as the single call does up to 64); the 7 % at 256 rows are not worth eight busy threads.
+static const size_t MSM_GROUP_HOST_HORNER_ROWS = 128;
+static int msm_shared_weights_grouped_on(sp_ctx* c, int lane, const uint64_t* weights, size_t n, const uint64_t* bases_rows, size_t rows, size_t groups,
+                                         uint64_t* out_rows_aff, unsigned horner = 0) {
+  if (!c || !weights || !bases_rows || !out_rows_aff) return fail(SP_ERR_INVALID_INPUT_LENGTH, "msm_shared_weights_grouped: null argument");
+  if (horner > SP_MSM_GROUPED_HORNER_DEVICE) return fail(SP_ERR_INVALID_INPUT_LENGTH, "msm_shared_weights_grouped: unknown flags");
+  if (rows == 0 || groups == 0) return SP_OK;
+  if (n >= (1u << 31) || rows >= (1u << 31) || groups > ((size_t)1 << 40) / rows || (n && groups * rows > ((size_t)1 << 40) / n))
+    return fail(SP_ERR_INVALID_INPUT_LENGTH, "msm_shared_weights_grouped: n, rows, groups * rows or groups * rows * n too large");
+  const size_t all_rows = groups * rows;
+  if (n == 0) {
+    memset(out_rows_aff, 0, all_rows * sizeof(aff_t));
+    return SP_OK;
+  }
+  if (all_rows < 64) {
+    for (size_t g = 0; g < groups; ++g) {
+      int rc = msm_shared_weights_on(c, lane, weights + 4 * n * g, n, bases_rows + 8 * rows * n * g, rows, out_rows_aff + 8 * rows * g);
+      if (rc) return rc;
+    }
+    return SP_OK;
+  }
+  hipStream_t const st = lane_stream(c, lane);
+  const int windows = spk::MSM_MAX_WINDOWS;
+  const size_t per_row = (size_t)windows * spk::MSM_BUCKETS;
+  const size_t chunk_groups = rows >= MSM_GROUP_ROWS ? 1 : MSM_GROUP_ROWS / rows, chunk_rows = std::min(groups, chunk_groups) * rows;
+  CallEvents whole(c, st, "msm_grouped_call");
+  fe_t* raw = (fe_t*)c->workspace(sp_ctx::WS_SCALARS_RAW, groups * n * sizeof(fe_t), lane);
+  fe_t* canon = (fe_t*)c->workspace(sp_ctx::WS_SCALARS_CANON, groups * n * sizeof(fe_t), lane);
+  aff_t* dbases = (aff_t*)c->workspace(sp_ctx::WS_BASES_TMP, all_rows * n * sizeof(aff_t), lane);
+  fe_t* folded = (fe_t*)c->workspace(sp_ctx::WS_MSM_FOLDED, groups * n * sizeof(fe_t), lane);
+  unsigned* order = (unsigned*)c->workspace(sp_ctx::WS_MSM_ORDER, groups * windows * n * 4, lane);
+  unsigned* start = (unsigned*)c->workspace(sp_ctx::WS_MSM_START, groups * windows * (spk::MSM_BUCKETS + 1) * 4, lane);
+  jac_t* buckets = (jac_t*)c->workspace(sp_ctx::WS_MSM_BUCKETS, chunk_rows * per_row * sizeof(jac_t), lane);
+  jac_t* wsum = (jac_t*)c->workspace(sp_ctx::WS_MSM_WSUM, all_rows * windows * sizeof(jac_t), lane);
+  jac_t* drows = (jac_t*)c->workspace(sp_ctx::WS_COMMIT_ROWS, all_rows * sizeof(jac_t), lane);
+  if (!raw || !canon || !dbases || !folded || !order || !start || !buckets || !wsum || !drows)
+    return fail(SP_ERR_NO_DEVICE, "msm_shared_weights_grouped: a workspace could not grow (" + std::to_string(all_rows) + " rows of " + std::to_string(n) + " points)");
+  SP_HIP(hipMemcpyAsync(raw, weights, groups * n * sizeof(fe_t), hipMemcpyHostToDevice, st));
+  SP_HIP(hipMemcpyAsync(dbases, bases_rows, all_rows * n * sizeof(aff_t), hipMemcpyHostToDevice, st));
+  size_t sb = (groups * n + 255) / 256;
+  if (sb > 4096) sb = 4096;
+  hipLaunchKernelGGL(spk::k_to_canonical, dim3((unsigned)sb), dim3(256), 0, st, raw, groups * n, canon);
+  hipLaunchKernelGGL(spk::k_fold_sign, dim3((unsigned)sb), dim3(256), 0, st, canon, groups * n, folded);
+  for (size_t g0 = 0; g0 < groups; g0 += 65535) {  // (the grid's y extent)
+    const size_t gc = std::min<size_t>(groups - g0, 65535);
+    hipLaunchKernelGGL(spk::k_msm_sort, dim3(windows, (unsigned)gc), dim3(256), 0, st, folded + g0 * n, (unsigned)n, order + g0 * windows * n,
+                       start + g0 * windows * (spk::MSM_BUCKETS + 1));
+  }
+  for (size_t g0 = 0; g0 < groups; g0 += chunk_groups) {
+    const size_t gc = std::min(groups - g0, chunk_groups), total = gc * rows * per_row, nwin = gc * rows * (size_t)windows;
+    c->timed_on(st, "msm_grouped_bucket_sum", 64ull * n * gc * rows, [&] {
+      hipLaunchKernelGGL(spk::k_msm_bucket_sum_grouped, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, dbases + g0 * rows * n, (unsigned)n, (unsigned)rows,
+                         order + g0 * windows * n, start + g0 * windows * (spk::MSM_BUCKETS + 1), windows, total, buckets);
+    });
+    // the next chunk reuses `buckets`: same stream, so it is ordered behind this reduction
+    hipLaunchKernelGGL(spk::k_msm_window_reduce_seg, dim3((unsigned)((nwin * 8 + 255) / 256)), dim3(256), 0, st, buckets, nwin, wsum + g0 * rows * windows);
+  }
+  std::vector<jac_t> res(all_rows);
+  if (horner ? horner == SP_MSM_GROUPED_HORNER_HOST : all_rows <= MSM_GROUP_HOST_HORNER_ROWS) {  // the Horner chain on host threads, as the single call does it for its few rows
+    std::vector<jac_t> ws(all_rows * windows);
+    SP_HIP(hipMemcpyAsync(ws.data(), wsum, ws.size() * sizeof(jac_t), hipMemcpyDeviceToHost, st));
+    SP_HIP(sp::stream_sync(st));
+    horner_rows_host(ws, windows, all_rows, res);
+  } else {
+    hipLaunchKernelGGL(spk::k_msm_horner_rows, dim3((unsigned)((all_rows + 63) / 64)), dim3(64), 0, st, wsum, windows, all_rows, drows);
+    SP_HIP(hipMemcpyAsync(res.data(), drows, all_rows * sizeof(jac_t), hipMemcpyDeviceToHost, st));
+    SP_HIP(sp::stream_sync(st));
+  }
+  std::vector<aff_t> a(all_rows);
+  normalize_batch(res, a.data());
+  memcpy(out_rows_aff, a.data(), all_rows * sizeof(aff_t));
+  return SP_OK;
+}
+int sp_msm_shared_weights_grouped(sp_ctx* c, const uint64_t* weights, size_t n, const uint64_t* bases_rows, size_t rows, size_t groups, uint64_t* out_rows_aff) {
+  return msm_shared_weights_grouped_on(c, 0, weights, n, bases_rows, rows, groups, out_rows_aff);
+}
+int sp_msm_shared_weights_grouped_aux(sp_ctx* c, const uint64_t* weights, size_t n, const uint64_t* bases_rows, size_t rows, size_t groups, uint64_t* out_rows_aff) {
+  return msm_shared_weights_grouped_on(c, 1, weights, n, bases_rows, rows, groups, out_rows_aff);
+}
+int sp_msm_shared_weights_grouped_opts(sp_ctx* c, const uint64_t* weights, size_t n, const uint64_t* bases_rows, size_t rows, size_t groups, uint64_t* out_rows_aff,
+                                       unsigned flags) {
+  return msm_shared_weights_grouped_on(c, 0, weights, n, bases_rows, rows, groups, out_rows_aff, flags);
+}
+size_t sp_msm_shared_weights_group_rows(void) { return MSM_GROUP_ROWS; }
 
 int sp_point_sum(const uint64_t* points_aff, size_t n, uint64_t out_aff[8]) {
   jac_t acc = jac_identity();

@@ -3,6 +3,7 @@
 //   k_msm_sort            K11 stage 1: signed 8-bit digits (msm.rs:110-145) + LDS counting sort by bucket, one block per window
 //   k_msm_bucket_sum      K11 stage 2: bucket accumulation, 8 lanes per bucket, mixed adds + shuffle tree
 //   k_msm_window_reduce   K11 stage 3: sum_k k*B_k per window by suffix scan + tree in LDS (summation by parts, msm.rs:169-174)
+//   k_msm_bucket_sum_grouped  the bucket sums of several shared-weights MSMs of one shape (sp_msm_shared_weights_grouped), one launch per chunk of groups
 //   k_msm_binary_rows     K10 msm_binary per Hyrax row (msm.rs:418-451 via hyrax_pc.rs:230-300)
 //   k_fixed_base_rows     K12 FixedBaseMul::mul per scalar (msm.rs:691-725): 32 table lookups + wave tree
 //   k_fixed_base_table    FixedBaseMul::precompute (msm.rs:653-689)
@@ -210,11 +211,15 @@ __global__ void __launch_bounds__(256) k_msm_sort_digits(const signed char* __re
 
 // One block per window. Outputs, per window w: order[w*n + pos] = base index | (negate << 31), grouped by bucket;
 // start[w*(BUCKETS+1) + k] = first position of bucket k+1's list (k = |digit| - 1).
+// blockIdx.y = group of a grouped shared-weights batch (its own n scalars, its own order / start lists, gridDim.x windows each); 0 for one weight vector.
 __global__ void __launch_bounds__(256) k_msm_sort(const fe_t* __restrict__ canon, unsigned n, unsigned* __restrict__ order,
                                                   unsigned* __restrict__ start) {
   __shared__ unsigned hist[MSM_BUCKETS + 1];
   __shared__ unsigned cursor[MSM_BUCKETS];
   const int w = blockIdx.x;
+  canon += (size_t)blockIdx.y * n;
+  order += (size_t)blockIdx.y * gridDim.x * n;
+  start += (size_t)blockIdx.y * gridDim.x * (MSM_BUCKETS + 1);
   for (int k = threadIdx.x; k <= MSM_BUCKETS; k += blockDim.x) hist[k] = 0;
   __syncthreads();
   for (unsigned j = threadIdx.x; j < n; j += blockDim.x) {
@@ -427,6 +432,37 @@ __global__ void __launch_bounds__(256) k_msm_bucket_sum_shared(const aff_t* __re
     acc = xyzz_add_mixed(acc, q);
   }
   buckets[b] = xyzz_to_jac(acc);
+}
+
+// Grouped shared-weights batch (sp_msm_shared_weights_grouped): `groups` weight vectors of n scalars, each with its own `rows` base rows - the commitment
+// folds of several proofs of one key in one launch. One lane per (group, window, bucket, row), the ROW running fastest, then the (window, bucket), then the
+// group: as in k_msm_bucket_sum_shared the lanes of a wave take one (window, bucket) of neighbouring rows, so they read one entry list and run one trip
+// count, and a wave never spans two groups unless rows * 33 * 128 is no multiple of 64 (then only the one wave on the seam does). With rows < 64 a wave
+// covers 64 / rows consecutive buckets of ONE window of ONE group and runs the longest of their lists; entry lists of different groups differ, so nothing
+// is gained by putting groups side by side in a wave. Lane-private reads: order / start of its group; bases of its (group, row). The result keeps the flat
+// (group * rows + row, window, bucket) place, which is what k_msm_window_reduce_seg and k_msm_horner_rows index.
+__global__ void __launch_bounds__(256) k_msm_bucket_sum_grouped(const aff_t* __restrict__ bases /* [groups][rows][n] */, unsigned n, unsigned rows,
+                                                                const unsigned* __restrict__ order /* [groups][windows][n] */,
+                                                                const unsigned* __restrict__ start /* [groups][windows][129] */, int windows, size_t total_buckets,
+                                                                jac_t* __restrict__ buckets) {
+  const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid >= total_buckets) return;
+  const size_t per_row = (size_t)windows * MSM_BUCKETS;
+  const size_t row = gid % rows, t = gid / rows;
+  const size_t wk = t % per_row, g = t / per_row;
+  const size_t w = wk / MSM_BUCKETS, k = wk % MSM_BUCKETS;
+  const unsigned* st = start + (g * windows + w) * (MSM_BUCKETS + 1) + k;
+  const unsigned lo = st[0], hi = st[1];
+  const unsigned* ord = order + (g * windows + w) * n;
+  const aff_t* rb = bases + (g * rows + row) * n;
+  xyzz_t acc = xyzz_identity();
+  for (unsigned p = lo; p < hi; ++p) {
+    const unsigned e = ord[p];
+    aff_t q = rb[e & 0x7fffffffu];
+    if (e & 0x80000000u) q = aff_neg(q);
+    acc = xyzz_add_mixed(acc, q);
+  }
+  buckets[(g * rows + row) * per_row + wk] = xyzz_to_jac(acc);
 }
 
 // Window sums for the batched path, work-efficient form: 8 adjacent lanes per (row, window); lane s runs the classical running sum over its 16

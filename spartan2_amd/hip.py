@@ -1066,6 +1066,33 @@ def msm_shared_weights(ctx, weights, bases_rows):
     return out
 
 
+def msm_shared_weights_group_rows() -> int:
+    """rows per launch of sp_msm_shared_weights_grouped (sp_msm_shared_weights_group_rows): where its groups are cut into chunks"""
+    lib().sp_msm_shared_weights_group_rows.restype = ctypes.c_size_t
+    return int(lib().sp_msm_shared_weights_group_rows())
+
+
+MSM_GROUPED_HORNER_HOST = 1  # sp_msm_shared_weights_grouped_opts flags (include/spartan_hip.h)
+MSM_GROUPED_HORNER_DEVICE = 2
+
+
+def msm_shared_weights_grouped(ctx, weights, bases_rows, aux: bool = False, horner: int = 0):
+    """sp_msm_shared_weights_grouped: weights (groups, n, 4), bases_rows (groups, rows, n, 8) -> (groups, rows, 8); row [g] is what
+    msm_shared_weights(ctx, weights[g], bases_rows[g]) returns. aux: the context's auxiliary stream and workspaces. horner: MSM_GROUPED_HORNER_HOST /
+    _DEVICE force the side that runs the window Horner (sp_msm_shared_weights_grouped_opts; main stream only), 0 = by row count."""
+    bases_rows = np.ascontiguousarray(bases_rows, dtype=np.uint64)
+    groups, rows, n = bases_rows.shape[0], bases_rows.shape[1], bases_rows.shape[2]
+    weights = np.ascontiguousarray(weights, dtype=np.uint64).reshape(groups, n, 4)
+    out = np.zeros((groups, rows, 8), dtype=np.uint64)
+    args = (ctx.h, p64(weights), ctypes.c_size_t(n), p64(bases_rows.reshape(-1)), ctypes.c_size_t(rows), ctypes.c_size_t(groups), p64(out))
+    if horner:
+        assert not aux
+        check(lib().sp_msm_shared_weights_grouped_opts(*args, ctypes.c_uint(horner)))
+    else:
+        check((lib().sp_msm_shared_weights_grouped_aux if aux else lib().sp_msm_shared_weights_grouped)(*args))
+    return out
+
+
 def eval_cubic_outer_pow(ctx, pow_left: Table, pow_right, A: Table, B: Table, C: Table):
     """compute_eval_points_cubic_with_additive_term_with_outer_pow (src/sumcheck.rs:366-498) -> (eval0, eval2, eval3)."""
     out = np.zeros((3, 4), dtype=np.uint64)

@@ -102,6 +102,8 @@ SS_BATCH_OPENING_BEHIND = 64  # ... the openings as one sp_hyrax_prove_batch cal
 SS_PREP_PER_STATE_COMMIT = 1  # ss_prep_prove_batch_opts / ss_prep_prove_sha256_batch_opts flags: one sp_hyrax_commit per state ...
 SS_PREP_PER_STATE_MATVEC = 2  # ... one sp_multiply_vec per state (what the driver takes unless asked otherwise: measured, profiles/prep_prove_batch.md)
 SS_PREP_CHUNKED_MATVEC = 4  # ... the cached products through sp_multiply_vec_chunked
+NNZ_VERIFY_BATCH_PER_PROOF = 1  # nnz_verify_batch_opts flag (host/neutronnova_zk.cpp): one nnz_verify per proof
+NNZ_VERIFY_BATCH_SHARED = 2  # ... the shared device stage and the combined opening from two proofs on
 PHASES = ("witness_commit", "matrix_vector_multiply", "outer_sumcheck", "prepare_poly_ABC", "inner_sumcheck", "pcs_prove", "total")
 
 
@@ -859,6 +861,39 @@ class NeutronNovaZkSNARK:
         if rc < 0:
             _check(rc)
         return rc
+
+    def _verify_batch(self, fn, items, lens, keep, seed, info, per_proof):
+        n = len(lens)  # (items is a ctypes array of at least one slot; keep holds the arrays it points into)
+        codes = (ctypes.c_int * max(n, 1))()
+        inf = VerifyBatchInfo()
+        sd = None
+        if seed is not None:
+            sd = np.frombuffer(bytes(seed), dtype=np.uint8).copy()
+            assert sd.shape[0] == 32, "seed must be 32 bytes"
+        flags = 0 if per_proof is None else (NNZ_VERIFY_BATCH_PER_PROOF if per_proof else NNZ_VERIFY_BATCH_SHARED)
+        _check(fn(self.pk, items, (ctypes.c_size_t * max(n, 1))(*lens), ctypes.c_size_t(n), hip.p8(sd) if sd is not None else None, codes, ctypes.byref(inf),
+                  ctypes.c_uint(flags)))
+        out = [int(codes[k]) for k in range(n)]
+        return (out, inf.as_dict()) if info else out
+
+    def verify_batch(self, proofs, seed=None, info=False, per_proof=None):
+        """verify() for every proof of `proofs` (flat word arrays of this key) in one pass (neutronnova_zk.cpp nn_verify_batch): the step-instance folds of
+        all proofs as one sp_msm_shared_weights_grouped, the matrix evaluations of a chunk of proofs per launch, the transcript work per proof, the openings
+        of all proofs as one random linear combination. -> the list of verify()'s codes; with info=True (codes, info), info = {matrix_chunks,
+        opening_batched_ok, fallback_proofs, opening_proofs}. seed: 32 bytes mixed into the weights of the combined check, or None. per_proof: True = one
+        verify() after the other (NNZ_VERIFY_BATCH_PER_PROOF), False = the shared form from two proofs on (NNZ_VERIFY_BATCH_SHARED), None = the form the
+        driver measured to be faster at this batch size. A batch of one is verify() itself."""
+        ws = [np.ascontiguousarray(w, dtype=np.uint64).reshape(-1) for w in proofs]
+        n = len(ws)
+        ptrs = (hip.c_u64p * max(n, 1))(*[hip.p64(w) if w.shape[0] else None for w in ws])
+        return self._verify_batch(lib().nnz_verify_batch_opts, ptrs, [w.shape[0] for w in ws], ws, seed, info, per_proof)
+
+    def verify_bytes_batch(self, blobs, seed=None, info=False, per_proof=None):
+        """verify_batch() over serialised proofs (proof_to_bytes): bytes that do not decode to a proof of this key get code 1."""
+        bs = [np.frombuffer(bytes(b), dtype=np.uint8).copy() if len(b) else np.zeros(1, dtype=np.uint8) for b in blobs]
+        n = len(bs)
+        ptrs = (hip.c_u8p * max(n, 1))(*[hip.p8(b) for b in bs])
+        return self._verify_batch(lib().nnz_verify_bytes_batch_opts, ptrs, [len(b) for b in blobs], bs, seed, info, per_proof)
 
     def close(self):
         if self.ps:

@@ -8,6 +8,8 @@
 // Scope = the bench circuits' class: step and core circuits without rest variables and without verifier challenges (`can_cache_matvec`, :1520).
 // The proof layout is the oracle's NNProof::serialize (oracle/neutronnova_zk.hpp); parity = word-for-word equality on the same inputs and tape.
 #include <deque>
+#include <future>
+#include <memory>
 
 #include "neutronnova_nifs.hpp"
 #include "proof_layout.hpp"
@@ -102,9 +104,12 @@ struct NNZkKey {
   // they run as jobs on a second context of the same GPU beside the replay, NovaNIFS::verify and the relaxed Spartan check
   mutable sp_ctx* v_ctx2 = nullptr;
   mutable Worker v_wk;
+  mutable std::vector<sp_table*> vb_Tx, vb_Ty;  // verify_batch()'s (T_x, T_y) pairs of one chunk of proofs, kept like the above
   ~NNZkKey() {
     v_wk.drain();
     sp_ctx_destroy(v_ctx2);
+    for (sp_table* t : vb_Tx) sp_table_free(t);
+    for (sp_table* t : vb_Ty) sp_table_free(t);
     sp_table_free(v_Tx);
     sp_table_free(v_Ty);
     for (sp_table* t : v_mv) sp_table_free(t);
@@ -1211,42 +1216,50 @@ static ProofBuf nn_prove(const NNZkKey& pk, NNZkPrep& ps, Tape& tape, double* ph
 // over a few hundred constraints plus small MSMs / two-term folds through the ABI. Returns 0 = accept, else the index of the failed check — the
 // oracle's codes (oracle/neutronnova_zk.hpp nn_verify): 1 shape / encoding, 2 verifier-circuit instance does not replay, 4 relaxed Spartan proof,
 // 5 public values of the verifier circuit, 6 folded opening.
-static int nn_verify(const NNZkKey& pk, const uint64_t* words, size_t nwords) {
-  sp_ctx* ctx = pk.ctx;
-  const sp_dims& d = pk.dims;
-  const vcirc::Shape& vs = pk.vc;
-  const size_t CW = DEFAULT_COMMITMENT_WIDTH, n = pk.num_steps, nv = pk.num_vars, N = d.num_cons, dpub = d.num_public, cpub = pk.dims_core.num_public;
-  const NNLayout& lay = pk.layout;
-  const size_t rows_sh = lay.rows_sh, rows = lay.rows();
-  const size_t vnv = vs.total_vars, vcons = vs.num_cons, vio = vs.num_io(), vlx = log2_ceil(vcons), vnvp = next_pow2(vnv), vly = log2_ceil(vnvp) + 1, VW = vs.width;
-  if (n == 0 || nwords != lay.words()) return 1;
-  ck(sp_ctx_bind_thread(ctx), "device");
-  static const bool laps = [] {
-    const char* e = getenv("SPARTAN_HOST_LAPS");
-    return e && e[0] == '1';
-  }();
-  auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  double t_lap = now();
-  auto lap = [&](const char* what) {
+//
+// The check is a sequence of named steps over one NNVerifyState; nn_verify runs them for one proof, nn_verify_batch for many proofs of one key:
+//   nn_verify_parse              host only: encoding checks, the views, the regular instances, Uv_X, weights_from_r, Xf, the fold's base rows   (1, 2)
+//   nn_fold_commitments_one /    the device work that needs r_b, r_x, r_y alone, for ONE proof (side jobs of nn_verify on the second context);
+//   nn_matrix_evaluations_one    the batch issues the same work for all proofs at once (nn_batch_fold, nn_batch_matrix_evaluations)
+//   nn_verify_transcript         the transcript, the verifier-circuit replay, NovaNIFS::verify, the relaxed Spartan verify                      (2, 4)
+//   nn_verify_publics            the six public values against the matrix evaluations                                                           (5)
+//   nn_verify_opening_challenge  the folded opening up to the IPA challenge: comm, comm_eval, comm_LZ, r, <z_vec, R>                            (6)
+//   nn_verify_opening_check      the two group equations of one proof                                                                           (6)
+struct NNVerifyState {
+  NNProofView pv;
+  size_t np = 0;
+  std::vector<std::vector<aff_t>> Ucomm;
+  std::vector<aff_t> core_comm, Uv_comm, fold_bases /* [rows][np] */, folded_comm;
+  std::vector<fe_t> core_X, Uv_X, wts, Xf, rhos;
+  fe_t eabc[2][3];  // A, B, C (r_x, r_y) of the step and of the core shape
+  std::unique_ptr<Tr> tr;
+  fe_t tau;
+  aff_t comm_LZ, comm_eval;
+  fe_t rr, ip;  // the IPA challenge; <z_vec, R>
+  ZJob zjob;    // <z_vec, ck> of the single form (the batch forms it once for all proofs)
+  bool laps = false;
+  double t_lap = 0;
+  static double now() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+  void lap(const char* what) {
     if (!laps) return;
     const double t = now();
     fprintf(stderr, "nn_verify lap %-28s %8.3f ms\n", what, t - t_lap);
     t_lap = t;
-  };
+  }
+};
+
+static int nn_verify_parse(const NNZkKey& pk, const uint64_t* words, size_t nwords, NNVerifyState& st) {
+  const vcirc::Shape& vs = pk.vc;
+  const size_t n = pk.num_steps, dpub = pk.dims.num_public, cpub = pk.dims_core.num_public;
+  const NNLayout& lay = pk.layout;
+  const size_t rows_sh = lay.rows_sh, rows = lay.rows();
+  const size_t vnv = vs.total_vars, VW = vs.width;
+  if (n == 0 || nwords != lay.words()) return 1;
   // ---- the proof in its canonical layout; every coordinate and scalar of an untrusted proof must be a canonical residue and every point on the curve
   if (!well_formed(lay, words)) return 1;
-  const NNProofView pv = lay.view(words);
-  const aff_t *comm_shared = pv.comm_shared, *comm_T = pv.comm_T, *rnd_comm_W = pv.rnd_comm_W, *rnd_comm_E = pv.rnd_comm_E;
-  const fe_t *z_vec = pv.z_vec, *vpub = pv.vpub, *rnd_X = pv.rnd_X, *v_outer = pv.v_outer, *v_claims = pv.v_claims, *v_inner = pv.v_inner, *v_W = pv.v_W, *v_E = pv.v_E;
-  const aff_t delta = *pv.delta, beta = *pv.beta;
-  const fe_t z_delta = *pv.z_delta, z_beta = *pv.z_beta, rnd_u = *pv.rnd_u, blind_vW = *pv.blind_vW, blind_vE = *pv.blind_vE;
-  lap("parse + encoding checks");
-  // <z_vec, ck> (ipa.rs:196-203) depends on nothing but the proof: its device part runs under everything that follows
-  ZJob zjob;
-  zjob.ctx = ctx;
-  zjob.key = pk.ck;
-  ck(sp_msm_ck_begin(ctx, pk.ck, u64p(z_vec), CW, &zjob.job), "<z, ck> (begin)");
-
+  st.pv = lay.view(words);
+  const NNProofView& pv = st.pv;
+  const aff_t* comm_shared = pv.comm_shared;
   // regular instances: comm_W = shared | precommitted | rest rows, X = the public values (src/r1cs/mod.rs:1723-1760)
   auto regular = [&](const NNProofView::Inst& u, size_t my_pre, size_t my_rest) {
     std::vector<aff_t> c(rows);
@@ -1257,71 +1270,84 @@ static int nn_verify(const NNZkKey& pk, const uint64_t* words, size_t nwords) {
   };
   size_t np = 2;
   while (np < n) np <<= 1;
+  st.np = np;
   const size_t nb = pk.nb, nx = pk.nx, ny = pk.ny;
   if (((size_t)1 << nb) != np) throw Error(SP_ERR_INTERNAL, "nn_verify: a single step instance is not driven by this layer");
   auto inst = [&](size_t i) { return i < n ? i : 0; };  // padding clones instance 0 (:549-552)
-  std::vector<std::vector<aff_t>> Ucomm(n);
-  for (size_t i = 0; i < n; ++i) Ucomm[i] = regular(pv.steps[i], lay.rows_pre, lay.rows_rest);
-  const std::vector<aff_t> core_comm = regular(pv.core, lay.rows_pre_c, lay.rows_rest_c);
-  const std::vector<fe_t> core_X(pv.core.pub, pv.core.pub + cpub);
+  st.Ucomm.resize(n);
+  for (size_t i = 0; i < n; ++i) st.Ucomm[i] = regular(pv.steps[i], lay.rows_pre, lay.rows_rest);
+  st.core_comm = regular(pv.core, lay.rows_pre_c, lay.rows_rest_c);
+  st.core_X.assign(pv.core.pub, pv.core.pub + cpub);
   // the verifier-circuit instance in its regular form: comm_W = the rounds' rows, X = challenges | public values; the challenges are checked against the
-  // transcript below, what is computed from them before that is only used after the check
-  const std::vector<aff_t> Uv_comm(pv.vcomm[0], pv.vcomm[0] + vnv / VW);  // the rounds are consecutive in the layout
-  std::vector<fe_t> Uv_X;
+  // transcript (nn_verify_transcript), what is computed from them before that is only used after the check
+  st.Uv_comm.assign(pv.vcomm[0], pv.vcomm[0] + vnv / VW);  // the rounds are consecutive in the layout
+  std::vector<fe_t>& Uv_X = st.Uv_X;
+  Uv_X.clear();
   for (size_t r = 0; r < vs.num_rounds; ++r) Uv_X.insert(Uv_X.end(), pv.vchal[r], pv.vchal[r] + vs.chals_per_round[r]);
-  Uv_X.insert(Uv_X.end(), vpub, vpub + vs.num_public);
+  Uv_X.insert(Uv_X.end(), pv.vpub, pv.vpub + vs.num_public);
   const size_t num_chal = nb + nx + 1 + ny;
   if (vs.total_challenges != num_chal || vs.num_public != 6) return 2;
-  const fe_t *r_b = Uv_X.data(), *r_x = r_b + nb, *r_y = r_x + nx + 1, *pub = Uv_X.data() + num_chal;
-  const fe_t r = Uv_X[nb + nx], r2 = fe_mul<S>(r, r), one = fe_one<S>();
+  const fe_t* r_b = Uv_X.data();
   // fold_multiple of the step instances (src/r1cs/mod.rs:695-722): X on the host, the commitment rows as shared-weights MSMs
-  std::vector<fe_t> wts(np);
-  ck(sp_weights_from_r(u64p(r_b), nb, np, u64p(wts.data())), "weights_from_r");
-  std::vector<fe_t> Xf(dpub, fe_zero());
+  st.wts.resize(np);
+  ck(sp_weights_from_r(u64p(r_b), nb, np, u64p(st.wts.data())), "weights_from_r");
+  st.Xf.assign(dpub, fe_zero());
   for (size_t i = 0; i < np; ++i)
-    for (size_t j = 0; j < dpub; ++j) Xf[j] = fe_add<S>(Xf[j], fe_mul<S>(wts[i], pv.steps[inst(i)].pub[j]));
-  std::vector<aff_t> folded_comm(rows), fold_bases(rows * np);
+    for (size_t j = 0; j < dpub; ++j) st.Xf[j] = fe_add<S>(st.Xf[j], fe_mul<S>(st.wts[i], pv.steps[inst(i)].pub[j]));
+  st.folded_comm.resize(rows);
+  st.fold_bases.resize(rows * np);
   for (size_t rr = 0; rr < rows; ++rr)
-    for (size_t i = 0; i < np; ++i) fold_bases[rr * np + i] = Ucomm[inst(i)][rr];
-  fe_t eabc[2][3];
-  const bool side = true;  // (false = everything inline on the caller's context: the order the phase comments describe)
-  auto fold_commitments = [&](sp_ctx* on) {
-    ck(sp_msm_shared_weights(on, u64p(wts.data()), np, reinterpret_cast<const uint64_t*>(fold_bases.data()), rows, reinterpret_cast<uint64_t*>(folded_comm.data())), "fold_commitments");
-  };
-  // the matrix evaluations A, B, C (r_x, r_y) of the step and core shapes: T_x^T (M T_y)
-  auto matrix_evaluations = [&](sp_ctx* on) {
-    if (!pk.v_Tx) {
-      ck(sp_table_zeros(on, (size_t)1 << nx, (size_t)-1, (size_t)-1, &pk.v_Tx), "T_x alloc");
-      ck(sp_table_zeros(on, (size_t)1 << ny, (size_t)-1, (size_t)-1, &pk.v_Ty), "T_y alloc");
-      for (int i = 0; i < 3; ++i) ck(sp_table_zeros(on, N, (size_t)-1, (size_t)-1, &pk.v_mv[i]), "M T_y alloc");
-    }
-    sp_table *Tx = pk.v_Tx, *Ty = pk.v_Ty, **mv = pk.v_mv;
-    ck(sp_table_set_len(Tx, (size_t)1 << nx, (size_t)-1, (size_t)-1), "T_x len");
-    ck(sp_table_set_len(Ty, (size_t)1 << ny, (size_t)-1, (size_t)-1), "T_y len");
-    ck(sp_eq_table_into(on, u64p(r_x), nx, Tx), "T_x");
-    ck(sp_eq_table_into(on, u64p(r_y), ny, Ty), "T_y");
-    const sp_shape* shapes[2] = {pk.S_step, pk.S_core};
-    const size_t cols[2] = {nv + 1 + dpub, nv + 1 + cpub};
-    for (int s2 = 0; s2 < 2; ++s2) {
-      ck(sp_table_set_len(Ty, cols[s2], (size_t)-1, (size_t)-1), "T_y as z");
-      ck(sp_multiply_vec(on, shapes[s2], Ty, mv[0], mv[1], mv[2]), "M T_y");
-      for (int i = 0; i < 3; ++i) ck(sp_table_dot(on, Tx, mv[i], N, u64p(&eabc[s2][i])), "T_x . (M T_y)");
-    }
-  };
-  struct Drain {  // the jobs read and write locals of this call
-    Worker& w;
-    ~Drain() { w.drain(); }
-  } drain{pk.v_wk};
-  size_t t_fold = 0, t_mat = 0;
-  if (side) {
-    if (!pk.v_ctx2) ck(sp_ctx_create(sp_ctx_device(ctx), &pk.v_ctx2), "second context");
-    t_fold = pk.v_wk.submit([&] {
-      ck(sp_ctx_bind_thread(pk.v_ctx2), "device");
-      fold_commitments(pk.v_ctx2);
-    });
-    t_mat = pk.v_wk.submit([&] { matrix_evaluations(pk.v_ctx2); });
+    for (size_t i = 0; i < np; ++i) st.fold_bases[rr * np + i] = st.Ucomm[inst(i)][rr];
+  return 0;
+}
+
+// fold_commitments of one proof's step instances (hyrax_pc.rs:737-793): one shared-weights MSM over its rows
+static void nn_fold_commitments_one(const NNZkKey& pk, sp_ctx* on, NNVerifyState& st) {
+  ck(sp_msm_shared_weights(on, u64p(st.wts.data()), st.np, reinterpret_cast<const uint64_t*>(st.fold_bases.data()), pk.layout.rows(),
+                           reinterpret_cast<uint64_t*>(st.folded_comm.data())),
+     "fold_commitments");
+}
+// the matrix evaluations A, B, C (r_x, r_y) of the step and core shapes of one proof: T_x^T (M T_y)
+static void nn_matrix_evaluations_one(const NNZkKey& pk, sp_ctx* on, NNVerifyState& st) {
+  const size_t nb = pk.nb, nx = pk.nx, ny = pk.ny, nv = pk.num_vars, N = pk.dims.num_cons, dpub = pk.dims.num_public, cpub = pk.dims_core.num_public;
+  const fe_t *r_x = st.Uv_X.data() + nb, *r_y = r_x + nx + 1;
+  if (!pk.v_Tx) {
+    ck(sp_table_zeros(on, (size_t)1 << nx, (size_t)-1, (size_t)-1, &pk.v_Tx), "T_x alloc");
+    ck(sp_table_zeros(on, (size_t)1 << ny, (size_t)-1, (size_t)-1, &pk.v_Ty), "T_y alloc");
+    for (int i = 0; i < 3; ++i) ck(sp_table_zeros(on, N, (size_t)-1, (size_t)-1, &pk.v_mv[i]), "M T_y alloc");
   }
-  Tr tr(ctx, "neutronnova_prove");
+  sp_table *Tx = pk.v_Tx, *Ty = pk.v_Ty, **mv = pk.v_mv;
+  ck(sp_table_set_len(Tx, (size_t)1 << nx, (size_t)-1, (size_t)-1), "T_x len");
+  ck(sp_table_set_len(Ty, (size_t)1 << ny, (size_t)-1, (size_t)-1), "T_y len");
+  ck(sp_eq_table_into(on, u64p(r_x), nx, Tx), "T_x");
+  ck(sp_eq_table_into(on, u64p(r_y), ny, Ty), "T_y");
+  const sp_shape* shapes[2] = {pk.S_step, pk.S_core};
+  const size_t cols[2] = {nv + 1 + dpub, nv + 1 + cpub};
+  for (int s2 = 0; s2 < 2; ++s2) {
+    ck(sp_table_set_len(Ty, cols[s2], (size_t)-1, (size_t)-1), "T_y as z");
+    ck(sp_multiply_vec(on, shapes[s2], Ty, mv[0], mv[1], mv[2]), "M T_y");
+    for (int i = 0; i < 3; ++i) ck(sp_table_dot(on, Tx, mv[i], N, u64p(&st.eabc[s2][i])), "T_x . (M T_y)");
+  }
+}
+
+// the transcript up to the relaxed Spartan proof: 0, or 2 (the verifier-circuit instance does not replay), or 4 (relaxed Spartan)
+static int nn_verify_transcript(const NNZkKey& pk, NNVerifyState& st) {
+  sp_ctx* ctx = pk.ctx;
+  const vcirc::Shape& vs = pk.vc;
+  const size_t n = pk.num_steps, np = st.np, nb = pk.nb, dpub = pk.dims.num_public;
+  const size_t vnv = vs.total_vars, vcons = vs.num_cons, vio = vs.num_io(), vlx = log2_ceil(vcons), vnvp = next_pow2(vnv), vly = log2_ceil(vnvp) + 1, VW = vs.width;
+  const NNProofView& pv = st.pv;
+  const aff_t *comm_T = pv.comm_T, *rnd_comm_W = pv.rnd_comm_W, *rnd_comm_E = pv.rnd_comm_E;
+  const fe_t *rnd_X = pv.rnd_X, *v_outer = pv.v_outer, *v_claims = pv.v_claims, *v_inner = pv.v_inner, *v_W = pv.v_W, *v_E = pv.v_E;
+  const fe_t rnd_u = *pv.rnd_u, blind_vW = *pv.blind_vW, blind_vE = *pv.blind_vE, one = fe_one<S>();
+  const std::vector<std::vector<aff_t>>& Ucomm = st.Ucomm;
+  const std::vector<aff_t>&core_comm = st.core_comm, &Uv_comm = st.Uv_comm;
+  const std::vector<fe_t>&core_X = st.core_X, &Uv_X = st.Uv_X;
+  std::vector<fe_t>& rhos = st.rhos;
+  auto inst = [&](size_t i) { return i < n ? i : 0; };
+  auto lap = [&](const char* what) { st.lap(what); };
+  st.tr.reset(new Tr(ctx, "neutronnova_prove"));
+  Tr& tr = *st.tr;
   tr.absorb("vk", pk.vk_digest, 32);
   absorb_instance(tr, "core_instance", core_comm, core_X);
   for (size_t i = 0; i < np; ++i) absorb_instance(tr, "U", Ucomm[inst(i)], std::vector<fe_t>(pv.steps[inst(i)].pub, pv.steps[inst(i)].pub + dpub));
@@ -1329,8 +1355,8 @@ static int nn_verify(const NNZkKey& pk, const uint64_t* words, size_t nwords) {
     uint8_t zero_be[32] = {0};  // T = 0 (:556-557)
     tr.absorb("T", zero_be, 32);
   }
-  const fe_t tau = tr.squeeze("tau");
-  std::vector<fe_t> rhos(nb);
+  st.tau = tr.squeeze("tau");
+  rhos.assign(nb, fe_zero());
   for (auto& x : rhos) x = tr.squeeze("rho");
   lap("instances absorbed");
   // U_verifier.validate (src/r1cs/mod.rs:1808-1834): the per-round commitments reproduce the challenges the instance carries
@@ -1423,11 +1449,18 @@ static int nn_verify(const NNZkKey& pk, const uint64_t* words, size_t nwords) {
     tr.absorb_scalars("v_E", v_E, VW);
   }
   lap("relaxed Spartan verify");
-  // the six public values of the verifier circuit (:2280-2330): tau(r_x), the X evaluations, eq(r_b, rho) and the matrix evaluations at (r_x, r_y)
-  if (t_mat)
-    pk.v_wk.wait(t_mat);
-  else
-    matrix_evaluations(ctx);
+  return 0;
+}
+
+// the six public values of the verifier circuit (:2280-2330): tau(r_x), the X evaluations, eq(r_b, rho) and the matrix evaluations at (r_x, r_y),
+// which st.eabc holds by now. 0 or 5.
+static int nn_verify_publics(const NNZkKey& pk, NNVerifyState& st) {
+  const size_t nb = pk.nb, nx = pk.nx, ny = pk.ny, dpub = pk.dims.num_public, cpub = pk.dims_core.num_public;
+  const NNProofView& pv = st.pv;
+  const std::vector<fe_t>&Uv_X = st.Uv_X, &Xf = st.Xf, &rhos = st.rhos;
+  const fe_t *r_b = Uv_X.data(), *r_x = r_b + nb, *r_y = r_x + nx + 1, *pub = Uv_X.data() + (nb + nx + 1 + ny);
+  const fe_t r = Uv_X[nb + nx], r2 = fe_mul<S>(r, r), one = fe_one<S>(), tau = st.tau;
+  const fe_t(*eabc)[3] = st.eabc;
   {
     auto eval_X = [&](const fe_t* Xv, size_t cnt) {
       std::vector<fe_t> v{one};
@@ -1447,18 +1480,27 @@ static int nn_verify(const NNZkKey& pk, const uint64_t* words, size_t nwords) {
         !fe_eq(pub[5], q_core))
       return 5;
   }
-  lap("matrix evaluations + publics");
-  // the folded opening (:2332-2343): HyraxPCS::verify (hyrax_pc.rs:480-531) + InnerProductArgumentLinear::verify (ipa.rs:173-221)
+  st.lap("matrix evaluations + publics");
+  return 0;
+}
+
+// the folded opening (:2332-2343) up to the IPA challenge: HyraxPCS::verify (hyrax_pc.rs:480-531) + InnerProductArgumentLinear::verify (ipa.rs:173-194).
+// Needs st.folded_comm. Leaves comm_LZ, comm_eval, the challenge rr and ip = <z_vec, R>. 0 or 6.
+static int nn_verify_opening_challenge(const NNZkKey& pk, NNVerifyState& st) {
+  sp_ctx* ctx = pk.ctx;
+  const vcirc::Shape& vs = pk.vc;
+  const size_t CW = DEFAULT_COMMITMENT_WIDTH, nb = pk.nb, nx = pk.nx, ny = pk.ny, rows = pk.layout.rows();
+  const NNProofView& pv = st.pv;
+  const std::vector<aff_t>&folded_comm = st.folded_comm, &core_comm = st.core_comm;
+  const fe_t *r_y = st.Uv_X.data() + nb + nx + 1, *z_vec = pv.z_vec;
+  const aff_t delta = *pv.delta, beta = *pv.beta;
+  Tr& tr = *st.tr;
+  aff_t &comm_LZ = st.comm_LZ, &comm_eval = st.comm_eval;
   const fe_t c_eval = tr.squeeze("c_eval");
   const size_t commit_round = nb + 1 + nx + 1 + ny + 1;
   if (commit_round + 1 >= vs.num_rounds) throw Error(SP_ERR_INTERNAL, "nn_verify: verifier-circuit round layout");
   std::vector<aff_t> comm(rows);
-  if (t_fold)
-    pk.v_wk.wait(t_fold);
-  else
-    fold_commitments(ctx);
   ck(sp_fold_commitments2(ctx, u64p(&folded_comm[0].x), u64p(&core_comm[0].x), rows, u64p(&c_eval), u64p(&comm[0].x)), "fold_commitments");
-  aff_t comm_eval;
   ck(sp_fold_commitments2(ctx, u64p(&pv.vcomm[commit_round][0].x), u64p(&pv.vcomm[commit_round + 1][0].x), 1, u64p(&c_eval), u64p(&comm_eval.x)), "fold eval commitments");
   {
     const std::vector<uint8_t> b = commitment_bytes(comm.data(), rows);
@@ -1466,7 +1508,6 @@ static int nn_verify(const NNZkKey& pk, const uint64_t* words, size_t nwords) {
   }
   const fe_t* point = r_y + 1;
   const size_t npoint = ny - 1, num_rows = (((size_t)1 << npoint) + CW - 1) / CW, nvr = log2_ceil(num_rows);
-  aff_t comm_LZ;
   std::vector<fe_t> R;
   if (nvr == 0) {
     comm_LZ = comm[0];
@@ -1489,23 +1530,263 @@ static int nn_verify(const NNZkKey& pk, const uint64_t* words, size_t nwords) {
     point_bytes(beta, b);
     tr.absorb("beta", b, 64);
   }
-  const fe_t rr = tr.squeeze("r");
-  aff_t pr2[2] = {comm_LZ, comm_eval}, rp[2], hzd, rhs2;
-  ck(sp_vartime_scalar_mul(ctx, u64p(&pr2[0].x), 2, u64p(&rr), u64p(&rp[0].x)), "r * (comm_LZ, comm_eval)");
-  ck(sp_fixed_base_mul_h(ctx, pk.ck, u64p(&z_delta), 1, u64p(&hzd.x)), "h * z_delta");
+  st.rr = tr.squeeze("r");
   fe_t ip = fe_zero();
   for (size_t i = 0; i < CW; ++i) ip = fe_add<S>(ip, fe_mul<S>(z_vec[i], R[i]));
-  ck(sp_hyrax_commit_small(ctx, pk.vc_ck, u64p(&ip), 1, u64p(&z_beta), u64p(&rhs2.x)), "<z, R> * ck_c + z_beta * h_c");
+  st.ip = ip;
+  return 0;
+}
+
+// the group equations of one proof (ipa.rs:196-221): r comm_LZ + delta == <z_vec, ck> + z_delta h and r comm_eval + beta == <z_vec, R> ck_c + z_beta h_c. 0 or 6.
+static int nn_verify_opening_check(const NNZkKey& pk, NNVerifyState& st) {
+  sp_ctx* ctx = pk.ctx;
+  const NNProofView& pv = st.pv;
+  const aff_t delta = *pv.delta, beta = *pv.beta;
+  const fe_t z_delta = *pv.z_delta, z_beta = *pv.z_beta;
+  aff_t pr2[2] = {st.comm_LZ, st.comm_eval}, rp[2], hzd, rhs2;
+  ck(sp_vartime_scalar_mul(ctx, u64p(&pr2[0].x), 2, u64p(&st.rr), u64p(&rp[0].x)), "r * (comm_LZ, comm_eval)");
+  ck(sp_fixed_base_mul_h(ctx, pk.ck, u64p(&z_delta), 1, u64p(&hzd.x)), "h * z_delta");
+  ck(sp_hyrax_commit_small(ctx, pk.vc_ck, u64p(&st.ip), 1, u64p(&z_beta), u64p(&rhs2.x)), "<z, R> * ck_c + z_beta * h_c");
   aff_t zc;
   {
-    sp_msm_job* j = zjob.job;
-    zjob.job = nullptr;
+    st.zjob.ctx = ctx;
+    st.zjob.key = pk.ck;
+    if (!st.zjob.job) ck(sp_msm_ck_begin(ctx, pk.ck, u64p(pv.z_vec), DEFAULT_COMMITMENT_WIDTH, &st.zjob.job), "<z, ck> (begin)");  // (a batch's fallback: nn_verify began it)
+    sp_msm_job* j = st.zjob.job;
+    st.zjob.job = nullptr;
     ck(sp_msm_ck_finish(ctx, pk.ck, j, nullptr, u64p(&zc.x)), "<z, ck> (finish)");
   }
   if (!same_point(jac_add_mixed(jac_from_affine(rp[0]), delta), jac_add_mixed(jac_from_affine(zc), hzd))) return 6;
   if (!same_point(jac_add_mixed(jac_from_affine(rp[1]), beta), jac_from_affine(rhs2))) return 6;
-  lap("folded opening");
+  st.lap("folded opening");
   return 0;
+}
+
+static int nn_verify(const NNZkKey& pk, const uint64_t* words, size_t nwords) {
+  sp_ctx* ctx = pk.ctx;
+  if (pk.num_steps == 0 || nwords != pk.layout.words()) return 1;
+  ck(sp_ctx_bind_thread(ctx), "device");
+  static const bool laps = [] {
+    const char* e = getenv("SPARTAN_HOST_LAPS");
+    return e && e[0] == '1';
+  }();
+  NNVerifyState st;
+  st.laps = laps;
+  st.t_lap = NNVerifyState::now();
+  int code;
+  if ((code = nn_verify_parse(pk, words, nwords, st)) == 1) return 1;
+  st.lap("parse + encoding checks");
+  // <z_vec, ck> (ipa.rs:196-203) depends on nothing but the proof: its device part runs under everything that follows
+  st.zjob.ctx = ctx;
+  st.zjob.key = pk.ck;
+  ck(sp_msm_ck_begin(ctx, pk.ck, u64p(st.pv.z_vec), DEFAULT_COMMITMENT_WIDTH, &st.zjob.job), "<z, ck> (begin)");
+  if (code) return code;
+  // r_b, r_x and r_y are words of the proof: the commitment fold and the matrix evaluations run as jobs on the second context beside the transcript work
+  struct Drain {  // the jobs read and write `st`
+    Worker& w;
+    ~Drain() { w.drain(); }
+  } drain{pk.v_wk};
+  if (!pk.v_ctx2) ck(sp_ctx_create(sp_ctx_device(ctx), &pk.v_ctx2), "second context");
+  const size_t t_fold = pk.v_wk.submit([&] {
+    ck(sp_ctx_bind_thread(pk.v_ctx2), "device");
+    nn_fold_commitments_one(pk, pk.v_ctx2, st);
+  });
+  const size_t t_mat = pk.v_wk.submit([&] { nn_matrix_evaluations_one(pk, pk.v_ctx2, st); });
+  if ((code = nn_verify_transcript(pk, st))) return code;
+  pk.v_wk.wait(t_mat);
+  if ((code = nn_verify_publics(pk, st))) return code;
+  pk.v_wk.wait(t_fold);
+  if ((code = nn_verify_opening_challenge(pk, st))) return code;
+  return nn_verify_opening_check(pk, st);
+}
+
+// ---- verify_batch: `count` proofs under one key in one pass -----------------------------------------------------------------------------------------------
+// codes[k] == nn_verify(proof k) for every k; a batch of one IS nn_verify. What the proofs of a batch share is paid once:
+//   parse       nn_verify_parse per proof on host threads (it touches no context);
+//   shared      on the second context's worker, as nn_verify's side jobs: ONE sp_msm_shared_weights_grouped for the step-instance folds of all proofs that
+//               parsed, and the matrix evaluations of S_step and S_core through sp_shape_matrix_evals_batched per chunk of sp_shape_matrix_evals_chunk()
+//               proofs (the chunk's eq tables are kept on the key; T_y is cut to each shape's column count) - no product tables, no per-proof launches;
+//   per proof   on the calling thread, each proof in nn_verify's order: nn_verify_transcript of every proof (the shared stage runs under all of it), then
+//               nn_verify_publics, then nn_verify_opening_challenge. This part stays sequential: sp_fold_commitments2, sp_msm, sp_hyrax_commit_small and
+//               the transcript's hash calls drive pk.ctx, and a context is one thread's. Nothing of it was moved to host threads;
+//   opening     the group equations of all survivors as one random linear combination (as spartan2::verify_batch):
+//                 sum_k rho_k (r_k comm_LZ_k + delta_k)  ==  < sum_k rho_k z_vec_k, ck >  +  (sum_k rho_k z_delta_k) h
+//                 sum_k rho'_k (r_k comm_eval_k + beta_k)  ==  (sum_k rho'_k <z_vec_k, R_k>) ck_c  +  (sum_k rho'_k z_beta_k) h_c
+//               (comm_eval_k is a fold of two proof points, not a commitment the verifier forms: it stays on the point side.) If either fails,
+//               nn_verify_opening_check names the proofs with code 6 one by one.
+// rho_k = w[2 k], rho'_k = w[2 k + 1] from the transcript "NeutronNovaZkSNARK::verify_batch": absorb "vk" (digest), "count" (K, 8 bytes LE), per proof in
+// batch order "proof_len" (words, 8 bytes LE) and "proof" (the words, LE), then "seed" (32 bytes) if the caller gave one; squeeze "rho" 2 K times.
+enum { NNZ_VERIFY_BATCH_PER_PROOF = 1, NNZ_VERIFY_BATCH_SHARED = 2 };  // flags of nnz_verify_batch_opts: force one form (0 = by count, NN_VERIFY_BATCH_MIN)
+// the smallest batch the shared form takes by default: the smallest measured K at which its median lay below the minimum of K verify calls
+// (profiles/nn_verify_batch.md: not at K = 2, where the combined opening's fixed cost outweighs what two proofs share; at K = 4 in some runs and not in
+// the recorded one, 0.98 x either way; at K = 8 and 16 in every run)
+static const size_t NN_VERIFY_BATCH_MIN = 8;
+
+static std::vector<fe_t> nn_batch_weights(const NNZkKey& pk, const uint64_t* const* words, const size_t* nwords, size_t count, const uint8_t* seed) {
+  Tr tr(pk.ctx, "NeutronNovaZkSNARK::verify_batch");
+  tr.absorb("vk", pk.vk_digest, 32);
+  auto le8 = [](uint64_t v, uint8_t b[8]) {
+    for (int i = 0; i < 8; ++i) b[i] = (uint8_t)(v >> (8 * i));
+  };
+  uint8_t b8[8];
+  le8(count, b8);
+  tr.absorb("count", b8, 8);
+  for (size_t k = 0; k < count; ++k) {
+    le8(nwords[k], b8);
+    tr.absorb("proof_len", b8, 8);
+    tr.absorb("proof", reinterpret_cast<const uint8_t*>(words[k]), nwords[k] * 8);
+  }
+  if (seed) tr.absorb("seed", seed, 32);
+  std::vector<fe_t> w(2 * count);
+  for (auto& x : w) x = tr.squeeze("rho");
+  return w;
+}
+
+// the step-instance folds of the proofs `live` in one grouped call: group g = proof live[g], its weights and its [rows][np] base rows
+static void nn_batch_fold(const NNZkKey& pk, sp_ctx* on, std::vector<NNVerifyState>& st, const std::vector<size_t>& live) {
+  const size_t G = live.size(), rows = pk.layout.rows(), np = st[live[0]].np;
+  std::vector<fe_t> w(G * np);
+  std::vector<aff_t> bases(G * rows * np), out(G * rows);
+  for (size_t g = 0; g < G; ++g) {
+    const NNVerifyState& s = st[live[g]];
+    std::copy(s.wts.begin(), s.wts.end(), w.begin() + g * np);
+    std::copy(s.fold_bases.begin(), s.fold_bases.end(), bases.begin() + g * rows * np);
+  }
+  ck(sp_msm_shared_weights_grouped(on, u64p(w.data()), np, reinterpret_cast<const uint64_t*>(bases.data()), rows, G, reinterpret_cast<uint64_t*>(out.data())),
+     "fold_commitments (grouped)");
+  for (size_t g = 0; g < G; ++g) std::copy(out.begin() + g * rows, out.begin() + (g + 1) * rows, st[live[g]].folded_comm.begin());
+}
+// A, B, C (r_x, r_y) of S_step and S_core for the proofs `live`, a chunk of proofs per pair of launches; *chunks counts the sp_shape_matrix_evals_batched calls
+static void nn_batch_matrix_evaluations(const NNZkKey& pk, sp_ctx* on, std::vector<NNVerifyState>& st, const std::vector<size_t>& live, uint64_t* chunks) {
+  const size_t KC = sp_shape_matrix_evals_chunk(), nb = pk.nb, nx = pk.nx, ny = pk.ny, nv = pk.num_vars;
+  if (pk.vb_Tx.empty()) {
+    for (size_t j = 0; j < KC; ++j) {
+      sp_table *tx = nullptr, *ty = nullptr;
+      ck(sp_table_zeros(on, (size_t)1 << nx, (size_t)-1, (size_t)-1, &tx), "T_x alloc");
+      pk.vb_Tx.push_back(tx);
+      ck(sp_table_zeros(on, (size_t)1 << ny, (size_t)-1, (size_t)-1, &ty), "T_y alloc");
+      pk.vb_Ty.push_back(ty);
+    }
+  }
+  const sp_shape* shapes[2] = {pk.S_step, pk.S_core};
+  const size_t cols[2] = {nv + 1 + pk.dims.num_public, nv + 1 + pk.dims_core.num_public};
+  for (size_t c0 = 0; c0 < live.size(); c0 += KC) {
+    const size_t kc = std::min(KC, live.size() - c0);
+    for (size_t j = 0; j < kc; ++j) {
+      const fe_t *r_x = st[live[c0 + j]].Uv_X.data() + nb, *r_y = r_x + nx + 1;
+      ck(sp_table_set_len(pk.vb_Ty[j], (size_t)1 << ny, (size_t)-1, (size_t)-1), "T_y len");
+      ck(sp_eq_table_into(on, u64p(r_x), nx, pk.vb_Tx[j]), "T_x");
+      ck(sp_eq_table_into(on, u64p(r_y), ny, pk.vb_Ty[j]), "T_y");
+    }
+    std::vector<fe_t> e(3 * kc);
+    for (int s2 = 0; s2 < 2; ++s2) {
+      for (size_t j = 0; j < kc; ++j) ck(sp_table_set_len(pk.vb_Ty[j], cols[s2], (size_t)-1, (size_t)-1), "T_y as z");
+      ck(sp_shape_matrix_evals_batched(on, shapes[s2], pk.vb_Tx.data(), pk.vb_Ty.data(), kc, u64p(e.data())), "matrix_evals_batched");
+      ++*chunks;
+      for (size_t j = 0; j < kc; ++j)
+        for (int m = 0; m < 3; ++m) st[live[c0 + j]].eabc[s2][m] = e[3 * j + m];
+    }
+  }
+}
+
+static void nn_verify_batch(const NNZkKey& pk, const uint64_t* const* words, const size_t* nwords, size_t count, const uint8_t* seed, int* codes,
+                            ss_verify_batch_info* info, unsigned flags) {
+  sp_ctx* ctx = pk.ctx;
+  ss_verify_batch_info inf{0, 1, 0, 0};
+  if (info) *info = inf;
+  if (count == 0) return;
+  const bool shared = (flags & NNZ_VERIFY_BATCH_SHARED) ? true : (flags & NNZ_VERIFY_BATCH_PER_PROOF) ? false : count >= NN_VERIFY_BATCH_MIN;
+  if (count == 1 || !shared) {  // nothing to share, or not enough of it: the single-proof form, proof after proof
+    for (size_t k = 0; k < count; ++k) codes[k] = nn_verify(pk, words[k], nwords[k]);
+    return;
+  }
+  ck(sp_ctx_bind_thread(ctx), "device");  // the caller may be a thread other than the one that created the context
+  // the weights need the proofs alone: hashed on a thread of their own under everything up to the combined opening
+  std::future<std::vector<fe_t>> weights = std::async(std::launch::async, [&] { return nn_batch_weights(pk, words, nwords, count, seed); });
+  struct Join {
+    std::future<std::vector<fe_t>>& f;
+    ~Join() {
+      if (f.valid()) f.wait();
+    }
+  } join{weights};
+  std::vector<NNVerifyState> st(count);
+  parallel_for(count, (size_t)1 << 20, [&](size_t k) { codes[k] = nn_verify_parse(pk, words[k], nwords[k], st[k]); });
+  std::vector<size_t> live;
+  for (size_t k = 0; k < count; ++k)
+    if (codes[k] == 0) live.push_back(k);
+  if (live.empty()) return;
+  // the shared device stage, on the second context's worker beside the transcript work below
+  const std::vector<size_t> parsed = live;  // (declared before the guard: the jobs read it until they are drained, on every exit)
+  struct Drain {  // the jobs read `parsed` and read and write `st` and `inf`: all three outlive this guard
+    Worker& w;
+    ~Drain() { w.drain(); }
+  } drain{pk.v_wk};
+  if (!pk.v_ctx2) ck(sp_ctx_create(sp_ctx_device(ctx), &pk.v_ctx2), "second context");
+  const size_t t_mat = pk.v_wk.submit([&] {  // (needed first: check 5 comes before the opening)
+    ck(sp_ctx_bind_thread(pk.v_ctx2), "device");
+    nn_batch_matrix_evaluations(pk, pk.v_ctx2, st, parsed, &inf.matrix_chunks);
+  });
+  const size_t t_fold = pk.v_wk.submit([&] { nn_batch_fold(pk, pk.v_ctx2, st, parsed); });
+  // per proof, every proof in nn_verify's order (each has its own transcript): the transcript step of all proofs first, so that the shared stage has the
+  // whole batch's transcript work to run under, then the public values of all, then the opening up to its challenge
+  auto step = [&](auto&& f) {
+    std::vector<size_t> next;
+    for (size_t k : live)
+      if ((codes[k] = f(st[k])) == 0) next.push_back(k);
+    live.swap(next);
+  };
+  step([&](NNVerifyState& s) { return nn_verify_transcript(pk, s); });
+  pk.v_wk.wait(t_mat);
+  step([&](NNVerifyState& s) { return nn_verify_publics(pk, s); });
+  pk.v_wk.wait(t_fold);
+  step([&](NNVerifyState& s) { return nn_verify_opening_challenge(pk, s); });
+  const std::vector<fe_t> w = weights.get();
+  if (!live.empty()) {
+    const size_t nz = DEFAULT_COMMITMENT_WIDTH, n = live.size();
+    inf.opening_proofs = n;
+    std::vector<fe_t> zsum(nz, fe_zero()), s1(2 * n), s2(2 * n);
+    std::vector<aff_t> p1(2 * n), p2(2 * n);
+    fe_t zd = fe_zero(), c2 = fe_zero(), b2 = fe_zero();
+    for (size_t i = 0; i < n; ++i) {
+      const NNVerifyState& s = st[live[i]];
+      const fe_t rho = w[2 * live[i]], rho2 = w[2 * live[i] + 1];
+      zd = fe_add<S>(zd, fe_mul<S>(rho, *s.pv.z_delta));
+      p1[2 * i] = s.comm_LZ;
+      s1[2 * i] = fe_mul<S>(rho, s.rr);
+      p1[2 * i + 1] = *s.pv.delta;
+      s1[2 * i + 1] = rho;
+      p2[2 * i] = s.comm_eval;
+      s2[2 * i] = fe_mul<S>(rho2, s.rr);
+      p2[2 * i + 1] = *s.pv.beta;
+      s2[2 * i + 1] = rho2;
+      c2 = fe_add<S>(c2, fe_mul<S>(rho2, s.ip));
+      b2 = fe_add<S>(b2, fe_mul<S>(rho2, *s.pv.z_beta));
+    }
+    parallel_for(8, (size_t)1 << 20, [&](size_t part) {  // sum_k rho_k z_vec_k, a column range per thread
+      for (size_t j = part * nz / 8, e = (part + 1) * nz / 8; j < e; ++j)
+        for (size_t i = 0; i < n; ++i) zsum[j] = fe_add<S>(zsum[j], fe_mul<S>(w[2 * live[i]], st[live[i]].pv.z_vec[j]));
+    });
+    ZJob zj;
+    zj.ctx = ctx;
+    zj.key = pk.ck;
+    ck(sp_msm_ck_begin(ctx, pk.ck, u64p(zsum.data()), nz, &zj.job), "<sum rho z, ck> (begin)");
+    aff_t lhs1, lhs2, rhs1, rhs2;
+    ck(sp_msm(ctx, u64p(s1.data()), u64p(&p1[0].x), 2 * n, u64p(&lhs1.x)), "sum rho (r comm_LZ + delta)");
+    ck(sp_msm(ctx, u64p(s2.data()), u64p(&p2[0].x), 2 * n, u64p(&lhs2.x)), "sum rho' (r comm_eval + beta)");
+    ck(sp_hyrax_commit_small(ctx, pk.vc_ck, u64p(&c2), 1, u64p(&b2), u64p(&rhs2.x)), "combined right side of the second equation");
+    {
+      sp_msm_job* j = zj.job;
+      zj.job = nullptr;
+      ck(sp_msm_ck_finish(ctx, pk.ck, j, u64p(&zd), u64p(&rhs1.x)), "<sum rho z, ck> (finish)");
+    }
+    const bool ok = same_point(jac_from_affine(lhs1), jac_from_affine(rhs1)) && same_point(jac_from_affine(lhs2), jac_from_affine(rhs2));
+    inf.opening_batched_ok = ok ? 1 : 0;
+    if (!ok) {
+      for (size_t k : live) codes[k] = nn_verify_opening_check(pk, st[k]);
+      inf.fallback_proofs = n;
+    }
+  }
+  if (info) *info = inf;
 }
 
 // ---- R1CSShape::is_sat (src/r1cs/mod.rs:358-394) on every instance of a prepared state ---------------------------------------------------------------
@@ -1727,5 +2008,50 @@ int nnz_verify_bytes(void* pk, const uint8_t* bytes, size_t n) {
   } catch (...) {
     return catch_all_nn();
   }
+}
+// verify_batch (see nn_verify_batch): `count` proofs of this key, codes[k] = what nnz_verify returns for proof k (0 accept, 1, 2, 4, 5, 6). seed: 32 bytes mixed
+// into the weights of the combined opening check, or NULL. info may be NULL. flags: 0 = the form the batch size calls for, NNZ_VERIFY_BATCH_PER_PROOF (1) =
+// one nnz_verify after the other, NNZ_VERIFY_BATCH_SHARED (2) = the shared stage and the combined opening from two proofs on. Returns 0, or < 0 = library
+// error (the codes are then meaningless); count != 0 with a null array is refused.
+int nnz_verify_batch_opts(void* pk, const uint64_t* const* words, const size_t* nwords, size_t count, const uint8_t* seed, int* codes, ss_verify_batch_info* info,
+                          unsigned flags) {
+  try {
+    if (!pk || (count && (!words || !nwords || !codes))) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "nnz_verify_batch: null argument");
+    nn_verify_batch(*(NNZkKey*)pk, words, nwords, count, seed, codes, info, flags);
+    return 0;
+  } catch (...) {
+    return catch_all_nn();
+  }
+}
+int nnz_verify_batch(void* pk, const uint64_t* const* words, const size_t* nwords, size_t count, const uint8_t* seed, int* codes, ss_verify_batch_info* info) {
+  return nnz_verify_batch_opts(pk, words, nwords, count, seed, codes, info, 0);
+}
+// the same over serialised proofs: bytes that do not decode to a proof of this key get code 1, as in nnz_verify_bytes
+int nnz_verify_bytes_batch_opts(void* pk_, const uint8_t* const* bytes, const size_t* nbytes, size_t count, const uint8_t* seed, int* codes, ss_verify_batch_info* info,
+                                unsigned flags) {
+  try {
+    if (!pk_ || (count && (!bytes || !nbytes || !codes))) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "nnz_verify_bytes_batch: null argument");
+    auto* pk = (NNZkKey*)pk_;
+    std::vector<std::vector<uint64_t>> store(count);
+    std::vector<const uint64_t*> words(count);
+    std::vector<size_t> nwords(count);
+    for (size_t k = 0; k < count; ++k) {
+      try {
+        store[k] = pk->layout.from_bytes(bytes[k], nbytes[k]);
+      } catch (const Error& e) {
+        if (e.code != SP_ERR_INVALID_INPUT_LENGTH) throw;
+        store[k].clear();  // no words, which fails the length check of the parse with code 1
+      }
+      words[k] = store[k].data();
+      nwords[k] = store[k].size();
+    }
+    nn_verify_batch(*pk, words.data(), nwords.data(), count, seed, codes, info, flags);
+    return 0;
+  } catch (...) {
+    return catch_all_nn();
+  }
+}
+int nnz_verify_bytes_batch(void* pk, const uint8_t* const* bytes, const size_t* nbytes, size_t count, const uint8_t* seed, int* codes, ss_verify_batch_info* info) {
+  return nnz_verify_bytes_batch_opts(pk, bytes, nbytes, count, seed, codes, info, 0);
 }
 }

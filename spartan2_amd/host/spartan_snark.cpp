@@ -17,17 +17,6 @@
 
 #include "proof_layout.hpp"
 
-// What ss_verify_batch / ss_verify_bytes_batch report beside the codes (C layout: four 64-bit words; host.py VerifyBatchInfo mirrors it). The ss_* surface
-// of this library has no header of its own: its types are declared here, at global scope, as a C caller would repeat them.
-extern "C" {
-typedef struct ss_verify_batch_info {
-  uint64_t matrix_chunks;       // sp_shape_matrix_evals_batched calls
-  uint64_t opening_batched_ok;  // 1: the combined equations held (or no proof reached them)
-  uint64_t fallback_proofs;     // proofs that went through the single-proof opening_check
-  uint64_t opening_proofs;      // proofs that reached the combined equations
-} ss_verify_batch_info;
-}
-
 namespace spartan2 {
 
 // ---- keys / state ----------------------------------------------------------------------------------------------------------

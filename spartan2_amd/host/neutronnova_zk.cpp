@@ -364,45 +364,78 @@ static void absorb_instance(Tr& tr, const char* label, const std::vector<aff_t>&
   for (size_t j = 0; j < X.size(); ++j) sp::fe_to_be_bytes<S>(X[j], b.data() + off + 32 * j);
   tr.absorb(label, b.data(), b.size());
 }
-// rows of `n` host scalars committed with the width-32 key in one device call (many rows: T, the random instance)
+// the transcript's head, as the prover and the verifier absorb it: the key's digest and the core instance
+static void absorb_head(Tr& tr, const NNZkKey& pk, const std::vector<aff_t>& core_comm, const std::vector<fe_t>& core_X) {
+  tr.absorb("vk", pk.vk_digest, 32);
+  absorb_instance(tr, "core_instance", core_comm, core_X);
+}
+// NovaNIFS (src/nifs.rs:34-77), both sides: U1, the random relaxed instance (comm_W, comm_E, u, X) ...
+static void absorb_U1(Tr& tr, const aff_t* comm_W, size_t rows_W, const aff_t* comm_E, size_t rows_E, const fe_t& u, const fe_t* X, size_t nX) {
+  std::vector<uint8_t> b = commitment_bytes(comm_W, rows_W), e = commitment_bytes(comm_E, rows_E);
+  b.insert(b.end(), e.begin(), e.end());
+  const size_t off = b.size();
+  b.resize(off + 32 * (1 + nX));
+  sp::fe_to_be_bytes<S>(u, b.data() + off);
+  for (size_t j = 0; j < nX; ++j) sp::fe_to_be_bytes<S>(X[j], b.data() + off + 32 * (1 + j));
+  tr.absorb("U1", b.data(), b.size());
+}
+// ... and the commitment of the cross term
+static void absorb_comm_T(Tr& tr, const aff_t* comm_T, size_t rows_T) {
+  const std::vector<uint8_t> b = commitment_bytes(comm_T, rows_T);
+  tr.absorb("comm_T", b.data(), b.size());
+}
+// SPARTAN_HOST_LAPS=1 (read once per process): one stderr line per lap of a prove or a verify, "<who> lap <what> <ms since the last lap>"
+struct NNLaps {
+  const char* who;
+  bool on = false;
+  double t_lap = 0;
+  static double now() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+  void start(double t) {
+    static const bool laps = [] {
+      const char* e = getenv("SPARTAN_HOST_LAPS");
+      return e && e[0] == '1';
+    }();
+    on = laps;
+    t_lap = t;
+  }
+  void lap(const char* what) {
+    if (!on) return;
+    const double t = now();
+    fprintf(stderr, "%s lap %-28s %8.3f ms\n", who, what, t - t_lap);
+    t_lap = t;
+  }
+};
+// a grow-only device table of a prep state with `len` elements: when `len` outgrows it, it is allocated again - with room to spare (at least 4096, else
+// twice `len`: the scratch slots, whose users differ in size) or exactly - and its length is set. Contents are whatever its last user left.
+static sp_table* grown_slot(sp_ctx* ctx, sp_table*& t, size_t& cap, size_t len, bool spare, const char* what, const char* what_len) {
+  if (len > cap) {  // per slot: other slots may be in use by the caller
+    sp_table_free(t);
+    t = nullptr;
+    cap = !spare ? len : len < 4096 ? 4096 : 2 * len;
+  }
+  if (!t) ck(sp_table_zeros(ctx, cap, (size_t)-1, (size_t)-1, &t), what);
+  ck(sp_table_set_len(t, len, (size_t)-1, (size_t)-1), what_len);
+  return t;
+}
 // slot `i` of the prep state's scratch tables holding `n` elements of host data
 static sp_table* stage(sp_ctx* ctx, NNZkPrep& ps, int i, const fe_t* data, size_t n) {
-  if (n > ps.vws_cap[i]) {  // grow-only, per slot: other slots may be in use by the caller
-    sp_table_free(ps.vws[i]);
-    ps.vws[i] = nullptr;
-    ps.vws_cap[i] = n < 4096 ? 4096 : 2 * n;
-  }
-  if (!ps.vws[i]) ck(sp_table_zeros(ctx, ps.vws_cap[i], (size_t)-1, (size_t)-1, &ps.vws[i]), "scratch table");
-  ck(sp_table_set_len(ps.vws[i], n, (size_t)-1, (size_t)-1), "scratch len");
-  ck(sp_table_write(ctx, ps.vws[i], 0, u64p(data), n), "upload");
-  return ps.vws[i];
+  sp_table* t = grown_slot(ctx, ps.vws[i], ps.vws_cap[i], n, true, "scratch table", "scratch len");
+  ck(sp_table_write(ctx, t, 0, u64p(data), n), "upload");
+  return t;
 }
-// working table `i` of the prep state with `len` elements (grow-only; contents are whatever the last prove left: every user writes what it reads)
-static sp_table* work_table(sp_ctx* ctx, NNZkPrep& ps, int i, size_t len) {
-  if (len > ps.work_cap[i]) {
-    sp_table_free(ps.work[i]);
-    ps.work[i] = nullptr;
-    ps.work_cap[i] = len;
-  }
-  if (!ps.work[i]) ck(sp_table_zeros(ctx, ps.work_cap[i], (size_t)-1, (size_t)-1, &ps.work[i]), "working table");
-  ck(sp_table_set_len(ps.work[i], len, (size_t)-1, (size_t)-1), "working table len");
-  return ps.work[i];
-}
-// the same for the helper thread's jobs: tables of their own, on the second context
+// working table `i` of the prep state with `len` elements (every user writes what it reads)
+static sp_table* work_table(sp_ctx* ctx, NNZkPrep& ps, int i, size_t len) { return grown_slot(ctx, ps.work[i], ps.work_cap[i], len, false, "working table", "working table len"); }
+// rows of host scalars committed with the width-32 key in one device call (many rows: T, the random instance) ...
+// ... by the helper thread's jobs: tables of their own, on the second context
 static std::vector<aff_t> commit_rows32_side(NNZkPrep& ps, int slot, const sp_ck* vc_ck, const std::vector<fe_t>& v, const std::vector<fe_t>& blinds) {
   sp_ctx* ctx = ps.ctx2;
-  if (v.size() > ps.bws_cap[slot]) {
-    sp_table_free(ps.bws[slot]);
-    ps.bws[slot] = nullptr;
-    ps.bws_cap[slot] = v.size() < 4096 ? 4096 : 2 * v.size();
-  }
-  if (!ps.bws[slot]) ck(sp_table_zeros(ctx, ps.bws_cap[slot], (size_t)-1, (size_t)-1, &ps.bws[slot]), "scratch table");
-  ck(sp_table_set_len(ps.bws[slot], v.size(), (size_t)-1, (size_t)-1), "scratch len");
-  ck(sp_table_write(ctx, ps.bws[slot], 0, u64p(v.data()), v.size()), "upload");
+  sp_table* t = grown_slot(ctx, ps.bws[slot], ps.bws_cap[slot], v.size(), true, "scratch table", "scratch len");
+  ck(sp_table_write(ctx, t, 0, u64p(v.data()), v.size()), "upload");
   std::vector<aff_t> out(blinds.size());
-  ck(sp_hyrax_commit(ctx, vc_ck, ps.bws[slot], 0, v.size(), u64p(blinds.data()), 0, u64p(&out[0].x)), "commit (width 32)");
+  ck(sp_hyrax_commit(ctx, vc_ck, t, 0, v.size(), u64p(blinds.data()), 0, u64p(&out[0].x)), "commit (width 32)");
   return out;
 }
+// ... and on the caller's context
 static std::vector<aff_t> commit_rows32(sp_ctx* ctx, NNZkPrep& ps, const sp_ck* vc_ck, const std::vector<fe_t>& v, const std::vector<fe_t>& blinds, bool latency = false) {
   std::vector<aff_t> out(blinds.size());
   // the latency form (one launch through mapped memory, the rows added by the library's polling threads) where the commitment sits in the transcript chain
@@ -434,172 +467,431 @@ static void prove_direct(size_t num_cols, const std::vector<fe_t>& poly, const s
   for (size_t i = 0; i < blind.size() && i < L.size(); ++i) *cb = fe_add<S>(*cb, fe_mul<S>(L[i], blind[i]));
 }
 
-// prove (:1609-2093)
+// the evaluation of [1 | X | 0 ..] at r_y[1..] (the X part of z, :1921-1935 and :2290-2300)
+static fe_t nn_eval_X(size_t ny, const fe_t* X, size_t cnt, const fe_t* r_y) {
+  std::vector<fe_t> v{fe_one<S>()};
+  v.insert(v.end(), X, X + cnt);
+  return sparse_poly_evaluate(ny - 1, v, r_y + 1);
+}
+// out = a + w * b over n points: the fold begun on b's doubling ladders is finished (and the job consumed), else it is one call
+static void fold2_finish_or_call(sp_ctx* ctx, sp_fold2_job*& job, const aff_t* a, const aff_t* b, size_t n, const fe_t& w, aff_t* out, const char* what) {
+  if (job) {
+    sp_fold2_job* j = job;
+    job = nullptr;
+    ck(sp_fold_commitments2_finish(ctx, j, u64p(&a->x), u64p(&w), u64p(&out->x)), what);
+  } else {
+    ck(sp_fold_commitments2(ctx, u64p(&a->x), u64p(&b->x), n, u64p(&w), u64p(&out->x)), what);
+  }
+}
+// sample_random_instance_witness (src/r1cs/mod.rs:474-531) on the verifier-circuit shape: Z = [W | u | X] and the blinds from `tape`, E = Az o Bz - u Cz, the
+// two width-32 commitments through commit(slot, values, blinds). Values from the randomness tape only.
+template <class Commit>
+static void sample_random_instance(const vcirc::Shape& vs, Tape& tape, NNZkPrep::RandomInstance& R, Commit commit) {
+  const size_t vnv = vs.total_vars, vcons = vs.num_cons, vio = vs.num_io();
+  R.tape_from = tape.pos;
+  R.Z.resize(vnv + vio + 1);
+  for (auto& z : R.Z) z = tape.next();
+  R.rW.resize(vnv / 32);
+  R.rE.resize(vcons / 32);
+  for (auto& b : R.rW) b = tape.next();
+  for (auto& b : R.rE) b = tape.next();
+  R.tape_count = tape.pos - R.tape_from;
+  std::vector<fe_t> mv[3];
+  vs.multiply_vec(R.Z, mv);
+  const fe_t u = R.Z[vnv];
+  R.E.resize(vcons);
+  for (size_t i = 0; i < vcons; ++i) R.E[i] = fe_sub<S>(fe_mul<S>(mv[0][i], mv[1][i]), fe_mul<S>(u, mv[2][i]));
+  R.comm_W = commit(0, std::vector<fe_t>(R.Z.begin(), R.Z.begin() + vnv), R.rW);
+  R.comm_E = commit(1, R.E, R.rE);
+}
+
+// ---- the helper's jobs and the guards of a prove: members of NNProveState (below), which states when they end ------------------------------------------
+// The random relaxed instance ahead of its place: its values sit at a position of the tape that only the shapes determine; checked again where it is used
+struct NNRandomInstanceJob {
+  const NNZkKey* pk = nullptr;
+  NNZkPrep* ps = nullptr;
+  Tape ahead{nullptr, 0};
+  void run() {
+    NNZkPrep::RandomInstance& R = ps->rnd;
+    try {
+      ck(sp_ctx_bind_thread(ps->ctx2), "device");
+      sample_random_instance(pk->vc, ahead, R, [&](int slot, const std::vector<fe_t>& v, const std::vector<fe_t>& bl) { return commit_rows32_side(*ps, slot, pk->vc_ck, v, bl); });
+      R.valid = true;
+    } catch (...) {
+      R.valid = false;  // the prover computes it inline when it gets there (and reports what fails, if it fails again)
+    }
+  }
+};
+// the fold of the step instances' commitments, handed over by nifs_prove (it writes the state's f_comm)
+struct NNFoldJob {
+  NNZkPrep* ps = nullptr;
+  std::function<void(sp_ctx*)> job;
+  void run() {
+    ck(sp_ctx_bind_thread(ps->ctx2), "device");
+    job(ps->ctx2);
+  }
+};
+// delta (ipa.rs:139-147): the mask and its blinds follow the random instance and NovaNIFS's r_T on the tape
+struct NNDeltaJob {
+  const NNZkKey* pk = nullptr;
+  NNZkPrep* ps = nullptr;
+  Tape ahead{nullptr, 0};
+  void run() {
+    NNZkPrep::OpeningAhead& O = ps->open;
+    try {
+      O.tape_from = ahead.pos;
+      O.dv.resize(DEFAULT_COMMITMENT_WIDTH);
+      for (auto& x : O.dv) x = ahead.next();
+      O.r_delta = ahead.next();
+      O.r_beta = ahead.next();
+      O.tape_count = ahead.pos - O.tape_from;
+      ck(sp_msm_ck(ps->ctx2, pk->ck, u64p(O.dv.data()), O.dv.size(), u64p(&O.r_delta), u64p(&O.delta.x)), "delta");
+      O.delta_valid = true;
+    } catch (...) {
+      O.delta_valid = false;
+    }
+  }
+};
+// r_y is known: the halves of comm_LZ and beta, under the verifier-circuit phase (reads the state's f_comm and core_comm)
+struct NNOpeningPointsJob {
+  const NNZkKey* pk = nullptr;
+  NNZkPrep* ps = nullptr;
+  const std::vector<aff_t>*f_comm = nullptr, *core_comm = nullptr;
+  size_t rows = 0;
+  std::vector<fe_t> L, Rv;
+  void run() {
+    NNZkPrep::OpeningAhead& O = ps->open;
+    try {
+      if (!O.delta_valid || Rv.size() != O.dv.size() || L.size() > rows) return;
+      ck(sp_ctx_bind_thread(ps->ctx2), "device");
+      ck(sp_msm(ps->ctx2, u64p(L.data()), u64p(&(*f_comm)[0].x), L.size(), u64p(&O.P_f.x)), "<L, folded rows>");
+      ck(sp_msm(ps->ctx2, u64p(L.data()), u64p(&(*core_comm)[0].x), L.size(), u64p(&O.P_c.x)), "<L, core rows>");
+      fe_t ip = fe_zero();
+      for (size_t i = 0; i < Rv.size(); ++i) ip = fe_add<S>(ip, fe_mul<S>(Rv[i], O.dv[i]));
+      ck(sp_hyrax_commit_small(ps->ctx2, pk->vc_ck, u64p(&ip), 1, u64p(&O.r_beta), u64p(&O.beta.x)), "beta");
+      sp_fold_commitments2_drop(O.lz_fold);
+      O.lz_fold = nullptr;
+      if (sp_fold_commitments2_begin(ps->ctx2, u64p(&O.P_c.x), 1, &O.lz_fold) != SP_OK) O.lz_fold = nullptr;
+      O.points_valid = true;
+    } catch (...) {
+      O.points_valid = false;
+    }
+  }
+};
+// The opening's W = folded_W + c_eval core_W exists only once c_eval is drawn, at the very end - but L^T W (bind_with_delayed, hyrax_pc.rs:38-54) is linear in
+// the table: LZ = L^T folded_W + c_eval L^T core_W, and L = eq(r_y[1..]) is known behind the inner sum-check. The two products run as jobs of the library's
+// vector stream under the verifier-circuit phase (one job at a time: the second is begun where the first is collected).
+struct NNLzAhead {
+  sp_vec_job* job = nullptr;
+  size_t cols = 0;
+  std::vector<fe_t> f, c;
+  int have = 0;  // 1: f, 2: f and c
+  void begin(sp_ctx* ctx, const sp_table* W, const fe_t* r_y, size_t nvr) {
+    if (sp_rowmat_vec_eq_begin(ctx, W, u64p(r_y + 1), nvr, cols, &job) != SP_OK) job = nullptr;
+  }
+  void step(sp_ctx* ctx, const sp_table* next_W, const fe_t* r_y, size_t nvr) {  // collect the product in flight, begin the next
+    if (!job) return;
+    std::vector<fe_t>& dst = have == 0 ? f : c;
+    dst.resize(cols);
+    sp_vec_job* j = job;
+    job = nullptr;
+    if (sp_rowmat_vec_eq_finish(ctx, j, u64p(dst.data())) != SP_OK) return;
+    if (++have == 1) begin(ctx, next_W, r_y, nvr);
+  }
+  void collect(sp_ctx* ctx) {  // an exit path: the job owns device work
+    if (!job) return;
+    std::vector<fe_t> sink(cols);
+    (void)sp_rowmat_vec_eq_finish(ctx, job, u64p(sink.data()));
+    job = nullptr;
+  }
+};
+// the opening folds comm = folded + c_eval * core rows and comm_eval = eW_step + c_eval * eW_core with a weight drawn at the very end: the doubling
+// ladders of the core rows (behind the instances) and of the core evaluation's commitment (behind its round) are built on the library's polling threads meanwhile
+struct NNFold2Jobs {
+  sp_fold2_job *rows = nullptr, *eval = nullptr;
+  void drop() {
+    sp_fold_commitments2_drop(rows);
+    sp_fold_commitments2_drop(eval);
+    rows = eval = nullptr;
+  }
+};
+// what the round hooks of nifs_prove and of the two batched sum-checks reach: process_round on the verifier circuit's state
+struct NNHookCtx {
+  const NNZkKey* pk;
+  vcirc::Circuit* vc;
+  vcirc::State* st;
+  Tr* tr;
+  Tape* tape;
+  size_t outer_start, inner_start;
+  std::exception_ptr err;
+};
+// NIFS (:1770-1783): finish_round! = vc.nifs_polys[t] <- coefficients, then process_round (:703-735); once more after the rounds (:1207-1210)
+static void nn_nifs_hook(void* u, size_t t, const uint64_t* co, uint64_t* r_b) {
+  NNHookCtx* h = (NNHookCtx*)u;
+  if (h->err) return;
+  try {
+    if (t < h->pk->nb) {
+      for (int q = 0; q < 4; ++q) memcpy(&h->vc->nifs_polys[t][q], co + 4 * q, 32);
+      const fe_t r = vcirc::process_round(h->pk->ctx, *h->st, h->pk->vc, h->pk->vc_ck, *h->vc, t, *h->tr, *h->tape)[0];
+      memcpy(r_b, &r, 32);
+    } else {
+      memcpy(&h->vc->t_out_step, co, 32);
+      memcpy(&h->vc->eq_rho_at_rb, co + 4, 32);
+      vcirc::process_round(h->pk->ctx, *h->st, h->pk->vc, h->pk->vc_ck, *h->vc, t, *h->tr, *h->tape);
+    }
+  } catch (...) {
+    h->err = std::current_exception();
+  }
+}
+// a round of the batched outer (4 coefficients) or inner (3) sum-check: the step and the core polynomial into the circuit, then process_round
+static int nn_batched_hook(void* u, size_t round, const uint64_t* cs_, const uint64_t* cc_, size_t ncoeffs, uint64_t r_out[4]) {
+  NNHookCtx* h = (NNHookCtx*)u;
+  try {
+    if (ncoeffs == 4) {
+      const size_t i = round - h->outer_start;
+      for (int q = 0; q < 4; ++q) {
+        memcpy(&h->vc->outer_step[i][q], cs_ + 4 * q, 32);
+        memcpy(&h->vc->outer_core[i][q], cc_ + 4 * q, 32);
+      }
+    } else {
+      const size_t j = round - h->inner_start;
+      for (int q = 0; q < 3; ++q) {
+        memcpy(&h->vc->inner_step[j][q], cs_ + 4 * q, 32);
+        memcpy(&h->vc->inner_core[j][q], cc_ + 4 * q, 32);
+      }
+    }
+    const fe_t r = vcirc::process_round(h->pk->ctx, *h->st, h->pk->vc, h->pk->vc_ck, *h->vc, round, *h->tr, *h->tape)[0];
+    memcpy(r_out, &r, 32);
+    return 0;
+  } catch (...) {
+    h->err = std::current_exception();
+    return SP_ERR_INTERNAL;
+  }
+}
+
+// ---- prove (:1609-2093) ---------------------------------------------------------------------------------------------------------------------------------
+// A sequence of named steps over one NNProveState, in the order of the reference's statements; nn_prove runs them for both drivers:
+//   nn_prove_setup             the device, the polling threads, the round-hooks promise; (side) the second context and the random instance's job
+//   nn_prove_rerandomize       core (shared, precommitted), then every step's precommitted commitment, one call                  (:1619-1627)
+//   nn_prove_rest_commitments  the rest rows' blinds; commit_zeros, or the rest segments of several instances per call           (:1662-1719)
+//   nn_prove_instances         the instances' rows and blinds, the proof's header; (side) the core rows' ladders begin           (:1662-1719)
+//   nn_prove_nifs              the transcript's head, the hooks, nifs_prove; (side) the fold's and delta's jobs                  (:1770-1783)
+//   nn_prove_outer             core products, the batched outer sum-check, the claims' round                                     (:1786-1850)
+//   nn_prove_inner             evals_rx, both poly_ABC, the z tables, the batched inner sum-check, the evaluation rounds;        (:1852-1945)
+//                              (side) the opening-points job, L^T folded_W begun, the core evaluation's ladder
+//   nn_prove_vc_instance       finalize_multiround_witness                                                                       (:1948-1952)
+//   nn_prove_random_instance   sample_random_instance_witness: the job's, or inline                                              (src/r1cs/mod.rs:474-531)
+//   nn_prove_nova_nifs         NovaNIFS::prove and the fold of instance and witness                                              (src/nifs.rs:34-61)
+//   nn_prove_relaxed_spartan   RelaxedR1CSSpartanProof::prove                                                                    (src/spartan_relaxed.rs:98-213)
+//   nn_prove_opening           the two evaluation claims folded, then nn_open_reference_order or nn_open_side                    (:2019-2080)
+//   nn_prove_emit              the rest of the proof in the canonical layout, the phase times, the layout check
 // reference_order: ONE thread, the statements of src/neutronnova_zk.rs:1609-2093 in their order, ABI calls only — no jobs on a second context, the folded
 // opening as the single PCS::prove call (sp_hyrax_prove) — what an unchanged neutronnova_zk.rs over the shim of integration/ gets. Same proof.
-static ProofBuf nn_prove(const NNZkKey& pk, NNZkPrep& ps, Tape& tape, double* phase_ms, bool reference_order = false) {
-  sp_ctx* ctx = pk.ctx;
-  const sp_dims& d = pk.dims;
-  const size_t CW = DEFAULT_COMMITMENT_WIDTH, n = ps.steps.size(), nv = pk.num_vars, N = d.num_cons;
-  const size_t rows_sh = d.num_shared_unpadded ? d.num_shared / CW : 0, rows_pre = d.num_precommitted_unpadded ? d.num_precommitted / CW : 0, rows_rest = d.num_rest / CW;
-  const size_t rows = rows_sh + rows_pre + rows_rest, dpub = d.num_public;
-  // the core circuit may split the same number of rows differently (nn_setup: equal shared segment, equal total after equalize)
-  const sp_dims& dc = pk.dims_core;
-  const size_t rows_pre_c = dc.num_precommitted_unpadded ? dc.num_precommitted / CW : 0, rows_rest_c = dc.num_rest / CW;
-  if (rows_sh + rows_pre_c + rows_rest_c != rows) throw Error(SP_ERR_INTERNAL, "NeutronNova: step and core rows differ after equalize");
-  auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  const double t_start = now();
-  static const bool laps = [] {
-    const char* e = getenv("SPARTAN_HOST_LAPS");
-    return e && e[0] == '1';
-  }();
-  double t_lap = t_start;
-  auto lap = [&](const char* what) {
-    if (!laps) return;
-    const double t = now();
-    fprintf(stderr, "nn_prove lap %-28s %8.3f ms\n", what, t - t_lap);
-    t_lap = t;
-  };
-  ck(sp_ctx_bind_thread(ctx), "device");
+//
+// LIFETIME RULE, stated here once: whatever a job on ps.wk, a begun sp_fold2_job or a begun sp_vec_job reads or writes is a member of this state (or of the
+// key / the prep state, which outlive it). ~NNProveState runs on every exit path, exceptions included, and its BODY - which runs before any member is
+// destroyed, whatever their declaration order - (1) drains ps.wk, (2) collects the outstanding vector job, (3) drops the fold-2 jobs, (4) resets the
+// round-hooks promise. A step must not hand a job the address of one of its locals.
+struct NNProveState {
+  const NNZkKey& pk;
+  NNZkPrep& ps;
+  Tape& tape;
+  sp_ctx* const ctx;
+  const bool reference_order, side;  // side = !reference_order: jobs on the second context (false = everything inline on the caller's context, in the steps' order)
+  // row counts and dimensions. The core circuit may split the same number of rows differently (nn_setup: equal shared segment, equal total after equalize)
+  const sp_dims &d, &dc;
+  const size_t CW = DEFAULT_COMMITMENT_WIDTH, n, nv, N, dpub;
+  const size_t rows_sh, rows_pre, rows_rest, rows, rows_pre_c, rows_rest_c, nvr;
+  ProofBuf proof;
+  // the instances
+  std::vector<aff_t> comms, core_comm, all_c_rest;
+  std::vector<fe_t> X, r_W, core_rW, all_rest;
+  std::vector<const sp_table*> Ws;
+  // the transcript, the verifier circuit and what the hooks reach
+  std::unique_ptr<Tr> tr;
+  std::unique_ptr<vcirc::Circuit> vc;
+  std::unique_ptr<vcirc::State> vst;
+  NNHookCtx hc{};
+  // the NIFS outputs and the working tables
+  size_t left = 0, right = 0;
+  std::vector<uint64_t> polys, r_bs, E_eq, tail, f_rW, f_X;
+  std::vector<aff_t> f_comm;
+  sp_table *A = nullptr, *B = nullptr, *C = nullptr, *fW = nullptr, *core_abc[3] = {}, *zc = nullptr, *pl = nullptr, *pr = nullptr, *rx = nullptr;
+  sp_table *abc_s = nullptr, *abc_c = nullptr, *zs = nullptr, *zcc = nullptr, *Wf = nullptr;
+  // the helper's jobs with their tickets, the begun folds, the product ahead, the promise
+  NNRandomInstanceJob rnd_job;
+  NNFoldJob fold_job;
+  NNDeltaJob delta_job;
+  NNOpeningPointsJob points_job;
+  size_t t_rnd = 0, t_fold = 0, t_open = 0;
+  NNFold2Jobs fold2;
+  NNLzAhead lz;
+  bool hooks_promised = false;
+  // the batched sum-checks
+  fe_t r, claims[2], fin[4];
+  std::vector<fe_t> r_x, r_y, folded_X;
+  size_t inner_final = 0;
+  // the verifier-circuit instance, the random one, their fold, the relaxed Spartan proof
+  std::vector<fe_t> vpub, Uv_X, Wv_r;
+  std::vector<aff_t> Uv_comm;
+  NNZkPrep::RandomInstance rnd;
+  fe_t rnd_u, ufold;
+  std::vector<fe_t> rnd_W, rnd_X, r_T, T, Wfold, Efold, rWfold, rEfold, Xfold;
+  std::vector<aff_t> comm_T;
+  std::vector<fe_t> v_outer, v_inner, v_W, v_E;
+  fe_t v_claims[3], blind_vW, blind_vE;
+  // the opening: the folded claim (commitment rows, their blinds, the evaluation's commitment and blind) and the argument's values
+  fe_t c_eval, blind_eval;
+  std::vector<aff_t> comm;
+  std::vector<fe_t> blind;
+  aff_t comm_eval, delta, beta;
+  std::vector<fe_t> z_vec;
+  fe_t z_delta, z_beta;
+  // time stamps and laps
+  double t_start = 0, t_inst = 0, t_nifs = 0, t_outer = 0, t_inner = 0, t_vc = 0, t_end = 0;
+  NNLaps laps{"nn_prove"};
+
+  static size_t seg_rows(size_t unpadded, size_t padded) { return unpadded ? padded / DEFAULT_COMMITMENT_WIDTH : 0; }
+  NNProveState(const NNZkKey& pk_, NNZkPrep& ps_, Tape& tape_, bool reference_order_)
+      : pk(pk_), ps(ps_), tape(tape_), ctx(pk_.ctx), reference_order(reference_order_), side(!reference_order_), d(pk_.dims), dc(pk_.dims_core), n(ps_.steps.size()),
+        nv(pk_.num_vars), N(d.num_cons), dpub(d.num_public), rows_sh(seg_rows(d.num_shared_unpadded, d.num_shared)),
+        rows_pre(seg_rows(d.num_precommitted_unpadded, d.num_precommitted)), rows_rest(d.num_rest / CW), rows(rows_sh + rows_pre + rows_rest),
+        rows_pre_c(seg_rows(dc.num_precommitted_unpadded, dc.num_precommitted)), rows_rest_c(dc.num_rest / CW), nvr(log2_ceil(rows)) {
+    if (rows_sh + rows_pre_c + rows_rest_c != rows) throw Error(SP_ERR_INTERNAL, "NeutronNova: step and core rows differ after equalize");
+  }
+  NNProveState(const NNProveState&) = delete;
+  NNProveState& operator=(const NNProveState&) = delete;
+  ~NNProveState() {  // the lifetime rule above
+    ps.wk.drain();
+    lz.collect(ctx);
+    fold2.drop();
+    if (hooks_promised) sp_ctx_round_hooks_host_only(ctx, 0);
+  }
+  template <class Job>
+  size_t submit(Job& job) {  // `job` is a member of this state
+    return ps.wk.submit([&job] { job.run(); });
+  }
+  static double now() { return NNLaps::now(); }
+};
+
+static void nn_prove_setup(NNProveState& st) {
+  const NNZkKey& pk = st.pk;
+  NNZkPrep& ps = st.ps;
+  ck(sp_ctx_bind_thread(st.ctx), "device");
   ck(sp_walkers_keep_hot(20000), "walkers");  // the round commitments and the host loops of the verifier-circuit instance are spread over them
   // process_round is host work when its commitments go through the walkers: the batched sum-checks may then queue a round's launch ahead of it
-  struct HookPromise {
-    sp_ctx* c;
-    ~HookPromise() { sp_ctx_round_hooks_host_only(c, 0); }
-  } hook_promise{ctx};
-  ck(sp_ctx_round_hooks_host_only(ctx, vcirc::split_commitments_on(pk.vc_ck) ? 1 : 0), "round hooks");
-  const bool side = !reference_order;  // (false = everything inline on the caller's context: the order the phase comments describe)
-  struct SideGuard {  // no exit path leaves a job running on state this call owns
-    NNZkPrep& ps;
-    ~SideGuard() { ps.wk.drain(); }
-  } side_guard{ps};
+  st.hooks_promised = true;
+  ck(sp_ctx_round_hooks_host_only(st.ctx, vcirc::split_commitments_on(pk.vc_ck) ? 1 : 0), "round hooks");
   ps.rnd.valid = false;
   ps.open.delta_valid = ps.open.points_valid = false;
-  size_t t_rnd = 0, t_fold = 0, t_open = 0;  // tickets of the helper's jobs
-  if (side) {
-    if (!ps.ctx2) ck(sp_ctx_create(sp_ctx_device(ctx), &ps.ctx2), "second context");
-    // the random relaxed instance: its values sit at a position of the tape that only the shapes determine (the draws in front of it are the
-    // rerandomisation blinds, the rest-row blinds and one blind per committed row of the verifier circuit's rounds); checked again where it is used
-    size_t before = ps.comm_shared.size() + ps.core.comm_pre.size() + n * rows_rest + rows_rest_c + pk.vc.total_vars / 32;
-    for (const auto& st : ps.steps) before += st.comm_pre.size();
-    Tape ahead = tape;
-    ahead.pos = tape.pos + before;
-    t_rnd = ps.wk.submit([&pk, &ps, ahead]() mutable {
-      const vcirc::Shape& vs = pk.vc;
-      const size_t vnv = vs.total_vars, vcons = vs.num_cons, vio = vs.num_io();
-      NNZkPrep::RandomInstance& R = ps.rnd;
-      try {
-        ck(sp_ctx_bind_thread(ps.ctx2), "device");
-        R.tape_from = ahead.pos;
-        R.Z.resize(vnv + vio + 1);
-        for (auto& z : R.Z) z = ahead.next();
-        R.rW.resize(vnv / 32);
-        R.rE.resize(vcons / 32);
-        for (auto& b : R.rW) b = ahead.next();
-        for (auto& b : R.rE) b = ahead.next();
-        R.tape_count = ahead.pos - R.tape_from;
-        std::vector<fe_t> mv[3];
-        vs.multiply_vec(R.Z, mv);
-        const fe_t u = R.Z[vnv];
-        R.E.resize(vcons);
-        for (size_t i = 0; i < vcons; ++i) R.E[i] = fe_sub<S>(fe_mul<S>(mv[0][i], mv[1][i]), fe_mul<S>(u, mv[2][i]));
-        R.comm_W = commit_rows32_side(ps, 0, pk.vc_ck, std::vector<fe_t>(R.Z.begin(), R.Z.begin() + vnv), R.rW);
-        R.comm_E = commit_rows32_side(ps, 1, pk.vc_ck, R.E, R.rE);
-        R.valid = true;
-      } catch (...) {
-        R.valid = false;  // the prover computes it inline when it gets there (and reports what fails, if it fails again)
-      }
-    });
-  }
-  // rerandomize (:1619-1627, hyrax_pc.rs:321-344): core (shared, precommitted), then every step's precommitted commitment. The new blinds are
-  // drawn in the reference's order; the row updates are independent, so all of them go through ONE sp_hyrax_rerandomize call.
-  {
-    std::vector<std::pair<std::vector<aff_t>*, std::vector<fe_t>*>> parts;
-    parts.push_back({&ps.comm_shared, &ps.r_shared});
-    parts.push_back({&ps.core.comm_pre, &ps.core.r_pre});
-    for (auto& st : ps.steps) parts.push_back({&st.comm_pre, &st.r_pre});
-    std::vector<aff_t> all_c;
-    std::vector<fe_t> all_old, all_new;
-    for (auto& pr_ : parts)
-      for (size_t i = 0; i < pr_.first->size(); ++i) {
-        all_c.push_back((*pr_.first)[i]);
-        all_old.push_back((*pr_.second)[i]);
-        all_new.push_back(tape.next());
-      }
-    if (!all_c.empty()) {
-      std::vector<aff_t> out(all_c.size());
-      ck(sp_hyrax_rerandomize(ctx, pk.ck, u64p(&all_c[0].x), all_c.size(), u64p(all_old.data()), u64p(all_new.data()), u64p(&out[0].x)), "rerandomize_commitment");
-      size_t o = 0;
-      for (auto& pr_ : parts)
-        for (size_t i = 0; i < pr_.first->size(); ++i, ++o) {
-          (*pr_.first)[i] = out[o];
-          (*pr_.second)[i] = all_new[o];
-        }
+  if (!st.side) return;
+  if (!ps.ctx2) ck(sp_ctx_create(sp_ctx_device(st.ctx), &ps.ctx2), "second context");
+  // the draws in front of the random instance's: the rerandomisation blinds, the rest-row blinds and one blind per committed row of the verifier circuit's rounds
+  size_t before = ps.comm_shared.size() + ps.core.comm_pre.size() + st.n * st.rows_rest + st.rows_rest_c + pk.vc.total_vars / 32;
+  for (const auto& s : ps.steps) before += s.comm_pre.size();
+  st.rnd_job.pk = &pk;
+  st.rnd_job.ps = &ps;
+  st.rnd_job.ahead = st.tape;
+  st.rnd_job.ahead.pos = st.tape.pos + before;
+  st.t_rnd = st.submit(st.rnd_job);
+}
+
+// rerandomize (:1619-1627, hyrax_pc.rs:321-344): core (shared, precommitted), then every step's precommitted commitment. The new blinds are
+// drawn in the reference's order; the row updates are independent, so all of them go through ONE sp_hyrax_rerandomize call.
+static void nn_prove_rerandomize(NNProveState& st) {
+  NNZkPrep& ps = st.ps;
+  std::vector<std::pair<std::vector<aff_t>*, std::vector<fe_t>*>> parts;
+  parts.push_back({&ps.comm_shared, &ps.r_shared});
+  parts.push_back({&ps.core.comm_pre, &ps.core.r_pre});
+  for (auto& s : ps.steps) parts.push_back({&s.comm_pre, &s.r_pre});
+  std::vector<aff_t> all_c;
+  std::vector<fe_t> all_old, all_new;
+  for (auto& pr_ : parts)
+    for (size_t i = 0; i < pr_.first->size(); ++i) {
+      all_c.push_back((*pr_.first)[i]);
+      all_old.push_back((*pr_.second)[i]);
+      all_new.push_back(st.tape.next());
     }
-  }
-  // instances and witnesses (:1662-1719): rest rows = commit_zeros (h * blind) — one sp_fixed_base_mul_h call for the rest rows of all instances — or, for a
-  // circuit with rest variables, the commitment of its rest segment under the same blinds (bellpepper/r1cs.rs:463-500); no challenges for these circuits
-  ProofBuf proof;
-  proof.pc(ps.comm_shared);
-  std::vector<aff_t> comms(n * rows);
-  std::vector<fe_t> X(n * dpub), r_W(n * rows);
-  std::vector<const sp_table*> Ws(n);
-  std::vector<fe_t> all_rest(n * rows_rest + rows_rest_c);
-  for (auto& b : all_rest) b = tape.next();  // steps in order, then the core: the reference's call order
-  std::vector<aff_t> all_c_rest(all_rest.size());
-  if (!all_rest.empty() && !(d.num_rest_unpadded && pk.dims_core.num_rest_unpadded))
+  if (all_c.empty()) return;
+  std::vector<aff_t> out(all_c.size());
+  ck(sp_hyrax_rerandomize(st.ctx, st.pk.ck, u64p(&all_c[0].x), all_c.size(), u64p(all_old.data()), u64p(all_new.data()), u64p(&out[0].x)), "rerandomize_commitment");
+  size_t o = 0;
+  for (auto& pr_ : parts)
+    for (size_t i = 0; i < pr_.first->size(); ++i, ++o) {
+      (*pr_.first)[i] = out[o];
+      (*pr_.second)[i] = all_new[o];
+    }
+}
+
+// instances and witnesses (:1662-1719), the rest rows: commit_zeros (h * blind) — one sp_fixed_base_mul_h call for the rest rows of all instances — or, for a
+// circuit with rest variables, the commitment of its rest segment under the same blinds (bellpepper/r1cs.rs:463-500); no challenges for these circuits
+static void nn_prove_rest_commitments(NNProveState& st) {
+  sp_ctx* ctx = st.ctx;
+  const NNZkKey& pk = st.pk;
+  NNZkPrep& ps = st.ps;
+  const sp_dims &d = st.d, &dc = st.dc;
+  const size_t n = st.n, rows_rest = st.rows_rest, rows_rest_c = st.rows_rest_c;
+  std::vector<fe_t>& all_rest = st.all_rest;
+  std::vector<aff_t>& all_c_rest = st.all_c_rest;
+  all_rest.resize(n * rows_rest + rows_rest_c);
+  for (auto& b : all_rest) b = st.tape.next();  // steps in order, then the core: the reference's call order
+  all_c_rest.resize(all_rest.size());
+  if (!all_rest.empty() && !(d.num_rest_unpadded && dc.num_rest_unpadded))
     ck(sp_fixed_base_mul_h(ctx, pk.ck, u64p(all_rest.data()), all_rest.size(), u64p(&all_c_rest[0].x)), "commit_zeros");
-  {
-    // the rest segments of several instances side by side in one table are ONE row-wise commitment (a Hyrax commitment is one MSM per 2048-entry row): a call
-    // per instance costs 0.25 ms of fixed work each (64 instances of the reference's two-block test circuit: 15.9 ms of a 23 ms prove)
-    struct RestJob {
-      const NNPre* p;
-      size_t off, len, blind_at, nrows;  // the segment inside p->W, its blinds / rows inside all_rest / all_c_rest
-    };
-    std::vector<RestJob> todo;
-    if (d.num_rest_unpadded)
-      for (size_t i = 0; i < n; ++i) todo.push_back({&ps.steps[i], d.num_shared + d.num_precommitted, d.num_rest, i * rows_rest, rows_rest});
-    if (dc.num_rest_unpadded) todo.push_back({&ps.core, dc.num_shared + dc.num_precommitted, dc.num_rest, n * rows_rest, rows_rest_c});
-    const size_t cap = (size_t)1 << 25;  // <= 1 GiB of staged elements per call
-    for (size_t at = 0; at < todo.size();) {
-      size_t cnt = 1, elems = todo[at].len;
-      while (at + cnt < todo.size() && elems + todo[at + cnt].len <= cap) elems += todo[at + cnt++].len;
-      if (cnt == 1) {
-        const RestJob& j = todo[at];
-        ck(sp_hyrax_commit(ctx, pk.ck, j.p->W, j.off, j.len, u64p(all_rest.data() + j.blind_at), ps.is_small ? 1 : 0, u64p(&all_c_rest[j.blind_at].x)), "commit rest");
-        at += 1;
-        continue;
-      }
-      if (elems > ps.rest_stage_cap) {
-        sp_table_free(ps.rest_stage);
-        ps.rest_stage = nullptr;
-        ps.rest_stage_cap = elems;
-        ck(sp_table_zeros(ctx, ps.rest_stage_cap, (size_t)-1, (size_t)-1, &ps.rest_stage), "rest staging table");
-      }
-      ck(sp_table_set_len(ps.rest_stage, elems, (size_t)-1, (size_t)-1), "rest staging len");
-      std::vector<fe_t> bl;
-      size_t pos = 0;
-      for (size_t k = 0; k < cnt; ++k) {
-        const RestJob& j = todo[at + k];
-        ck(sp_table_copy(ctx, ps.rest_stage, pos, j.p->W, j.off, j.len), "stage rest segment");
-        pos += j.len;
-        bl.insert(bl.end(), all_rest.begin() + j.blind_at, all_rest.begin() + j.blind_at + j.nrows);
-      }
-      std::vector<aff_t> out(bl.size());
-      ck(sp_hyrax_commit(ctx, pk.ck, ps.rest_stage, 0, elems, u64p(bl.data()), ps.is_small ? 1 : 0, u64p(&out[0].x)), "commit rest (batched)");
-      size_t o = 0;
-      for (size_t k = 0; k < cnt; ++k) {
-        const RestJob& j = todo[at + k];
-        std::copy(out.begin() + o, out.begin() + o + j.nrows, all_c_rest.begin() + j.blind_at);
-        o += j.nrows;
-      }
-      at += cnt;
+  // the rest segments of several instances side by side in one table are ONE row-wise commitment (a Hyrax commitment is one MSM per 2048-entry row): a call
+  // per instance costs 0.25 ms of fixed work each (64 instances of the reference's two-block test circuit: 15.9 ms of a 23 ms prove)
+  struct RestJob {
+    const NNPre* p;
+    size_t off, len, blind_at, nrows;  // the segment inside p->W, its blinds / rows inside all_rest / all_c_rest
+  };
+  std::vector<RestJob> todo;
+  if (d.num_rest_unpadded)
+    for (size_t i = 0; i < n; ++i) todo.push_back({&ps.steps[i], d.num_shared + d.num_precommitted, d.num_rest, i * rows_rest, rows_rest});
+  if (dc.num_rest_unpadded) todo.push_back({&ps.core, dc.num_shared + dc.num_precommitted, dc.num_rest, n * rows_rest, rows_rest_c});
+  const size_t cap = (size_t)1 << 25;  // <= 1 GiB of staged elements per call
+  for (size_t at = 0; at < todo.size();) {
+    size_t cnt = 1, elems = todo[at].len;
+    while (at + cnt < todo.size() && elems + todo[at + cnt].len <= cap) elems += todo[at + cnt++].len;
+    if (cnt == 1) {
+      const RestJob& j = todo[at];
+      ck(sp_hyrax_commit(ctx, pk.ck, j.p->W, j.off, j.len, u64p(all_rest.data() + j.blind_at), ps.is_small ? 1 : 0, u64p(&all_c_rest[j.blind_at].x)), "commit rest");
+      at += 1;
+      continue;
     }
+    sp_table* staged = grown_slot(ctx, ps.rest_stage, ps.rest_stage_cap, elems, false, "rest staging table", "rest staging len");
+    std::vector<fe_t> bl;
+    size_t pos = 0;
+    for (size_t k = 0; k < cnt; ++k) {
+      const RestJob& j = todo[at + k];
+      ck(sp_table_copy(ctx, staged, pos, j.p->W, j.off, j.len), "stage rest segment");
+      pos += j.len;
+      bl.insert(bl.end(), all_rest.begin() + j.blind_at, all_rest.begin() + j.blind_at + j.nrows);
+    }
+    std::vector<aff_t> out(bl.size());
+    ck(sp_hyrax_commit(ctx, pk.ck, staged, 0, elems, u64p(bl.data()), ps.is_small ? 1 : 0, u64p(&out[0].x)), "commit rest (batched)");
+    size_t o = 0;
+    for (size_t k = 0; k < cnt; ++k) {
+      const RestJob& j = todo[at + k];
+      std::copy(out.begin() + o, out.begin() + o + j.nrows, all_c_rest.begin() + j.blind_at);
+      o += j.nrows;
+    }
+    at += cnt;
   }
+}
+
+// instances and witnesses (:1662-1719), each instance: comm_W = shared | precommitted | rest rows with their blinds, and its fields of the proof
+static void nn_prove_instances(NNProveState& st) {
+  NNZkPrep& ps = st.ps;
+  const size_t n = st.n, rows = st.rows, rows_sh = st.rows_sh;
+  st.proof.pc(ps.comm_shared);
+  st.comms.resize(n * rows);
+  st.X.resize(n * st.dpub);
+  st.r_W.resize(n * rows);
+  st.Ws.resize(n);
   auto instance = [&](NNPre& p, size_t which, aff_t* comm_out, fe_t* r_out) {
-    const size_t my_pre = which == n ? rows_pre_c : rows_pre, my_rest = which == n ? rows_rest_c : rows_rest;
-    const fe_t* r_rest = all_rest.data() + which * rows_rest;  // (the core's blinds follow the n steps')
-    const aff_t* c_rest = all_c_rest.data() + which * rows_rest;
+    const size_t my_pre = which == n ? st.rows_pre_c : st.rows_pre, my_rest = which == n ? st.rows_rest_c : st.rows_rest;
+    const fe_t* r_rest = st.all_rest.data() + which * st.rows_rest;  // (the core's blinds follow the n steps')
+    const aff_t* c_rest = st.all_c_rest.data() + which * st.rows_rest;
     if (p.comm_pre.size() != my_pre) throw Error(SP_ERR_INTERNAL, "NeutronNova: precommitted rows of an instance");
     std::copy(ps.comm_shared.begin(), ps.comm_shared.end(), comm_out);
     std::copy(p.comm_pre.begin(), p.comm_pre.end(), comm_out + rows_sh);
@@ -607,351 +899,253 @@ static ProofBuf nn_prove(const NNZkKey& pk, NNZkPrep& ps, Tape& tape, double* ph
     std::copy(ps.r_shared.begin(), ps.r_shared.end(), r_out);
     std::copy(p.r_pre.begin(), p.r_pre.end(), r_out + rows_sh);
     std::copy(r_rest, r_rest + my_rest, r_out + rows_sh + my_pre);
-    proof.pc(p.comm_pre);
-    for (size_t i = 0; i < my_rest; ++i) proof.pp(c_rest[i]);
-    for (const fe_t& f : p.publics) proof.pf(f);
+    st.proof.pc(p.comm_pre);
+    for (size_t i = 0; i < my_rest; ++i) st.proof.pp(c_rest[i]);
+    for (const fe_t& f : p.publics) st.proof.pf(f);
   };
   for (size_t i = 0; i < n; ++i) {
-    instance(ps.steps[i], i, &comms[i * rows], &r_W[i * rows]);
-    std::copy(ps.steps[i].publics.begin(), ps.steps[i].publics.end(), X.begin() + i * dpub);
-    Ws[i] = ps.steps[i].W;
+    instance(ps.steps[i], i, &st.comms[i * rows], &st.r_W[i * rows]);
+    std::copy(ps.steps[i].publics.begin(), ps.steps[i].publics.end(), st.X.begin() + i * st.dpub);
+    st.Ws[i] = ps.steps[i].W;
   }
-  std::vector<aff_t> core_comm(rows);
-  std::vector<fe_t> core_rW(rows);
-  instance(ps.core, n, core_comm.data(), core_rW.data());
-  // the opening folds comm = folded + c_eval * core rows and comm_eval = eW_step + c_eval * eW_core with a weight drawn at the very end: the doubling
-  // ladders of the core rows (now) and of the core evaluation's commitment (behind its round) are built on the library's polling threads meanwhile
-  struct Fold2Guard {
-    sp_fold2_job *rows = nullptr, *eval = nullptr;
-    ~Fold2Guard() {
-      sp_fold_commitments2_drop(rows);
-      sp_fold_commitments2_drop(eval);
-    }
-  } fold2;
-  if (side) ck(sp_fold_commitments2_begin(ctx, u64p(&core_comm[0].x), rows, &fold2.rows), "fold_commitments (ladders)");
-  const double t_inst = now();
+  st.core_comm.resize(rows);
+  st.core_rW.resize(rows);
+  instance(ps.core, n, st.core_comm.data(), st.core_rW.data());
+  if (st.side) ck(sp_fold_commitments2_begin(st.ctx, u64p(&st.core_comm[0].x), rows, &st.fold2.rows), "fold_commitments (ladders)");
+  st.t_inst = st.now();
+}
 
-  Tr tr(ctx, "neutronnova_prove");
-  tr.absorb("vk", pk.vk_digest, 32);
-  absorb_instance(tr, "core_instance", core_comm, ps.core.publics);
-  vcirc::Circuit vc(pk.nb, pk.nx, pk.ny, 32);
-  vcirc::State vst(pk.vc);
-  struct HookCtx {
-    const NNZkKey* pk;
-    vcirc::Circuit* vc;
-    vcirc::State* st;
-    Tr* tr;
-    Tape* tape;
-    size_t outer_start, inner_start;
-    std::exception_ptr err;
-  } hc{&pk, &vc, &vst, &tr, &tape, pk.nb + 1, pk.nb + 1 + pk.nx + 1, nullptr};
-  // NIFS (:1770-1783): finish_round! = vc.nifs_polys[t] <- coefficients, then process_round (:703-735); once more after the rounds (:1207-1210)
-  auto nifs_hook = [](void* u, size_t t, const uint64_t* co, uint64_t* r_b) {
-    HookCtx* h = (HookCtx*)u;
-    if (h->err) return;
-    try {
-      if (t < h->pk->nb) {
-        for (int q = 0; q < 4; ++q) memcpy(&h->vc->nifs_polys[t][q], co + 4 * q, 32);
-        const fe_t r = vcirc::process_round(h->pk->ctx, *h->st, h->pk->vc, h->pk->vc_ck, *h->vc, t, *h->tr, *h->tape)[0];
-        memcpy(r_b, &r, 32);
-      } else {
-        memcpy(&h->vc->t_out_step, co, 32);
-        memcpy(&h->vc->eq_rho_at_rb, co + 4, 32);
-        vcirc::process_round(h->pk->ctx, *h->st, h->pk->vc, h->pk->vc_ck, *h->vc, t, *h->tr, *h->tape);
-      }
-    } catch (...) {
-      h->err = std::current_exception();
-    }
-  };
-  size_t ell, left, right;
-  compute_tensor_decomp(N, &ell, &left, &right);
-  const size_t nb = pk.nb;
-  std::vector<uint64_t> polys(16 * std::max<size_t>(nb, 1)), r_bs(4 * std::max<size_t>(nb, 1)), E_eq(4 * (left + right)), tail(8), f_rW(4 * rows), f_X(4 * std::max<size_t>(dpub, 1));
-  std::vector<aff_t> f_comm(rows);
-  SideGuard side_guard_rows{ps};  // f_comm and core_comm are read and written by the helper's jobs: drained before they go out of scope
-  sp_table *A = work_table(ctx, ps, 0, N), *B = work_table(ctx, ps, 1, N), *C = work_table(ctx, ps, 2, N), *fW = work_table(ctx, ps, 3, nv);
-  sp_table *core_abc[3] = {work_table(ctx, ps, 4, N), work_table(ctx, ps, 5, N), work_table(ctx, ps, 6, N)}, *zc = work_table(ctx, ps, 7, nv + 1 + dpub);
-  sp_table *pl = work_table(ctx, ps, 8, left), *pr = work_table(ctx, ps, 9, right), *rx = work_table(ctx, ps, 10, N);
-  sp_table *abc_s = work_table(ctx, ps, 11, 2 * nv), *abc_c = work_table(ctx, ps, 12, 2 * nv), *zs = work_table(ctx, ps, 13, 2 * nv), *zcc = work_table(ctx, ps, 14, 2 * nv);
-  sp_table* Wf = work_table(ctx, ps, 15, nv);
-  NifsOutputs no{polys.data(), r_bs.data(), E_eq.data(), tail.data(), f_rW.data(), f_X.data(), (uint64_t*)f_comm.data(), A, B, C, fW};
-  std::function<void(sp_ctx*)> fold_job;
-  if (side) no.deferred_fold_commitments = &fold_job;
-  nifs_prove(ctx, pk.S_step, d, pk.ck, n, rows, comms.data(), X.data(), Ws.data(), r_W.data(), true, ps.nifs_cached, tr.t, nifs_hook, &hc, no);
-  if (hc.err) std::rethrow_exception(hc.err);
-  if (fold_job) {
-    t_fold = ps.wk.submit([&ps, job = std::move(fold_job)] {
-      ck(sp_ctx_bind_thread(ps.ctx2), "device");
-      job(ps.ctx2);
-    });
-    // delta (ipa.rs:139-147): the mask and its blinds follow the random instance and NovaNIFS's r_T on the tape
-    Tape ahead = tape;
-    {
-      const vcirc::Shape& vs = pk.vc;
-      ahead.pos = tape.pos + (pk.vc.total_vars / 32 - vst.commits) + (vs.total_vars + vs.num_io() + 1) + vs.total_vars / 32 + 2 * (vs.num_cons / 32);
-    }
-    ps.wk.submit([&pk, &ps, ahead]() mutable {
-      NNZkPrep::OpeningAhead& O = ps.open;
-      try {
-        O.tape_from = ahead.pos;
-        O.dv.resize(DEFAULT_COMMITMENT_WIDTH);
-        for (auto& x : O.dv) x = ahead.next();
-        O.r_delta = ahead.next();
-        O.r_beta = ahead.next();
-        O.tape_count = ahead.pos - O.tape_from;
-        ck(sp_msm_ck(ps.ctx2, pk.ck, u64p(O.dv.data()), O.dv.size(), u64p(&O.r_delta), u64p(&O.delta.x)), "delta");
-        O.delta_valid = true;
-      } catch (...) {
-        O.delta_valid = false;
-      }
-    });
+// NeutronNovaNIFS::prove (:1770-1783) with process_round as its round hook; behind it the helper gets the fold of the step commitments and delta
+static void nn_prove_nifs(NNProveState& st) {
+  sp_ctx* ctx = st.ctx;
+  const NNZkKey& pk = st.pk;
+  NNZkPrep& ps = st.ps;
+  const size_t N = st.N, nv = st.nv, nb = pk.nb, rows = st.rows, dpub = st.dpub;
+  st.tr.reset(new Tr(ctx, "neutronnova_prove"));
+  absorb_head(*st.tr, pk, st.core_comm, ps.core.publics);
+  st.vc.reset(new vcirc::Circuit(pk.nb, pk.nx, pk.ny, 32));
+  st.vst.reset(new vcirc::State(pk.vc));
+  st.hc = NNHookCtx{&pk, st.vc.get(), st.vst.get(), st.tr.get(), &st.tape, pk.nb + 1, pk.nb + 1 + pk.nx + 1, nullptr};
+  size_t ell;
+  compute_tensor_decomp(N, &ell, &st.left, &st.right);
+  st.polys.resize(16 * std::max<size_t>(nb, 1));
+  st.r_bs.resize(4 * std::max<size_t>(nb, 1));
+  st.E_eq.resize(4 * (st.left + st.right));
+  st.tail.resize(8);
+  st.f_rW.resize(4 * rows);
+  st.f_X.resize(4 * std::max<size_t>(dpub, 1));
+  st.f_comm.resize(rows);
+  st.A = work_table(ctx, ps, 0, N), st.B = work_table(ctx, ps, 1, N), st.C = work_table(ctx, ps, 2, N), st.fW = work_table(ctx, ps, 3, nv);
+  for (int m = 0; m < 3; ++m) st.core_abc[m] = work_table(ctx, ps, 4 + m, N);
+  st.zc = work_table(ctx, ps, 7, nv + 1 + dpub);
+  st.pl = work_table(ctx, ps, 8, st.left), st.pr = work_table(ctx, ps, 9, st.right), st.rx = work_table(ctx, ps, 10, N);
+  st.abc_s = work_table(ctx, ps, 11, 2 * nv), st.abc_c = work_table(ctx, ps, 12, 2 * nv), st.zs = work_table(ctx, ps, 13, 2 * nv), st.zcc = work_table(ctx, ps, 14, 2 * nv);
+  st.Wf = work_table(ctx, ps, 15, nv);
+  NifsOutputs no{st.polys.data(), st.r_bs.data(), st.E_eq.data(), st.tail.data(), st.f_rW.data(), st.f_X.data(), (uint64_t*)st.f_comm.data(), st.A, st.B, st.C, st.fW};
+  st.fold_job.ps = &ps;
+  if (st.side) no.deferred_fold_commitments = &st.fold_job.job;
+  nifs_prove(ctx, pk.S_step, st.d, pk.ck, st.n, rows, st.comms.data(), st.X.data(), st.Ws.data(), st.r_W.data(), true, ps.nifs_cached, st.tr->t, nn_nifs_hook, &st.hc, no);
+  if (st.hc.err) std::rethrow_exception(st.hc.err);
+  if (st.fold_job.job) {
+    st.t_fold = st.submit(st.fold_job);
+    const vcirc::Shape& vs = pk.vc;
+    st.delta_job.pk = &pk;
+    st.delta_job.ps = &ps;
+    st.delta_job.ahead = st.tape;
+    st.delta_job.ahead.pos = st.tape.pos + (pk.vc.total_vars / 32 - st.vst->commits) + (vs.total_vars + vs.num_io() + 1) + vs.total_vars / 32 + 2 * (vs.num_cons / 32);
+    st.submit(st.delta_job);
   }
-  const double t_nifs = now();
+  st.t_nifs = st.now();
+}
 
-  // core products, batched outer sum-check (:1786-1850)
-  const fe_t one = fe_one<S>();
+// z = [W | 1 | X] of a circuit into a working table
+static void nn_fill_z(NNProveState& st, sp_table* z, const sp_table* W, const std::vector<fe_t>& Xv) {
+  ck(sp_table_copy(st.ctx, z, 0, W, 0, st.nv), "z <- W");
+  std::vector<fe_t> tl(1 + Xv.size());
+  tl[0] = fe_one<S>();
+  std::copy(Xv.begin(), Xv.end(), tl.begin() + 1);
+  ck(sp_table_write(st.ctx, z, st.nv, u64p(tl.data()), tl.size()), "z tail");
+}
+
+// core products, batched outer sum-check (:1786-1850)
+static void nn_prove_outer(NNProveState& st) {
+  sp_ctx* ctx = st.ctx;
+  const NNZkKey& pk = st.pk;
+  vcirc::Circuit& vc = *st.vc;
+  sp_table** core_abc = st.core_abc;
+  nn_fill_z(st, st.zc, st.ps.core.W, st.ps.core.publics);
+  ck(sp_multiply_vec(ctx, pk.S_core, st.zc, core_abc[0], core_abc[1], core_abc[2]), "multiply_vec (core)");
+  ck(sp_table_write(ctx, st.pl, 0, st.E_eq.data(), st.left), "pow left");
+  ck(sp_table_write(ctx, st.pr, 0, st.E_eq.data() + 4 * st.left, st.right), "pow right");
+  st.r_x.resize(pk.nx);
   {
-    ck(sp_table_copy(ctx, zc, 0, ps.core.W, 0, nv), "z <- W");
-    std::vector<fe_t> tl(1 + dpub);
-    tl[0] = one;
-    std::copy(ps.core.publics.begin(), ps.core.publics.end(), tl.begin() + 1);
-    ck(sp_table_write(ctx, zc, nv, u64p(tl.data()), tl.size()), "z tail");
-    ck(sp_multiply_vec(ctx, pk.S_core, zc, core_abc[0], core_abc[1], core_abc[2]), "multiply_vec (core)");
-  }
-  ck(sp_table_write(ctx, pl, 0, E_eq.data(), left), "pow left");
-  ck(sp_table_write(ctx, pr, 0, E_eq.data() + 4 * left, right), "pow right");
-  auto batched_hook = [](void* u, size_t round, const uint64_t* cs_, const uint64_t* cc_, size_t ncoeffs, uint64_t r_out[4]) -> int {
-    HookCtx* h = (HookCtx*)u;
-    try {
-      if (ncoeffs == 4) {
-        const size_t i = round - h->outer_start;
-        for (int q = 0; q < 4; ++q) {
-          memcpy(&h->vc->outer_step[i][q], cs_ + 4 * q, 32);
-          memcpy(&h->vc->outer_core[i][q], cc_ + 4 * q, 32);
-        }
-      } else {
-        const size_t j = round - h->inner_start;
-        for (int q = 0; q < 3; ++q) {
-          memcpy(&h->vc->inner_step[j][q], cs_ + 4 * q, 32);
-          memcpy(&h->vc->inner_core[j][q], cc_ + 4 * q, 32);
-        }
-      }
-      const fe_t r = vcirc::process_round(h->pk->ctx, *h->st, h->pk->vc, h->pk->vc_ck, *h->vc, round, *h->tr, *h->tape)[0];
-      memcpy(r_out, &r, 32);
-      return 0;
-    } catch (...) {
-      h->err = std::current_exception();
-      return SP_ERR_INTERNAL;
-    }
-  };
-  std::vector<fe_t> r_x(pk.nx);
-  {
-    int rc = sp_sumcheck_cubic_outer_pow_batched(ctx, pk.nx, pl, pr, A, B, C, core_abc[0], core_abc[1], core_abc[2], tail.data(), hc.outer_start, batched_hook, &hc, u64p(r_x.data()));
-    if (hc.err) std::rethrow_exception(hc.err);
+    int rc = sp_sumcheck_cubic_outer_pow_batched(ctx, pk.nx, st.pl, st.pr, st.A, st.B, st.C, core_abc[0], core_abc[1], core_abc[2], st.tail.data(), st.hc.outer_start,
+                                                 nn_batched_hook, &st.hc, u64p(st.r_x.data()));
+    if (st.hc.err) std::rethrow_exception(st.hc.err);
     ck(rc, "outer sum-check (batched)");
   }
   {
-    sp_table* cl[6] = {A, B, C, core_abc[0], core_abc[1], core_abc[2]};
+    sp_table* cl[6] = {st.A, st.B, st.C, core_abc[0], core_abc[1], core_abc[2]};
     fe_t v[6];
     for (int q = 0; q < 6; ++q) ck(sp_table_read(ctx, cl[q], 0, 1, u64p(&v[q])), "claims");
     for (int q = 0; q < 3; ++q) {
       vc.claim_step[q] = v[q];
       vc.claim_core[q] = v[3 + q];
     }
-    ck(sp_table_read(ctx, pl, 0, 1, u64p(&vc.tau_at_rx)), "tau_at_rx");
+    ck(sp_table_read(ctx, st.pl, 0, 1, u64p(&vc.tau_at_rx)), "tau_at_rx");
   }
-  const fe_t r = vcirc::process_round(ctx, vst, pk.vc, pk.vc_ck, vc, hc.outer_start + pk.nx, tr, tape)[0];
-  const double t_outer = now();
-  const fe_t r2 = fe_mul<S>(r, r);
-  fe_t claims[2] = {fe_add<S>(fe_add<S>(vc.claim_step[0], fe_mul<S>(r, vc.claim_step[1])), fe_mul<S>(r2, vc.claim_step[2])),
-                    fe_add<S>(fe_add<S>(vc.claim_core[0], fe_mul<S>(r, vc.claim_core[1])), fe_mul<S>(r2, vc.claim_core[2]))};
-  // evals_rx, both poly_ABC, the z tables, batched inner sum-check (:1852-1945)
-  ck(sp_eq_table_into(ctx, u64p(r_x.data()), pk.nx, rx), "evals_rx");
-  ck(sp_poly_abc(ctx, pk.S_step, rx, u64p(&r), 2 * nv, abc_s), "poly_ABC (step)");
-  ck(sp_poly_abc(ctx, pk.S_core, rx, u64p(&r), 2 * nv, abc_c), "poly_ABC (core)");
-  std::vector<fe_t> folded_X(dpub);
-  memcpy(folded_X.data(), f_X.data(), dpub * sizeof(fe_t));
+  st.r = vcirc::process_round(ctx, *st.vst, pk.vc, pk.vc_ck, vc, st.hc.outer_start + pk.nx, *st.tr, st.tape)[0];
+  st.t_outer = st.now();
+}
+
+// evals_rx, both poly_ABC, the z tables, batched inner sum-check (:1852-1945)
+static void nn_prove_inner(NNProveState& st) {
+  sp_ctx* ctx = st.ctx;
+  const NNZkKey& pk = st.pk;
+  NNZkPrep& ps = st.ps;
+  vcirc::Circuit& vc = *st.vc;
+  const size_t nv = st.nv, dpub = st.dpub, nvr = st.nvr;
+  const fe_t r = st.r, r2 = fe_mul<S>(r, r);
+  st.claims[0] = joint_inner_claim(vc.claim_step, r, r2);
+  st.claims[1] = joint_inner_claim(vc.claim_core, r, r2);
+  ck(sp_eq_table_into(ctx, u64p(st.r_x.data()), pk.nx, st.rx), "evals_rx");
+  ck(sp_poly_abc(ctx, pk.S_step, st.rx, u64p(&r), 2 * nv, st.abc_s), "poly_ABC (step)");
+  ck(sp_poly_abc(ctx, pk.S_core, st.rx, u64p(&r), 2 * nv, st.abc_c), "poly_ABC (core)");
+  st.folded_X.resize(dpub);
+  memcpy(st.folded_X.data(), st.f_X.data(), dpub * sizeof(fe_t));
   auto fill_z = [&](sp_table* z, const sp_table* W, const std::vector<fe_t>& Xv) {
-    ck(sp_table_copy(ctx, z, 0, W, 0, nv), "z <- W");
-    std::vector<fe_t> tl(1 + Xv.size());
-    tl[0] = one;
-    std::copy(Xv.begin(), Xv.end(), tl.begin() + 1);
-    ck(sp_table_write(ctx, z, nv, u64p(tl.data()), tl.size()), "z tail");
-    ck(sp_table_zero(ctx, z, nv + tl.size(), nv - tl.size()), "z: zero high half");  // a working table: the last prove's rounds were bound in place
+    nn_fill_z(st, z, W, Xv);
+    ck(sp_table_zero(ctx, z, nv + 1 + Xv.size(), nv - 1 - Xv.size()), "z: zero high half");  // a working table: the last prove's rounds were bound in place
   };
-  fill_z(zs, fW, folded_X);
-  fill_z(zcc, ps.core.W, ps.core.publics);
-  for (sp_table* t : {abc_s, abc_c, zs, zcc}) ck(sp_table_set_len(t, 2 * nv, nv, 1 + dpub), "halves");
-  std::vector<fe_t> r_y(pk.ny);
-  fe_t fin[4];
+  fill_z(st.zs, st.fW, st.folded_X);
+  fill_z(st.zcc, ps.core.W, ps.core.publics);
+  for (sp_table* t : {st.abc_s, st.abc_c, st.zs, st.zcc}) ck(sp_table_set_len(t, 2 * nv, nv, 1 + dpub), "halves");
+  st.r_y.resize(pk.ny);
+  const std::vector<fe_t>& r_y = st.r_y;
   {
-    int rc = sp_sumcheck_quad_batched(ctx, u64p(claims), pk.ny, abc_s, abc_c, zs, zcc, hc.inner_start, batched_hook, &hc, u64p(r_y.data()), u64p(fin));
-    if (hc.err) std::rethrow_exception(hc.err);
+    int rc = sp_sumcheck_quad_batched(ctx, u64p(st.claims), pk.ny, st.abc_s, st.abc_c, st.zs, st.zcc, st.hc.inner_start, nn_batched_hook, &st.hc, u64p(st.r_y.data()), u64p(st.fin));
+    if (st.hc.err) std::rethrow_exception(st.hc.err);
     ck(rc, "inner sum-check (batched)");
   }
-  if (t_fold) {  // r_y is known: the halves of comm_LZ and beta, under the verifier-circuit phase
-    const size_t nvr = log2_ceil(rows);
-    t_open = ps.wk.submit([&pk, &ps, &f_comm, &core_comm, rows, L = eq_evals_host(r_y.data() + 1, nvr), Rv = eq_evals_host(r_y.data() + 1 + nvr, pk.ny - 1 - nvr)] {
-      NNZkPrep::OpeningAhead& O = ps.open;
-      try {
-        if (!O.delta_valid || Rv.size() != O.dv.size() || L.size() > rows) return;
-        ck(sp_ctx_bind_thread(ps.ctx2), "device");
-        ck(sp_msm(ps.ctx2, u64p(L.data()), u64p(&f_comm[0].x), L.size(), u64p(&O.P_f.x)), "<L, folded rows>");
-        ck(sp_msm(ps.ctx2, u64p(L.data()), u64p(&core_comm[0].x), L.size(), u64p(&O.P_c.x)), "<L, core rows>");
-        fe_t ip = fe_zero();
-        for (size_t i = 0; i < Rv.size(); ++i) ip = fe_add<S>(ip, fe_mul<S>(Rv[i], O.dv[i]));
-        ck(sp_hyrax_commit_small(ps.ctx2, pk.vc_ck, u64p(&ip), 1, u64p(&O.r_beta), u64p(&O.beta.x)), "beta");
-        sp_fold_commitments2_drop(O.lz_fold);
-        O.lz_fold = nullptr;
-        if (sp_fold_commitments2_begin(ps.ctx2, u64p(&O.P_c.x), 1, &O.lz_fold) != SP_OK) O.lz_fold = nullptr;
-        O.points_valid = true;
-
-      } catch (...) {
-        O.points_valid = false;
-      }
-    });
+  if (st.t_fold) {  // r_y is known: the halves of comm_LZ and beta, under the verifier-circuit phase
+    NNOpeningPointsJob& j = st.points_job;
+    j.pk = &pk, j.ps = &ps, j.f_comm = &st.f_comm, j.core_comm = &st.core_comm, j.rows = st.rows;
+    j.L = eq_evals_host(r_y.data() + 1, nvr);
+    j.Rv = eq_evals_host(r_y.data() + 1 + nvr, pk.ny - 1 - nvr);
+    st.t_open = st.submit(j);
   }
-  // The opening's W = folded_W + c_eval core_W exists only once c_eval is drawn, at the very end - but L^T W (bind_with_delayed, hyrax_pc.rs:38-54) is linear in
-  // the table: LZ = L^T folded_W + c_eval L^T core_W, and L = eq(r_y[1..]) is known now. The two products run as jobs of the library's vector stream under the
-  // verifier-circuit phase (one job at a time: the second is begun where the first is collected).
-  struct LzAhead {
-    sp_ctx* ctx;
-    sp_vec_job* job = nullptr;
-    size_t cols = 0;
-    std::vector<fe_t> f, c;
-    int have = 0;  // 1: f, 2: f and c
-    ~LzAhead() {
-      if (job) {
-        std::vector<fe_t> sink(cols);
-        (void)sp_rowmat_vec_eq_finish(ctx, job, u64p(sink.data()));
-      }
-    }
-  } lz{ctx};
-  if (side) {
-    const size_t nvr = log2_ceil(rows);
-    lz.cols = (size_t)1 << (pk.ny - 1 - nvr);
-    if (sp_rowmat_vec_eq_begin(ctx, fW, u64p(r_y.data() + 1), nvr, lz.cols, &lz.job) != SP_OK) lz.job = nullptr;
+  if (st.side) {  // L^T folded_W goes out (NNLzAhead)
+    st.lz.cols = (size_t)1 << (pk.ny - 1 - nvr);
+    st.lz.begin(ctx, st.fW, r_y.data(), nvr);
   }
-  auto lz_step = [&] {  // collect the product in flight, begin the next
-    if (!lz.job) return;
-    const size_t nvr = log2_ceil(rows);
-    std::vector<fe_t>& dst = lz.have == 0 ? lz.f : lz.c;
-    dst.resize(lz.cols);
-    sp_vec_job* j = lz.job;
-    lz.job = nullptr;
-    if (sp_rowmat_vec_eq_finish(ctx, j, u64p(dst.data())) != SP_OK) return;
-    if (++lz.have == 1 && sp_rowmat_vec_eq_begin(ctx, ps.core.W, u64p(r_y.data() + 1), nvr, lz.cols, &lz.job) != SP_OK) lz.job = nullptr;
-  };
-  auto eval_X = [&](const std::vector<fe_t>& Xv) {
-    std::vector<fe_t> v{one};
-    v.insert(v.end(), Xv.begin(), Xv.end());
-    return sparse_poly_evaluate(pk.ny - 1, v, r_y.data() + 1);
-  };
-  vc.eval_X_step = eval_X(folded_X);
-  vc.eval_X_core = eval_X(ps.core.publics);
-  const fe_t den = fe_sub<S>(one, r_y[0]);
-  if (fe_is_zero(den)) throw Error(SP_ERR_DIVISION_BY_ZERO, "DivisionByZero");
-  const fe_t inv = fe_inv_vartime<S>(den);
-  vc.eval_W_step = fe_mul<S>(fe_sub<S>(fin[2], fe_mul<S>(r_y[0], vc.eval_X_step)), inv);
-  vc.eval_W_core = fe_mul<S>(fe_sub<S>(fin[3], fe_mul<S>(r_y[0], vc.eval_X_core)), inv);
-  const size_t inner_final = hc.inner_start + pk.ny;
-  for (size_t k = 0; k < 3; ++k) vcirc::process_round(ctx, vst, pk.vc, pk.vc_ck, vc, inner_final + k, tr, tape);
-  if (side) ck(sp_fold_commitments2_begin(ctx, u64p(&vst.comm_per_round[inner_final + 2][0].x), 1, &fold2.eval), "fold eval commitments (ladder)");
-  const double t_inner = now();
+  vc.eval_X_step = nn_eval_X(pk.ny, st.folded_X.data(), st.folded_X.size(), r_y.data());
+  vc.eval_X_core = nn_eval_X(pk.ny, ps.core.publics.data(), ps.core.publics.size(), r_y.data());
+  const fe_t inv = inv_one_minus(r_y[0]);
+  vc.eval_W_step = eval_W_from(st.fin[2], r_y[0], vc.eval_X_step, inv);
+  vc.eval_W_core = eval_W_from(st.fin[3], r_y[0], vc.eval_X_core, inv);
+  st.inner_final = st.hc.inner_start + pk.ny;
+  for (size_t k = 0; k < 3; ++k) vcirc::process_round(ctx, *st.vst, pk.vc, pk.vc_ck, vc, st.inner_final + k, *st.tr, st.tape);
+  if (st.side) ck(sp_fold_commitments2_begin(ctx, u64p(&st.vst->comm_per_round[st.inner_final + 2][0].x), 1, &st.fold2.eval), "fold eval commitments (ladder)");
+  st.t_inner = st.now();
+}
 
-  // finalize_multiround_witness (:1948-1952): U_verifier, its regular form, W_verifier
-  const vcirc::Shape& vs = pk.vc;
-  std::vector<fe_t> vpub(vst.cs.inputs.begin() + 1 + vs.total_challenges, vst.cs.inputs.end());
-  std::vector<aff_t> Uv_comm;
-  std::vector<fe_t> Uv_X, Wv_r;
-  for (const auto& c : vst.comm_per_round) Uv_comm.insert(Uv_comm.end(), c.begin(), c.end());
-  for (const auto& c : vst.challenges) Uv_X.insert(Uv_X.end(), c.begin(), c.end());
-  Uv_X.insert(Uv_X.end(), vpub.begin(), vpub.end());
-  for (const auto& b : vst.blind_per_round) Wv_r.insert(Wv_r.end(), b.begin(), b.end());
-  lap("(up to the vc instance)");
-  if (laps) fprintf(stderr, "nn_prove: process_round totals: synthesis %.3f ms, commitments %.3f ms, transcript %.3f ms over %zu rounds\n", vst.synth_ms, vst.commit_ms, vst.hash_ms, vst.current);
-  // sample_random_instance_witness (src/r1cs/mod.rs:474-531) on the verifier-circuit shape
-  const size_t vnv = vs.total_vars, vcons = vs.num_cons, vio = vs.num_io();
-  if (t_rnd) ps.wk.wait(t_rnd);
-  const bool ahead_ok = side && ps.rnd.valid && ps.rnd.tape_from == tape.pos;
-  std::vector<fe_t> Z, rnd_rW, rnd_rE, rnd_E, mv[3];
-  std::vector<aff_t> rnd_comm_W, rnd_comm_E;
+// finalize_multiround_witness (:1948-1952): U_verifier, its regular form, W_verifier
+static void nn_prove_vc_instance(NNProveState& st) {
+  const vcirc::Shape& vs = st.pk.vc;
+  const vcirc::State& vst = *st.vst;
+  st.vpub.assign(vst.cs.inputs.begin() + 1 + vs.total_challenges, vst.cs.inputs.end());
+  for (const auto& c : vst.comm_per_round) st.Uv_comm.insert(st.Uv_comm.end(), c.begin(), c.end());
+  for (const auto& c : vst.challenges) st.Uv_X.insert(st.Uv_X.end(), c.begin(), c.end());
+  st.Uv_X.insert(st.Uv_X.end(), st.vpub.begin(), st.vpub.end());
+  for (const auto& b : vst.blind_per_round) st.Wv_r.insert(st.Wv_r.end(), b.begin(), b.end());
+  st.laps.lap("(up to the vc instance)");
+  if (st.laps.on)
+    fprintf(stderr, "nn_prove: process_round totals: synthesis %.3f ms, commitments %.3f ms, transcript %.3f ms over %zu rounds\n", vst.synth_ms, vst.commit_ms, vst.hash_ms, vst.current);
+}
+
+// sample_random_instance_witness (src/r1cs/mod.rs:474-531) on the verifier-circuit shape: what the helper's job left, if it is this tape position's; else here
+static void nn_prove_random_instance(NNProveState& st) {
+  const NNZkKey& pk = st.pk;
+  NNZkPrep& ps = st.ps;
+  const size_t vnv = pk.vc.total_vars;
+  if (st.t_rnd) ps.wk.wait(st.t_rnd);
+  const bool ahead_ok = st.side && ps.rnd.valid && ps.rnd.tape_from == st.tape.pos;
   if (ahead_ok) {
-    Z.swap(ps.rnd.Z);
-    rnd_rW.swap(ps.rnd.rW);
-    rnd_rE.swap(ps.rnd.rE);
-    rnd_E.swap(ps.rnd.E);
-    rnd_comm_W.swap(ps.rnd.comm_W);
-    rnd_comm_E.swap(ps.rnd.comm_E);
-    tape.skip(ps.rnd.tape_count);
+    st.tape.skip(ps.rnd.tape_count);
+    std::swap(st.rnd, ps.rnd);
   } else {
-    if (laps && side) fprintf(stderr, "nn_prove: random instance computed inline (job valid %d, tape %zu vs %zu)\n", (int)ps.rnd.valid, ps.rnd.tape_from, tape.pos);
-    Z.resize(vnv + vio + 1);
-    for (auto& z : Z) z = tape.next();
-    rnd_rW.resize(vnv / 32);
-    rnd_rE.resize(vcons / 32);
-    for (auto& b : rnd_rW) b = tape.next();
-    for (auto& b : rnd_rE) b = tape.next();
-    vs.multiply_vec(Z, mv);
-    rnd_E.resize(vcons);
-    for (size_t i = 0; i < vcons; ++i) rnd_E[i] = fe_sub<S>(fe_mul<S>(mv[0][i], mv[1][i]), fe_mul<S>(Z[vnv], mv[2][i]));
-    rnd_comm_W = commit_rows32(ctx, ps, pk.vc_ck, std::vector<fe_t>(Z.begin(), Z.begin() + vnv), rnd_rW);
-    rnd_comm_E = commit_rows32(ctx, ps, pk.vc_ck, rnd_E, rnd_rE);
+    if (st.laps.on && st.side)
+      fprintf(stderr, "nn_prove: random instance computed inline (job valid %d, tape %zu vs %zu)\n", (int)ps.rnd.valid, ps.rnd.tape_from, st.tape.pos);
+    sample_random_instance(pk.vc, st.tape, st.rnd, [&](int, const std::vector<fe_t>& v, const std::vector<fe_t>& bl) { return commit_rows32(st.ctx, ps, pk.vc_ck, v, bl); });
   }
-  const fe_t rnd_u = Z[vnv];
-  const std::vector<fe_t> rnd_W(Z.begin(), Z.begin() + vnv), rnd_X(Z.begin() + vnv + 1, Z.end());
-  lap("random instance + 2 commits");
-  // NovaNIFS::prove (src/nifs.rs:34-61)
-  {
-    std::vector<uint8_t> b = commitment_bytes(rnd_comm_W.data(), rnd_comm_W.size()), e = commitment_bytes(rnd_comm_E.data(), rnd_comm_E.size());
-    b.insert(b.end(), e.begin(), e.end());
-    const size_t off = b.size();
-    b.resize(off + 32 * (1 + rnd_X.size()));
-    sp::fe_to_be_bytes<S>(rnd_u, b.data() + off);
-    for (size_t j = 0; j < rnd_X.size(); ++j) sp::fe_to_be_bytes<S>(rnd_X[j], b.data() + off + 32 * (1 + j));
-    tr.absorb("U1", b.data(), b.size());
-  }
-  absorb_instance(tr, "U2", Uv_comm, Uv_X);
-  std::vector<fe_t> r_T(vcons / 32);
-  for (auto& b : r_T) b = tape.next();
-  std::vector<fe_t> Zs(vnv + 1 + vio);
+  const std::vector<fe_t>& Z = st.rnd.Z;
+  st.rnd_u = Z[vnv];
+  st.rnd_W.assign(Z.begin(), Z.begin() + vnv);
+  st.rnd_X.assign(Z.begin() + vnv + 1, Z.end());
+  st.laps.lap("random instance + 2 commits");
+}
+
+// NovaNIFS::prove (src/nifs.rs:34-61) + commit_T (src/r1cs/folds.rs:28-88), then the fold of the two instances and witnesses with the challenge
+static void nn_prove_nova_nifs(NNProveState& st) {
+  const NNZkKey& pk = st.pk;
+  const vcirc::Shape& vs = pk.vc;
+  const vcirc::State& vst = *st.vst;
+  Tr& tr = *st.tr;
+  const size_t vnv = vs.total_vars, vcons = vs.num_cons, vio = vs.num_io();
+  const std::vector<fe_t>&rnd_W = st.rnd_W, &rnd_X = st.rnd_X, &rnd_E = st.rnd.E, &rnd_rW = st.rnd.rW, &rnd_rE = st.rnd.rE, &Uv_X = st.Uv_X;
+  std::vector<fe_t>&T = st.T, &r_T = st.r_T;
+  const fe_t rnd_u = st.rnd_u;
+  absorb_U1(tr, st.rnd.comm_W.data(), st.rnd.comm_W.size(), st.rnd.comm_E.data(), st.rnd.comm_E.size(), rnd_u, rnd_X.data(), rnd_X.size());
+  absorb_instance(tr, "U2", st.Uv_comm, Uv_X);
+  r_T.resize(vcons / 32);
+  for (auto& b : r_T) b = st.tape.next();
+  std::vector<fe_t> Zs(vnv + 1 + vio), mv[3];
   par_for(vnv, 256, [&](size_t lo, size_t hi) {
     for (size_t i = lo; i < hi; ++i) Zs[i] = fe_add<S>(rnd_W[i], vst.w[i]);
   });
-  const fe_t u1 = fe_add<S>(rnd_u, one);
+  const fe_t u1 = fe_add<S>(rnd_u, fe_one<S>());
   Zs[vnv] = u1;
   for (size_t i = 0; i < vio; ++i) Zs[vnv + 1 + i] = fe_add<S>(rnd_X[i], Uv_X[i]);
   vs.multiply_vec(Zs, mv);
-  std::vector<fe_t> T(vcons);
+  T.resize(vcons);
   par_for(vcons, 48, [&](size_t lo, size_t hi) {
     for (size_t i = lo; i < hi; ++i) T[i] = fe_sub<S>(fe_sub<S>(fe_mul<S>(mv[0][i], mv[1][i]), fe_mul<S>(u1, mv[2][i])), rnd_E[i]);
   });
-  lap("NovaNIFS: absorbs, Z, multiply_vec, T");
-  const std::vector<aff_t> comm_T = commit_rows32(ctx, ps, pk.vc_ck, T, r_T, side);
-  lap("NovaNIFS: commit_T");
-  {
-    const std::vector<uint8_t> b = commitment_bytes(comm_T.data(), comm_T.size());
-    tr.absorb("comm_T", b.data(), b.size());
-  }
-  lz_step();  // L^T folded_W is in; L^T core_W goes out
-  lap("NovaNIFS: T + commit_T");
+  st.laps.lap("NovaNIFS: absorbs, Z, multiply_vec, T");
+  st.comm_T = commit_rows32(st.ctx, st.ps, pk.vc_ck, T, r_T, st.side);
+  st.laps.lap("NovaNIFS: commit_T");
+  absorb_comm_T(tr, st.comm_T.data(), st.comm_T.size());
+  st.lz.step(st.ctx, st.ps.core.W, st.r_y.data(), st.nvr);  // L^T folded_W is in; L^T core_W goes out
+  st.laps.lap("NovaNIFS: T + commit_T");
   const fe_t rf = tr.squeeze("r");
-  std::vector<fe_t> Wfold(vnv), Efold(vcons), rWfold(rnd_rW.size()), rEfold(rnd_rE.size()), Xfold(vio);
+  std::vector<fe_t>&Wfold = st.Wfold, &Efold = st.Efold, &rWfold = st.rWfold, &rEfold = st.rEfold, &Xfold = st.Xfold;
+  Wfold.resize(vnv), Efold.resize(vcons), rWfold.resize(rnd_rW.size()), rEfold.resize(rnd_rE.size()), Xfold.resize(vio);
   par_for(vnv + vcons, 96, [&](size_t lo, size_t hi) {
     for (size_t i = lo; i < hi; ++i) {
       if (i < vnv) Wfold[i] = fe_add<S>(rnd_W[i], fe_mul<S>(rf, vst.w[i]));
       else Efold[i - vnv] = fe_add<S>(rnd_E[i - vnv], fe_mul<S>(rf, T[i - vnv]));
     }
   });
-  for (size_t i = 0; i < rWfold.size(); ++i) rWfold[i] = fe_add<S>(rnd_rW[i], fe_mul<S>(rf, Wv_r[i]));
+  for (size_t i = 0; i < rWfold.size(); ++i) rWfold[i] = fe_add<S>(rnd_rW[i], fe_mul<S>(rf, st.Wv_r[i]));
   for (size_t i = 0; i < rEfold.size(); ++i) rEfold[i] = fe_add<S>(rnd_rE[i], fe_mul<S>(rf, r_T[i]));
   for (size_t i = 0; i < vio; ++i) Xfold[i] = fe_add<S>(rnd_X[i], fe_mul<S>(rf, Uv_X[i]));
-  const fe_t ufold = fe_add<S>(rnd_u, rf);
-  // RelaxedR1CSSpartanProof::prove (src/spartan_relaxed.rs:98-213)
+  st.ufold = fe_add<S>(rnd_u, rf);
+}
+
+// RelaxedR1CSSpartanProof::prove (src/spartan_relaxed.rs:98-213) on the folded instance
+static void nn_prove_relaxed_spartan(NNProveState& st) {
+  sp_ctx* ctx = st.ctx;
+  NNZkPrep& ps = st.ps;
+  const vcirc::Shape& vs = st.pk.vc;
+  Tr& tr = *st.tr;
+  const size_t vnv = vs.total_vars, vcons = vs.num_cons;
+  const std::vector<fe_t>&Wfold = st.Wfold, &Efold = st.Efold, &Xfold = st.Xfold;
+  const fe_t ufold = st.ufold;
+  fe_t* v_claims = st.v_claims;
   tr.absorb_scalars("u_relaxed", &ufold, 1);
   tr.absorb_scalars("X_relaxed", Xfold.data(), Xfold.size());
   const size_t vlx = log2_ceil(vcons), vnvp = next_pow2(vnv), vly = log2_ceil(vnvp) + 1, vz_len = 2 * vnvp;
-  std::vector<fe_t> zr = Wfold;
+  std::vector<fe_t> zr = Wfold, mv[3];
   zr.push_back(ufold);
   zr.insert(zr.end(), Xfold.begin(), Xfold.end());
   vs.multiply_vec(zr, mv);
@@ -961,26 +1155,26 @@ static ProofBuf nn_prove(const NNZkKey& pk, NNZkPrep& ps, Tape& tape, double* ph
   par_for(vcons, 96, [&](size_t lo, size_t hi) {
     for (size_t i = lo; i < hi; ++i) uczE[i] = fe_add<S>(fe_mul<S>(ufold, mv[2][i]), Efold[i]);
   });
-  std::vector<fe_t> v_outer(3 * vlx), v_rx(vlx), v_inner(2 * vly), v_ry(vly);
-  fe_t v_claims[3];
+  std::vector<fe_t> v_rx(vlx), v_ry(vly);
+  st.v_outer.resize(3 * vlx);
+  st.v_inner.resize(2 * vly);
   // the two relaxed-Spartan sum-checks run on tables this driver holds on the host (2^9 and 2^12 elements): with polling host threads in the process
   // every round is run there (sp_sumcheck_*_host); staged to the device they are a trip over the bus a round
   static const bool host_sc_off = [] {
     const char* e = getenv("SPARTAN_HOST_SC");  // "0": the device provers on staged tables (A/B runs)
     return e && e[0] == '0';
   }();
-  const bool host_sc = side && sp_walkers() > 0 && !host_sc_off;
+  const bool host_sc = st.side && sp_walkers() > 0 && !host_sc_off;
+  const fe_t zero = fe_zero();
   if (host_sc) {
-    const fe_t zero = fe_zero();
-    ck(sp_sumcheck_cubic3_host(ctx, u64p(&zero), u64p(vtau.data()), vlx, u64p(mv[0].data()), u64p(mv[1].data()), u64p(uczE.data()), tr.t, u64p(v_outer.data()),
+    ck(sp_sumcheck_cubic3_host(ctx, u64p(&zero), u64p(vtau.data()), vlx, u64p(mv[0].data()), u64p(mv[1].data()), u64p(uczE.data()), tr.t, u64p(st.v_outer.data()),
                                u64p(v_rx.data()), u64p(v_claims)),
        "relaxed outer sum-check (host tables)");
   } else {
     sp_table *ta = stage(ctx, ps, 0, mv[0].data(), vcons), *tb = stage(ctx, ps, 1, mv[1].data(), vcons), *tc = stage(ctx, ps, 2, uczE.data(), vcons);
-    const fe_t zero = fe_zero();
-    ck(sp_sumcheck_cubic3(ctx, u64p(&zero), u64p(vtau.data()), vlx, ta, tb, tc, tr.t, u64p(v_outer.data()), u64p(v_rx.data()), u64p(v_claims)), "relaxed outer sum-check");
+    ck(sp_sumcheck_cubic3(ctx, u64p(&zero), u64p(vtau.data()), vlx, ta, tb, tc, tr.t, u64p(st.v_outer.data()), u64p(v_rx.data()), u64p(v_claims)), "relaxed outer sum-check");
   }
-  lap("folds + relaxed outer sc");
+  st.laps.lap("folds + relaxed outer sc");
   tr.absorb_scalars("claims_outer", v_claims, 3);
   const fe_t vr = tr.squeeze("r"), vr2 = fe_mul<S>(vr, vr);
   const std::vector<fe_t> v_evals_rx = eq_evals_host(v_rx.data(), vlx);
@@ -996,7 +1190,8 @@ static ProofBuf nn_prove(const NNZkKey& pk, NNZkPrep& ps, Tape& tape, double* ph
     });
     for (const auto& x : partial) claim_E = fe_add<S>(claim_E, x);
   }
-  const fe_t v_claim_inner = fe_add<S>(fe_add<S>(v_claims[0], fe_mul<S>(vr, v_claims[1])), fe_mul<S>(vr2, fe_sub<S>(v_claims[2], claim_E)));
+  const fe_t minus_E[3] = {v_claims[0], v_claims[1], fe_sub<S>(v_claims[2], claim_E)};
+  const fe_t v_claim_inner = joint_inner_claim(minus_E, vr, vr2);
   const size_t vcols = vs.num_cols();
   std::vector<fe_t> vabc(vz_len, fe_zero());
   {
@@ -1017,194 +1212,212 @@ static ProofBuf nn_prove(const NNZkKey& pk, NNZkPrep& ps, Tape& tape, double* ph
       for (size_t i = lo; i < hi; ++i) vabc[i] = fe_add<S>(fe_add<S>(ev[0][i], fe_mul<S>(vr, ev[1][i])), fe_mul<S>(r2u, ev[2][i]));
     });
   }
-  lap("claim_E + bind_matrix_rows");
+  st.laps.lap("claim_E + bind_matrix_rows");
   zr.resize(vz_len, fe_zero());
+  fe_t ci[2];
   if (host_sc) {
-    fe_t ci[2];
-    ck(sp_sumcheck_quad_host(ctx, u64p(&v_claim_inner), vly, u64p(vabc.data()), u64p(zr.data()), tr.t, u64p(v_inner.data()), u64p(v_ry.data()), u64p(ci)),
+    ck(sp_sumcheck_quad_host(ctx, u64p(&v_claim_inner), vly, u64p(vabc.data()), u64p(zr.data()), tr.t, u64p(st.v_inner.data()), u64p(v_ry.data()), u64p(ci)),
        "relaxed inner sum-check (host tables)");
   } else {
     sp_table *ta = stage(ctx, ps, 3, vabc.data(), vz_len), *tb = stage(ctx, ps, 4, zr.data(), vz_len);
-    fe_t ci[2];
-    ck(sp_sumcheck_quad(ctx, u64p(&v_claim_inner), vly, ta, tb, tr.t, u64p(v_inner.data()), u64p(v_ry.data()), u64p(ci)), "relaxed inner sum-check");
+    ck(sp_sumcheck_quad(ctx, u64p(&v_claim_inner), vly, ta, tb, tr.t, u64p(st.v_inner.data()), u64p(v_ry.data()), u64p(ci)), "relaxed inner sum-check");
   }
-  lap("relaxed inner sc");
-  std::vector<fe_t> v_W, v_E;
-  fe_t blind_vW, blind_vE;
-  prove_direct(32, Wfold, rWfold, v_ry.data() + 1, vly - 1, &v_W, &blind_vW);
-  prove_direct(32, Efold, rEfold, v_rx.data(), vlx, &v_E, &blind_vE);
-  tr.absorb_scalars("v_W", v_W.data(), v_W.size());
-  tr.absorb_scalars("v_E", v_E.data(), v_E.size());
-  lap("prove_direct x2");
-  const double t_vc = now();
+  st.laps.lap("relaxed inner sc");
+  prove_direct(32, Wfold, st.rWfold, v_ry.data() + 1, vly - 1, &st.v_W, &st.blind_vW);
+  prove_direct(32, Efold, st.rEfold, v_rx.data(), vlx, &st.v_E, &st.blind_vE);
+  tr.absorb_scalars("v_W", st.v_W.data(), st.v_W.size());
+  tr.absorb_scalars("v_E", st.v_E.data(), st.v_E.size());
+  st.laps.lap("prove_direct x2");
+  st.t_vc = st.now();
+}
 
-  // fold the two evaluation claims (:2019-2051) and open (:2054-2065)
+// W = folded_W + c_eval * core_W as a table: only where the opening's halves were not computed ahead
+static void nn_fold_W(NNProveState& st, const fe_t& c_eval) {
+  const sp_table* two[2] = {st.fW, st.ps.core.W};
+  const fe_t wts[2] = {fe_one<S>(), c_eval};
+  ck(sp_fold_tables(st.ctx, two, 2, u64p(wts), st.nv, st.Wf), "W = folded_W + c_eval * core_W");
+}
+// PCS::prove(ck, ck_eval = the width-32 key, transcript, comm, W, blind, r_y[1..], comm_eval, blind_eval) (:2067-2080) as one call
+static void nn_open_reference_order(NNProveState& st) {
+  const NNZkKey& pk = st.pk;
+  Tape& tape = st.tape;
+  const size_t CW = st.CW;
+  nn_fold_W(st, st.c_eval);
+  std::vector<uint64_t> arg(16 + 4 * CW + 8);
+  ck(sp_hyrax_prove(st.ctx, pk.ck, pk.vc_ck, st.tr->t, u64p(&st.comm[0].x), st.comm.size(), st.Wf, st.nv, u64p(st.blind.data()), u64p(st.r_y.data() + 1), pk.ny - 1,
+                    u64p(&st.comm_eval.x), u64p(&st.blind_eval), tape.bytes + 64 * tape.pos, tape.blocks - tape.pos, arg.data()),
+     "PCS::prove");
+  tape.skip(CW + 2);
+  memcpy(&st.delta, arg.data(), 64);
+  memcpy(&st.beta, arg.data() + 8, 64);
+  memcpy(st.z_vec.data(), arg.data() + 16, 32 * CW);
+  memcpy(&st.z_delta, arg.data() + 16 + 4 * CW, 32);
+  memcpy(&st.z_beta, arg.data() + 16 + 4 * CW + 4, 32);
+}
+// HyraxPCS::prove (hyrax_pc.rs:387-478) + InnerProductArgumentLinear::prove (ipa.rs:125-170) statement by statement, taking what the helper's jobs and the
+// products ahead have ready
+static void nn_open_side(NNProveState& st) {
+  sp_ctx* ctx = st.ctx;
+  const NNZkKey& pk = st.pk;
+  NNZkPrep& ps = st.ps;
+  Tape& tape = st.tape;
+  Tr& tr = *st.tr;
+  const fe_t c_eval = st.c_eval;
+  {
+    const std::vector<uint8_t> b = commitment_bytes(st.comm.data(), st.comm.size());
+    tr.absorb("poly_com", b.data(), b.size());
+  }
+  st.laps.lap("pcs: absorb poly_com");
+  const fe_t* point = st.r_y.data() + 1;
+  const size_t npoint = pk.ny - 1, nvr = st.nvr;
+  const std::vector<fe_t> L = eq_evals_host(point, nvr);
+  const size_t ncols = (size_t)1 << (npoint - nvr);
+  if (st.t_open) ps.wk.wait(st.t_open);
+  st.laps.lap("pcs: wait for the opening's points");
+  const bool open_ahead = st.t_open && ps.open.delta_valid && ps.open.points_valid && ps.open.tape_from == tape.pos && ncols == ps.open.dv.size();
+  std::vector<fe_t> LZ(ncols), Rv;
+  NNLzAhead& lz = st.lz;
+  lz.step(ctx, ps.core.W, st.r_y.data(), nvr);
+  if (lz.have == 2 && lz.f.size() == ncols && lz.c.size() == ncols) {
+    const fe_t *lf = lz.f.data(), *lc = lz.c.data();
+    par_for(ncols, 256, [&](size_t lo, size_t hi) {
+      for (size_t i = lo; i < hi; ++i) LZ[i] = fe_add<S>(lf[i], fe_mul<S>(c_eval, lc[i]));
+    });
+  } else {
+    nn_fold_W(st, c_eval);
+    ck(sp_rowmat_vec(ctx, st.Wf, L.size(), ncols, u64p(L.data()), u64p(LZ.data())), "bind_with_delayed");
+  }
+  st.laps.lap("pcs: L^T W");
+  fe_t r_LZ = fe_zero();
+  for (size_t i = 0; i < L.size(); ++i) r_LZ = fe_add<S>(r_LZ, fe_mul<S>(L[i], st.blind[i]));
+  std::vector<fe_t> dv;
+  fe_t r_delta, r_beta;
+  aff_t comm_LZ;
+  if (open_ahead) {
+    // the helper has delta, beta and the two halves of comm_LZ = <L, rows of (folded + c_eval core)> = P_f + c_eval P_c
+    dv.swap(ps.open.dv);
+    r_delta = ps.open.r_delta;
+    r_beta = ps.open.r_beta;
+    tape.skip(ps.open.tape_count);
+    st.delta = ps.open.delta;
+    st.beta = ps.open.beta;
+    fold2_finish_or_call(ctx, ps.open.lz_fold, &ps.open.P_f, &ps.open.P_c, 1, c_eval, &comm_LZ, "comm_LZ = P_f + c_eval P_c");
+  } else {
+    if (st.laps.on && st.side)
+      fprintf(stderr, "nn_prove: opening inputs computed inline (delta %d, points %d, tape %zu vs %zu)\n", (int)ps.open.delta_valid, (int)ps.open.points_valid, ps.open.tape_from, tape.pos);
+    // the mask d and its blinds do not depend on the transcript (ipa.rs:139-147): delta's MSM runs on the auxiliary stream beside comm_LZ's
+    Rv = eq_evals_host(point + nvr, npoint - nvr);
+    dv.resize(Rv.size());
+    for (auto& x : dv) x = tape.next();
+    r_delta = tape.next();
+    r_beta = tape.next();
+    sp_msm_job* dj = nullptr;
+    ck(sp_msm_ck_begin(ctx, pk.ck, u64p(dv.data()), dv.size(), &dj), "delta (begin)");
+    int rc_lz = sp_msm_ck(ctx, pk.ck, u64p(LZ.data()), LZ.size(), u64p(&r_LZ), u64p(&comm_LZ.x));
+    int rc_d = sp_msm_ck_finish(ctx, pk.ck, dj, u64p(&r_delta), u64p(&st.delta.x));  // always collected: the job owns device work
+    ck(rc_lz, "comm_LZ");
+    ck(rc_d, "delta (finish)");
+    fe_t ip = fe_zero();
+    for (size_t i = 0; i < Rv.size(); ++i) ip = fe_add<S>(ip, fe_mul<S>(Rv[i], dv[i]));
+    ck(sp_hyrax_commit_small(ctx, pk.vc_ck, u64p(&ip), 1, u64p(&r_beta), u64p(&st.beta.x)), "beta");
+  }
+  tr.dom_sep("inner product argument (linear)");
+  absorb_ipa_instance(tr, comm_LZ, st.comm_eval, st.delta, st.beta);
+  const fe_t rr = tr.squeeze("r");
+  st.laps.lap("pcs: comm_LZ + transcript");
+  par_for(ncols, 256, [&](size_t lo, size_t hi) {
+    for (size_t i = lo; i < hi; ++i) st.z_vec[i] = fe_add<S>(fe_mul<S>(rr, LZ[i]), dv[i]);
+  });
+  st.z_delta = fe_add<S>(fe_mul<S>(rr, r_LZ), r_delta);
+  st.z_beta = fe_add<S>(fe_mul<S>(rr, st.blind_eval), r_beta);
+  st.laps.lap("pcs: z_vec");
+}
+// fold the two evaluation claims (:2019-2051) and open (:2054-2065); ck_eval = the width-32 key (ck_c = its first base, its h)
+static void nn_prove_opening(NNProveState& st) {
+  sp_ctx* ctx = st.ctx;
+  const vcirc::State& vst = *st.vst;
+  const size_t rows = st.rows, inner_final = st.inner_final;
   const std::vector<aff_t>& comm_eW_s = vst.comm_per_round[inner_final + 1];
   const std::vector<aff_t>& comm_eW_c = vst.comm_per_round[inner_final + 2];
-  const fe_t c_eval = tr.squeeze("c_eval");
-  std::vector<aff_t> comm(rows);
-  if (t_fold) ps.wk.wait(t_fold);  // the folded commitment of the step instances: the helper's second job, started behind the NIFS rounds
-  lap("pcs: wait for the folded commitment");
-  if (fold2.rows) {
-    sp_fold2_job* j = fold2.rows;
-    fold2.rows = nullptr;
-    ck(sp_fold_commitments2_finish(ctx, j, u64p(&f_comm[0].x), u64p(&c_eval), u64p(&comm[0].x)), "fold_commitments");
-  } else {
-    ck(sp_fold_commitments2(ctx, u64p(&f_comm[0].x), u64p(&core_comm[0].x), rows, u64p(&c_eval), u64p(&comm[0].x)), "fold_commitments");
-  }
-  lap("pcs: fold_commitments2 (rows)");
-  std::vector<fe_t> blind(rows);
+  const fe_t c_eval = st.c_eval = st.tr->squeeze("c_eval");
+  st.comm.resize(rows);
+  if (st.t_fold) st.ps.wk.wait(st.t_fold);  // the folded commitment of the step instances: the helper's second job, started behind the NIFS rounds
+  st.laps.lap("pcs: wait for the folded commitment");
+  fold2_finish_or_call(ctx, st.fold2.rows, st.f_comm.data(), st.core_comm.data(), rows, c_eval, st.comm.data(), "fold_commitments");
+  st.laps.lap("pcs: fold_commitments2 (rows)");
+  st.blind.resize(rows);
   for (size_t i = 0; i < rows; ++i) {
     fe_t a;
-    memcpy(&a, f_rW.data() + 4 * i, 32);
-    blind[i] = fe_add<S>(a, fe_mul<S>(c_eval, core_rW[i]));
+    memcpy(&a, st.f_rW.data() + 4 * i, 32);
+    st.blind[i] = fe_add<S>(a, fe_mul<S>(c_eval, st.core_rW[i]));
   }
-  auto fold_W = [&] {  // W = folded_W + c_eval * core_W as a table: only where the opening's halves were not computed ahead
-    const sp_table* two[2] = {fW, ps.core.W};
-    const fe_t wts[2] = {one, c_eval};
-    ck(sp_fold_tables(ctx, two, 2, u64p(wts), nv, Wf), "W = folded_W + c_eval * core_W");
-  };
-  aff_t comm_eval;
-  if (fold2.eval) {
-    sp_fold2_job* j = fold2.eval;
-    fold2.eval = nullptr;
-    ck(sp_fold_commitments2_finish(ctx, j, u64p(&comm_eW_s[0].x), u64p(&c_eval), u64p(&comm_eval.x)), "fold eval commitments");
-  } else {
-    ck(sp_fold_commitments2(ctx, u64p(&comm_eW_s[0].x), u64p(&comm_eW_c[0].x), 1, u64p(&c_eval), u64p(&comm_eval.x)), "fold eval commitments");
-  }
-  const fe_t blind_eval = fe_add<S>(vst.blind_per_round[inner_final + 1][0], fe_mul<S>(c_eval, vst.blind_per_round[inner_final + 2][0]));
-  lap("pcs: W fold + eval commitment fold");
-  // HyraxPCS::prove (hyrax_pc.rs:387-478) + InnerProductArgumentLinear::prove (ipa.rs:125-170); ck_eval = the width-32 key (ck_c = its first base, its h)
-  aff_t delta, beta;
-  std::vector<fe_t> z_vec(CW);
-  fe_t z_delta, z_beta;
-  if (reference_order) {  // PCS::prove(ck, ck_eval = the width-32 key, transcript, comm, W, blind, r_y[1..], comm_eval, blind_eval) (:2067-2080) as one call
-    fold_W();
-    std::vector<uint64_t> arg(16 + 4 * CW + 8);
-    ck(sp_hyrax_prove(ctx, pk.ck, pk.vc_ck, tr.t, u64p(&comm[0].x), comm.size(), Wf, nv, u64p(blind.data()), u64p(r_y.data() + 1), pk.ny - 1, u64p(&comm_eval.x),
-                      u64p(&blind_eval), tape.bytes + 64 * tape.pos, tape.blocks - tape.pos, arg.data()),
-       "PCS::prove");
-    tape.skip(CW + 2);
-    memcpy(&delta, arg.data(), 64);
-    memcpy(&beta, arg.data() + 8, 64);
-    memcpy(z_vec.data(), arg.data() + 16, 32 * CW);
-    memcpy(&z_delta, arg.data() + 16 + 4 * CW, 32);
-    memcpy(&z_beta, arg.data() + 16 + 4 * CW + 4, 32);
-  } else {
-    const std::vector<uint8_t> b = commitment_bytes(comm.data(), comm.size());
-    tr.absorb("poly_com", b.data(), b.size());
-    lap("pcs: absorb poly_com");
-    const fe_t* point = r_y.data() + 1;
-    const size_t npoint = pk.ny - 1, nvr = log2_ceil(rows);
-    const std::vector<fe_t> L = eq_evals_host(point, nvr);
-    const size_t ncols = (size_t)1 << (npoint - nvr);
-    if (t_open) ps.wk.wait(t_open);
-    lap("pcs: wait for the opening's points");
-    const bool open_ahead = t_open && ps.open.delta_valid && ps.open.points_valid && ps.open.tape_from == tape.pos && ncols == ps.open.dv.size();
-    std::vector<fe_t> LZ(ncols), Rv;
-    lz_step();
-    if (lz.have == 2 && lz.f.size() == ncols && lz.c.size() == ncols) {
-      const fe_t *lf = lz.f.data(), *lc = lz.c.data();
-      par_for(ncols, 256, [&](size_t lo, size_t hi) {
-        for (size_t i = lo; i < hi; ++i) LZ[i] = fe_add<S>(lf[i], fe_mul<S>(c_eval, lc[i]));
-      });
-    } else {
-      fold_W();
-      ck(sp_rowmat_vec(ctx, Wf, L.size(), ncols, u64p(L.data()), u64p(LZ.data())), "bind_with_delayed");
-    }
-    lap("pcs: L^T W");
-    fe_t r_LZ = fe_zero();
-    for (size_t i = 0; i < L.size(); ++i) r_LZ = fe_add<S>(r_LZ, fe_mul<S>(L[i], blind[i]));
-    std::vector<fe_t> dv;
-    fe_t r_delta, r_beta;
-    aff_t comm_LZ;
-    if (open_ahead) {
-      // the helper has delta, beta and the two halves of comm_LZ = <L, rows of (folded + c_eval core)> = P_f + c_eval P_c
-      dv.swap(ps.open.dv);
-      r_delta = ps.open.r_delta;
-      r_beta = ps.open.r_beta;
-      tape.skip(ps.open.tape_count);
-      delta = ps.open.delta;
-      beta = ps.open.beta;
-      if (ps.open.lz_fold) {
-        sp_fold2_job* j = ps.open.lz_fold;
-        ps.open.lz_fold = nullptr;
-        ck(sp_fold_commitments2_finish(ctx, j, u64p(&ps.open.P_f.x), u64p(&c_eval), u64p(&comm_LZ.x)), "comm_LZ = P_f + c_eval P_c");
-      } else {
-        ck(sp_fold_commitments2(ctx, u64p(&ps.open.P_f.x), u64p(&ps.open.P_c.x), 1, u64p(&c_eval), u64p(&comm_LZ.x)), "comm_LZ = P_f + c_eval P_c");
-      }
-    } else {
-      if (laps && side) fprintf(stderr, "nn_prove: opening inputs computed inline (delta %d, points %d, tape %zu vs %zu)\n", (int)ps.open.delta_valid, (int)ps.open.points_valid, ps.open.tape_from, tape.pos);
-      // the mask d and its blinds do not depend on the transcript (ipa.rs:139-147): delta's MSM runs on the auxiliary stream beside comm_LZ's
-      Rv = eq_evals_host(point + nvr, npoint - nvr);
-      dv.resize(Rv.size());
-      for (auto& x : dv) x = tape.next();
-      r_delta = tape.next();
-      r_beta = tape.next();
-      sp_msm_job* dj = nullptr;
-      ck(sp_msm_ck_begin(ctx, pk.ck, u64p(dv.data()), dv.size(), &dj), "delta (begin)");
-      int rc_lz = sp_msm_ck(ctx, pk.ck, u64p(LZ.data()), LZ.size(), u64p(&r_LZ), u64p(&comm_LZ.x));
-      int rc_d = sp_msm_ck_finish(ctx, pk.ck, dj, u64p(&r_delta), u64p(&delta.x));  // always collected: the job owns device work
-      ck(rc_lz, "comm_LZ");
-      ck(rc_d, "delta (finish)");
-      fe_t ip = fe_zero();
-      for (size_t i = 0; i < Rv.size(); ++i) ip = fe_add<S>(ip, fe_mul<S>(Rv[i], dv[i]));
-      ck(sp_hyrax_commit_small(ctx, pk.vc_ck, u64p(&ip), 1, u64p(&r_beta), u64p(&beta.x)), "beta");
-    }
-    tr.dom_sep("inner product argument (linear)");
-    uint8_t pb[128];
-    point_bytes(comm_LZ, pb);
-    point_bytes(comm_eval, pb + 64);
-    tr.absorb("U", pb, 128);
-    point_bytes(delta, pb);
-    tr.absorb("delta", pb, 64);
-    point_bytes(beta, pb);
-    tr.absorb("beta", pb, 64);
-    const fe_t rr = tr.squeeze("r");
-    lap("pcs: comm_LZ + transcript");
-    par_for(ncols, 256, [&](size_t lo, size_t hi) {
-      for (size_t i = lo; i < hi; ++i) z_vec[i] = fe_add<S>(fe_mul<S>(rr, LZ[i]), dv[i]);
-    });
-    z_delta = fe_add<S>(fe_mul<S>(rr, r_LZ), r_delta);
-    z_beta = fe_add<S>(fe_mul<S>(rr, blind_eval), r_beta);
-    lap("pcs: z_vec");
-  }
-  const double t_end = now();
-  // the rest of the proof in the canonical layout
-  proof.pp(delta);
-  proof.pp(beta);
-  for (const fe_t& f : z_vec) proof.pf(f);
-  proof.pf(z_delta);
-  proof.pf(z_beta);
+  fold2_finish_or_call(ctx, st.fold2.eval, comm_eW_s.data(), comm_eW_c.data(), 1, c_eval, &st.comm_eval, "fold eval commitments");
+  st.blind_eval = fe_add<S>(vst.blind_per_round[inner_final + 1][0], fe_mul<S>(c_eval, vst.blind_per_round[inner_final + 2][0]));
+  st.laps.lap("pcs: W fold + eval commitment fold");
+  st.z_vec.resize(st.CW);
+  if (st.reference_order) nn_open_reference_order(st);
+  else nn_open_side(st);
+  st.t_end = st.now();
+}
+
+// the rest of the proof in the canonical layout; phase_ms[8]: see nnz_prove_impl
+static ProofBuf nn_prove_emit(NNProveState& st, double* phase_ms) {
+  ProofBuf& proof = st.proof;
+  const vcirc::State& vst = *st.vst;
+  proof.pp(st.delta);
+  proof.pp(st.beta);
+  for (const fe_t& f : st.z_vec) proof.pf(f);
+  proof.pf(st.z_delta);
+  proof.pf(st.z_beta);
   for (const auto& c : vst.comm_per_round) proof.pc(c);
-  for (const fe_t& f : vpub) proof.pf(f);
+  for (const fe_t& f : st.vpub) proof.pf(f);
   for (const auto& cr : vst.challenges)
     for (const fe_t& f : cr) proof.pf(f);
-  proof.pc(comm_T);
-  proof.pc(rnd_comm_W);
-  proof.pc(rnd_comm_E);
-  proof.pf(rnd_u);
-  for (const fe_t& f : rnd_X) proof.pf(f);
-  for (const fe_t& f : v_outer) proof.pf(f);
-  for (int i = 0; i < 3; ++i) proof.pf(v_claims[i]);
-  for (const fe_t& f : v_inner) proof.pf(f);
-  for (const fe_t& f : v_W) proof.pf(f);
-  proof.pf(blind_vW);
-  for (const fe_t& f : v_E) proof.pf(f);
-  proof.pf(blind_vE);
+  proof.pc(st.comm_T);
+  proof.pc(st.rnd.comm_W);
+  proof.pc(st.rnd.comm_E);
+  proof.pf(st.rnd_u);
+  for (const fe_t& f : st.rnd_X) proof.pf(f);
+  for (const fe_t& f : st.v_outer) proof.pf(f);
+  for (int i = 0; i < 3; ++i) proof.pf(st.v_claims[i]);
+  for (const fe_t& f : st.v_inner) proof.pf(f);
+  for (const fe_t& f : st.v_W) proof.pf(f);
+  proof.pf(st.blind_vW);
+  for (const fe_t& f : st.v_E) proof.pf(f);
+  proof.pf(st.blind_vE);
   if (phase_ms) {
-    phase_ms[0] = t_inst - t_start;   // rerandomize + instances
-    phase_ms[1] = t_nifs - t_inst;    // NIFS (layers, rounds, folds, process_round per round)
-    phase_ms[2] = t_outer - t_nifs;   // core products + batched outer sum-check
-    phase_ms[3] = t_inner - t_outer;  // poly_ABC x 2 + batched inner sum-check
-    phase_ms[4] = t_vc - t_inner;     // verifier-circuit instance: random instance, NovaNIFS, relaxed Spartan
-    phase_ms[5] = t_end - t_vc;       // folded opening
-    phase_ms[6] = t_end - t_start;
+    phase_ms[0] = st.t_inst - st.t_start;   // rerandomize + instances
+    phase_ms[1] = st.t_nifs - st.t_inst;    // NIFS (layers, rounds, folds, process_round per round)
+    phase_ms[2] = st.t_outer - st.t_nifs;   // core products + batched outer sum-check
+    phase_ms[3] = st.t_inner - st.t_outer;  // poly_ABC x 2 + batched inner sum-check
+    phase_ms[4] = st.t_vc - st.t_inner;     // verifier-circuit instance: random instance, NovaNIFS, relaxed Spartan
+    phase_ms[5] = st.t_end - st.t_vc;       // folded opening
+    phase_ms[6] = st.t_end - st.t_start;
     phase_ms[7] = vst.commit_ms;  // inside the phases above: the per-round verifier-circuit commitments (process_round)
   }
-  if (proof.words.size() != pk.layout.words()) throw Error(SP_ERR_INTERNAL, "nn_prove: the proof does not fill the key's layout");
-  return proof;
+  if (proof.words.size() != st.pk.layout.words()) throw Error(SP_ERR_INTERNAL, "nn_prove: the proof does not fill the key's layout");
+  return std::move(proof);
 }
+
+static ProofBuf nn_prove(const NNZkKey& pk, NNZkPrep& ps, Tape& tape, double* phase_ms, bool reference_order = false) {
+  NNProveState st(pk, ps, tape, reference_order);
+  st.t_start = st.now();
+  st.laps.start(st.t_start);
+  nn_prove_setup(st);
+  nn_prove_rerandomize(st);
+  nn_prove_rest_commitments(st);
+  nn_prove_instances(st);
+  nn_prove_nifs(st);
+  nn_prove_outer(st);
+  nn_prove_inner(st);
+  nn_prove_vc_instance(st);
+  nn_prove_random_instance(st);
+  nn_prove_nova_nifs(st);
+  nn_prove_relaxed_spartan(st);
+  nn_prove_opening(st);
+  return nn_prove_emit(st, phase_ms);
+}
+
 
 
 // ---- NeutronNovaZkSNARK::verify (src/neutronnova_zk.rs:2096-2343) — SURVEY 8(f) rank 3 for caller #2 -----------------------------------------------
@@ -1237,15 +1450,8 @@ struct NNVerifyState {
   aff_t comm_LZ, comm_eval;
   fe_t rr, ip;  // the IPA challenge; <z_vec, R>
   ZJob zjob;    // <z_vec, ck> of the single form (the batch forms it once for all proofs)
-  bool laps = false;
-  double t_lap = 0;
-  static double now() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-  void lap(const char* what) {
-    if (!laps) return;
-    const double t = now();
-    fprintf(stderr, "nn_verify lap %-28s %8.3f ms\n", what, t - t_lap);
-    t_lap = t;
-  }
+  NNLaps laps{"nn_verify"};
+  void lap(const char* what) { laps.lap(what); }
 };
 
 static int nn_verify_parse(const NNZkKey& pk, const uint64_t* words, size_t nwords, NNVerifyState& st) {
@@ -1348,8 +1554,7 @@ static int nn_verify_transcript(const NNZkKey& pk, NNVerifyState& st) {
   auto lap = [&](const char* what) { st.lap(what); };
   st.tr.reset(new Tr(ctx, "neutronnova_prove"));
   Tr& tr = *st.tr;
-  tr.absorb("vk", pk.vk_digest, 32);
-  absorb_instance(tr, "core_instance", core_comm, core_X);
+  absorb_head(tr, pk, core_comm, core_X);
   for (size_t i = 0; i < np; ++i) absorb_instance(tr, "U", Ucomm[inst(i)], std::vector<fe_t>(pv.steps[inst(i)].pub, pv.steps[inst(i)].pub + dpub));
   {
     uint8_t zero_be[32] = {0};  // T = 0 (:556-557)
@@ -1368,20 +1573,9 @@ static int nn_verify_transcript(const NNZkKey& pk, NNVerifyState& st) {
   }
   lap("vc instance replayed");
   // NovaNIFS::verify (src/nifs.rs:65-77): the random relaxed instance folded with the verifier-circuit instance
-  {
-    std::vector<uint8_t> b = commitment_bytes(rnd_comm_W, vnv / VW), e = commitment_bytes(rnd_comm_E, vcons / VW);
-    b.insert(b.end(), e.begin(), e.end());
-    const size_t off = b.size();
-    b.resize(off + 32 * (1 + vio));
-    sp::fe_to_be_bytes<S>(rnd_u, b.data() + off);
-    for (size_t j = 0; j < vio; ++j) sp::fe_to_be_bytes<S>(rnd_X[j], b.data() + off + 32 * (1 + j));
-    tr.absorb("U1", b.data(), b.size());
-  }
+  absorb_U1(tr, rnd_comm_W, vnv / VW, rnd_comm_E, vcons / VW, rnd_u, rnd_X, vio);
   absorb_instance(tr, "U2", Uv_comm, Uv_X);
-  {
-    const std::vector<uint8_t> b = commitment_bytes(comm_T, vcons / VW);
-    tr.absorb("comm_T", b.data(), b.size());
-  }
+  absorb_comm_T(tr, comm_T, vcons / VW);
   const fe_t rf = tr.squeeze("r");
   std::vector<aff_t> fU_W(vnv / VW), fU_E(vcons / VW);
   ck(sp_fold_commitments2(ctx, u64p(&rnd_comm_W[0].x), u64p(&Uv_comm[0].x), fU_W.size(), u64p(&rf), u64p(&fU_W[0].x)), "fold comm_W");
@@ -1426,7 +1620,8 @@ static int nn_verify_transcript(const NNZkKey& pk, NNVerifyState& st) {
     const fe_t vr = tr.squeeze("r"), vr2 = fe_mul<S>(vr, vr);
     fe_t eval_E, eval_W;
     if (!verify_direct(fU_E, v_E, blind_vE, vrx.data(), vlx, &eval_E)) return 4;
-    const fe_t claim_inner = fe_add<S>(fe_add<S>(v_claims[0], fe_mul<S>(vr, v_claims[1])), fe_mul<S>(vr2, fe_sub<S>(v_claims[2], eval_E)));
+    const fe_t minus_E[3] = {v_claims[0], v_claims[1], fe_sub<S>(v_claims[2], eval_E)};
+    const fe_t claim_inner = joint_inner_claim(minus_E, vr, vr2);
     if (!sumcheck_verify(tr, claim_inner, vly, 2, v_inner, &claim_inner_final, &vry)) return 4;
     if (!verify_direct(fU_W, v_W, blind_vW, vry.data() + 1, vly - 1, &eval_W)) return 4;
     const std::vector<fe_t> Tx = eq_evals_host(vrx.data(), vlx), Ty = eq_evals_host(vry.data(), vly);
@@ -1462,13 +1657,8 @@ static int nn_verify_publics(const NNZkKey& pk, NNVerifyState& st) {
   const fe_t r = Uv_X[nb + nx], r2 = fe_mul<S>(r, r), one = fe_one<S>(), tau = st.tau;
   const fe_t(*eabc)[3] = st.eabc;
   {
-    auto eval_X = [&](const fe_t* Xv, size_t cnt) {
-      std::vector<fe_t> v{one};
-      v.insert(v.end(), Xv, Xv + cnt);
-      return sparse_poly_evaluate(ny - 1, v, r_y + 1);
-    };
-    const fe_t q_step = fe_add<S>(fe_add<S>(eabc[0][0], fe_mul<S>(r, eabc[0][1])), fe_mul<S>(r2, eabc[0][2]));
-    const fe_t q_core = fe_add<S>(fe_add<S>(eabc[1][0], fe_mul<S>(r, eabc[1][1])), fe_mul<S>(r2, eabc[1][2]));
+    auto eval_X = [&](const fe_t* Xv, size_t cnt) { return nn_eval_X(ny, Xv, cnt, r_y); };
+    const fe_t q_step = joint_inner_claim(eabc[0], r, r2), q_core = joint_inner_claim(eabc[1], r, r2);
     fe_t tau_at_rx = one, p = tau;  // PowPolynomial::evaluate (src/polys/power.rs:33-50): tau^(2^i) pairs with the i-th variable from the end
     for (size_t i = 0; i < nx; ++i) {
       tau_at_rx = fe_mul<S>(tau_at_rx, fe_add<S>(one, fe_mul<S>(fe_sub<S>(p, one), r_x[nx - 1 - i])));
@@ -1520,16 +1710,7 @@ static int nn_verify_opening_challenge(const NNZkKey& pk, NNVerifyState& st) {
   }
   if (R.size() != CW) return 6;
   tr.dom_sep("inner product argument (linear)");
-  {
-    uint8_t b[128];
-    point_bytes(comm_LZ, b);
-    point_bytes(comm_eval, b + 64);
-    tr.absorb("U", b, 128);
-    point_bytes(delta, b);
-    tr.absorb("delta", b, 64);
-    point_bytes(beta, b);
-    tr.absorb("beta", b, 64);
-  }
+  absorb_ipa_instance(tr, comm_LZ, comm_eval, delta, beta);
   st.rr = tr.squeeze("r");
   fe_t ip = fe_zero();
   for (size_t i = 0; i < CW; ++i) ip = fe_add<S>(ip, fe_mul<S>(z_vec[i], R[i]));
@@ -1566,13 +1747,8 @@ static int nn_verify(const NNZkKey& pk, const uint64_t* words, size_t nwords) {
   sp_ctx* ctx = pk.ctx;
   if (pk.num_steps == 0 || nwords != pk.layout.words()) return 1;
   ck(sp_ctx_bind_thread(ctx), "device");
-  static const bool laps = [] {
-    const char* e = getenv("SPARTAN_HOST_LAPS");
-    return e && e[0] == '1';
-  }();
   NNVerifyState st;
-  st.laps = laps;
-  st.t_lap = NNVerifyState::now();
+  st.laps.start(NNLaps::now());
   int code;
   if ((code = nn_verify_parse(pk, words, nwords, st)) == 1) return 1;
   st.lap("parse + encoding checks");

@@ -330,15 +330,21 @@ struct FbJobGuard {
   }
 };
 // claim_inner_joint = claims_outer[0] + r claims_outer[1] + r^2 claims_outer[2]   (src/spartan.rs:311-315)
-inline fe_t joint_inner_claim(const fe_t claims_outer[3], const fe_t& r) {
-  return fe_add<S>(fe_add<S>(claims_outer[0], fe_mul<S>(r, claims_outer[1])), fe_mul<S>(fe_mul<S>(r, r), claims_outer[2]));
+inline fe_t joint_inner_claim(const fe_t claims_outer[3], const fe_t& r, const fe_t& r2) {  // (a caller that holds r^2)
+  return fe_add<S>(fe_add<S>(claims_outer[0], fe_mul<S>(r, claims_outer[1])), fe_mul<S>(r2, claims_outer[2]));
 }
-// eval_W = (eval_Z - r_y0 eval_X) / (1 - r_y0)   (src/spartan.rs:405-421); to_regular_instance: X = public_values ++ challenges (src/r1cs/mod.rs:1546-1549)
+inline fe_t joint_inner_claim(const fe_t claims_outer[3], const fe_t& r) { return joint_inner_claim(claims_outer, r, fe_mul<S>(r, r)); }
+// eval_W = (eval_Z - r_y0 eval_X) / (1 - r_y0)   (src/spartan.rs:405-421): the division, once per point (NeutronNova has a step and a core claim at one r_y) ...
+inline fe_t inv_one_minus(const fe_t& r_y0) {
+  const fe_t denom = fe_sub<S>(fe_one<S>(), r_y0);
+  if (fe_is_zero(denom)) throw Error(SP_ERR_DIVISION_BY_ZERO, "DivisionByZero");
+  return fe_inv_vartime<S>(denom);
+}
+inline fe_t eval_W_from(const fe_t& eval_Z, const fe_t& r_y0, const fe_t& eval_X, const fe_t& inv) { return fe_mul<S>(fe_sub<S>(eval_Z, fe_mul<S>(r_y0, eval_X)), inv); }
+// ... and the whole of it; to_regular_instance: X = public_values ++ challenges (src/r1cs/mod.rs:1546-1549)
 inline fe_t eval_W_from(const fe_t& eval_Z, const fe_t* r_y, size_t num_rounds_y, const std::vector<fe_t>& publics, const std::vector<fe_t>& challenges) {
   const fe_t eval_X = sparse_poly_evaluate(num_rounds_y - 1, z_tail(1 + publics.size() + challenges.size(), publics, challenges), r_y + 1);
-  const fe_t denom = fe_sub<S>(fe_one<S>(), r_y[0]);
-  if (fe_is_zero(denom)) throw Error(SP_ERR_DIVISION_BY_ZERO, "DivisionByZero");
-  return fe_mul<S>(fe_sub<S>(eval_Z, fe_mul<S>(r_y[0], eval_X)), fe_inv_vartime<S>(denom));
+  return eval_W_from(eval_Z, r_y[0], eval_X, inv_one_minus(r_y[0]));
 }
 // the IPA's instance and first message in front of its challenge (ipa.rs:128-152): U = (comm_LZ, comm_eval_W), delta, beta
 inline void absorb_ipa_instance(Tr& tr, const aff_t& comm_LZ, const aff_t& comm_eval_W, const aff_t& delta, const aff_t& beta) {

@@ -236,3 +236,110 @@ def test_c3_sha256_neutronnova_32_steps(ctx):
     assert pubs == ([[0]] * 32, [0])
     print("C3 prove phases (ms):", {k: round(v, 3) for k, v in phases.items()}, "proof bytes:", len(data))
     gnn.close()
+
+
+# ---- the prover's observable behaviour beside the proof words: lap lines, the exits on a short tape, the phase times ----------------------------------
+# The literal lists and messages below were recorded from the prover while nn_prove was one function, before it became named steps over one state.
+def _smallest():
+    steps = [frontend.synthetic_circuit(8, 0xA5, num_public=1, witness_seed=50 + i) for i in range(2)]
+    return steps, frontend.synthetic_circuit(8, 0xA5, num_public=1, witness_seed=999)
+
+
+_LAPS_CHILD = """
+import sys
+sys.path.insert(0, {root!r}); sys.path.insert(0, {tests!r})
+import oracle_lib as ol
+from spartan2_amd import frontend, hip, host
+ctx = hip.Context(0)
+steps = [frontend.synthetic_circuit(8, 0xA5, num_public=1, witness_seed=50 + i) for i in range(2)]
+core = frontend.synthetic_circuit(8, 0xA5, num_public=1, witness_seed=999)
+gnn = host.NeutronNovaZkSNARK(ctx, steps, core)
+tape = ol.make_tape(62, 65536)
+at = gnn.prep_prove(tape)
+for ref in (0, 1):
+    for k in range(3):
+        sys.stderr.write("@@ %d %d\\n" % (ref, k)); sys.stderr.flush()
+        words, used, _ = gnn.prove(tape[at:], reference_order=bool(ref))
+        at += used
+        assert gnn.verify(words) == 0
+gnn.close(); ctx.close()
+"""
+
+_LAPS_VC = ["(up to the vc instance)", "random instance + 2 commits", "NovaNIFS: absorbs, Z, multiply_vec, T", "NovaNIFS: commit_T", "NovaNIFS: T + commit_T",
+            "folds + relaxed outer sc", "claim_E + bind_matrix_rows", "relaxed inner sc", "prove_direct x2", "pcs: wait for the folded commitment",
+            "pcs: fold_commitments2 (rows)", "pcs: W fold + eval commitment fold"]
+LAPS_HEADLINE = _LAPS_VC + ["pcs: absorb poly_com", "pcs: wait for the opening's points", "pcs: L^T W", "pcs: comm_LZ + transcript", "pcs: z_vec"]
+LAPS_REFERENCE_ORDER = _LAPS_VC
+
+
+def test_lap_lines_are_the_recorded_ones():
+    """SPARTAN_HOST_LAPS=1 (read once per process, so in a child): the names of the `nn_prove lap` lines of the third prove of each driver, in order, are the
+    recorded lists; the headline driver's third prove prints neither `computed inline` line (its helper jobs delivered the random instance and the opening's
+    inputs). Names only, no times."""
+    import os
+    import re
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = _LAPS_CHILD.format(root=root, tests=os.path.join(root, "tests"))
+    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, SPARTAN_HOST_LAPS="1"), capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    err = r.stderr
+    for ref, want in ((0, LAPS_HEADLINE), (1, LAPS_REFERENCE_ORDER)):
+        third = err.split("@@ %d 2\n" % ref)[1].split("@@ ")[0]
+        names = [m.group(1).rstrip() for m in re.finditer(r"^nn_prove lap (.*?)\s+\d+\.\d{3} ms$", third, re.M)]
+        print("reference_order" if ref else "headline", "lap names:", names)
+        print([l for l in third.splitlines() if "computed inline" in l])
+        assert names == want
+        if not ref:
+            assert "computed inline" not in third
+
+
+SHORT_TAPE_MESSAGES = {  # reference_order -> cut point -> the error's text
+    False: {"1": "rc=-5: random tape exhausted", "used // 2": "rc=-5: random tape exhausted", "used - 1": "rc=-5: random tape exhausted"},
+    # the reference-order driver's opening is one sp_hyrax_prove call, which takes the rest of the tape and reports a short one itself; the opening's
+    # cols + 2 draws are more than half of this prove's, so the tape cut to used // 2 blocks gets that far as well
+    True: {"1": "rc=-5: random tape exhausted",
+           "used // 2": "rc=-1: PCS::prove: Hyrax prove: the randomness stream holds fewer than cols + 2 blocks",
+           "used - 1": "rc=-1: PCS::prove: Hyrax prove: the randomness stream holds fewer than cols + 2 blocks"},
+}
+
+
+@pytest.mark.parametrize("reference_order", [False, True])
+def test_an_exhausted_tape_leaves_the_state_usable(ctx, reference_order):
+    """A tape cut to 1, used // 2 and used - 1 blocks: prove raises (a host-side exception, thrown while helper jobs of the headline driver are in
+    flight) with the recorded text, and the next prove on the same object with the whole tape succeeds and verifies."""
+    steps, core = _smallest()
+    gnn = host.NeutronNovaZkSNARK(ctx, steps, core)
+    tape = ol.make_tape(63, 65536)
+    at = gnn.prep_prove(tape)
+    words, used, _ = gnn.prove(tape[at:], reference_order=reference_order)
+    assert gnn.verify(words) == 0
+    at += used
+    said = {}
+    for name, cut in (("1", 1), ("used // 2", used // 2), ("used - 1", used - 1)):
+        with pytest.raises(hip.SpartanHipError) as e:
+            gnn.prove(tape[at:at + cut], reference_order=reference_order)
+        said[name] = str(e.value)
+        words, used_again, _ = gnn.prove(tape[at:], reference_order=reference_order)
+        assert used_again == used and gnn.verify(words) == 0
+        at += used
+    print(reference_order, said)
+    assert said == SHORT_TAPE_MESSAGES[reference_order]
+    gnn.close()
+
+
+@pytest.mark.parametrize("reference_order", [False, True])
+def test_phase_times_are_consistent(ctx, reference_order):
+    """phases[0..5] telescope over the same seven time stamps as phases[6], the total; phases[7] (the per-round verifier-circuit commitments) lies inside it"""
+    steps, core = _smallest()
+    gnn = host.NeutronNovaZkSNARK(ctx, steps, core)
+    tape = ol.make_tape(64, 32768)
+    at = gnn.prep_prove(tape)
+    _, _, phases = gnn.prove(tape[at:], reference_order=reference_order)
+    ms = [phases[k] for k in host.NN_PHASES]
+    print(ms)
+    assert all(v >= 0 for v in ms[:6]) and abs(sum(ms[:6]) - ms[6]) <= 1e-6
+    assert 0 <= ms[7] <= ms[6]
+    gnn.close()

@@ -18,6 +18,7 @@ using sp::fail;
 typedef FqP S;
 
 #include "group_common.hpp"
+#include "opening_host.hpp"
 #include "walk_pool.hpp"
 #include <sys/mman.h>
 
@@ -1626,17 +1627,7 @@ int sp_msm_points(sp_ctx* c, const sp_table* scalars, size_t off, size_t n, cons
   return SP_OK;
 }
 // eq table of k variables on the host, r[0] on the index MSB (EqPolynomial::evals_from_points, src/polys/eq.rs:59-93)
-static void eq_table_host(const fe_t* r, size_t k, fe_t* out) {
-  out[0] = fe_one<spk::SF>();
-  for (size_t j = 0; j < k; ++j) {
-    const size_t half = (size_t)1 << j;
-    for (size_t i = half; i-- > 0;) {
-      const fe_t hi = fe_mul<spk::SF>(out[i], r[j]);
-      out[2 * i] = fe_sub<spk::SF>(out[i], hi);
-      out[2 * i + 1] = hi;
-    }
-  }
-}
+static void eq_table_host(const fe_t* r, size_t k, fe_t* out) { sp::host::eq_table<spk::SF>(r, k, out); }
 int sp_msm_eq_begin(sp_ctx* c, const sp_points* pts, const uint64_t* r, size_t ell, sp_msm_job** out) {
   if (!pts || !out || (!r && ell)) return fail(SP_ERR_INVALID_INPUT_LENGTH, "sp_msm_eq_begin: null argument");
   if (ell > 20) return fail(SP_ERR_INVALID_INPUT_LENGTH, "sp_msm_eq_begin: more than 2^20 points");
@@ -1749,8 +1740,10 @@ __global__ void __launch_bounds__(256) k_scale_add_wait(const fe_t* __restrict__
   if (threadIdx.x == 0) flags[blockIdx.x] = seq;
 }
 }  // namespace
+}  // extern "C"
+namespace sp {  // (declared in group_common.hpp: the lone opening, capi_opening.hip, uses them too)
 // landing buffer of the product | staging of the addend | landing of the scaled sum | its per-block flags: one mapped pinned allocation, grow-only
-static int ensure_pinned_vec(sp_ctx* c, size_t cols) {
+int ensure_pinned_vec(sp_ctx* c, size_t cols) {
   if (!c->stream3) SP_HIP(hipStreamCreateWithFlags(&c->stream3, hipStreamNonBlocking));
   if (!c->vec_ev) SP_HIP(hipEventCreateWithFlags(&c->vec_ev, hipEventDisableTiming));
   if (c->h_pinned_vec_bytes < 3 * cols * sizeof(fe_t) + VEC_FLAG_BYTES + VEC_CTRL_BYTES) {
@@ -1789,7 +1782,7 @@ static bool scale_add_armed_enabled() {
   }();
   return on;
 }
-static unsigned scale_add_arm(sp_ctx* c, hipStream_t st, const fe_t* dx, const fe_t* da, size_t cols) {
+unsigned scale_add_arm(sp_ctx* c, hipStream_t st, const fe_t* dx, const fe_t* da, size_t cols) {
   const size_t nblocks = (cols + 255) / 256;
   // One context in the process = one prove at a time (the latency case this is for). With several, streams of different contexts share hardware queues and
   // a kernel that WAITS in one holds up whatever another context queued behind it: eight contexts went from 0.61 to 0.83-0.94 ms per proof with it.
@@ -1804,14 +1797,13 @@ static unsigned scale_add_arm(sp_ctx* c, hipStream_t st, const fe_t* dx, const f
   hipLaunchKernelGGL(k_scale_add_wait, dim3((unsigned)nblocks), dim3(256), 0, st, dx, da, d_ctrl, cols, d_hout, d_flags, seq);
   return seq;
 }
-static void scale_add_abort(sp_ctx* c, unsigned seq) {
+void scale_add_abort(sp_ctx* c, unsigned seq) {
   if (!seq || !c->h_pinned_vec) return;
   volatile unsigned* ctl = vec_ctrl(c);
   ctl[10] = seq;
   vec_ctrl_flush(c);
 }
-static int scale_add_to_host(sp_ctx* c, hipStream_t st, const fe_t* dx, const fe_t* da, const fe_t& sc, size_t cols, uint64_t* out, const char* site);
-static int scale_add_fire(sp_ctx* c, hipStream_t st, unsigned seq, const fe_t* dx, const fe_t* da, const fe_t& sc, size_t cols, uint64_t* out, const char* site) {
+int scale_add_fire(sp_ctx* c, hipStream_t st, unsigned seq, const fe_t* dx, const fe_t* da, const fe_t& sc, size_t cols, uint64_t* out, const char* site) {
   const size_t nblocks = (cols + 255) / 256;
   volatile unsigned* ctl = vec_ctrl(c);
   unsigned sum = 0, wsum = 0;
@@ -1856,7 +1848,7 @@ static int scale_add_fire(sp_ctx* c, hipStream_t st, unsigned seq, const fe_t* d
   return SP_OK;
 }
 // scale * x + addend -> mapped host memory, polled through the per-block arrival flags (the tail of sp_rowmat_vec_eq_finish_scaled and of an announced opening)
-static int scale_add_to_host(sp_ctx* c, hipStream_t st, const fe_t* dx, const fe_t* da, const fe_t& sc, size_t cols, uint64_t* out, const char* site) {
+int scale_add_to_host(sp_ctx* c, hipStream_t st, const fe_t* dx, const fe_t* da, const fe_t& sc, size_t cols, uint64_t* out, const char* site) {
   const size_t nblocks = (cols + 255) / 256;
   if (nblocks * sizeof(unsigned) > VEC_FLAG_BYTES) return fail(SP_ERR_INVALID_INPUT_LENGTH, "bind_with_delayed (scaled): more than 2^18 columns");
   if (++c->vec_seq == 0) ++c->vec_seq;
@@ -1885,6 +1877,13 @@ static int scale_add_to_host(sp_ctx* c, hipStream_t st, const fe_t* dx, const fe
   memcpy(out, h_out, cols * sizeof(fe_t));
   return SP_OK;
 }
+// the addend of a scaled sum is the IPA's mask (ipa.rs:139-149): its staging copy in the pinned block and its device copy, the latter on `st`
+void addend_wipe(sp_ctx* c, fe_t* d_add, size_t cols, hipStream_t st) {
+  explicit_bzero(reinterpret_cast<fe_t*>(c->h_pinned_vec) + c->h_pinned_vec_cols, cols * sizeof(fe_t));
+  (void)hipMemsetAsync(d_add, 0, cols * sizeof(fe_t), st);
+}
+}  // namespace sp
+extern "C" {
 int sp_rowmat_vec_eq_begin(sp_ctx* c, const sp_table* poly, const uint64_t* r, size_t ell, size_t cols, sp_vec_job** out) {
   return sp_rowmat_vec_eq_begin_with(c, poly, r, ell, cols, nullptr, out);
 }
@@ -1894,7 +1893,7 @@ int sp_rowmat_vec_eq_begin_with(sp_ctx* c, const sp_table* poly, const uint64_t*
   const size_t rows = (size_t)1 << ell;
   if (rows * cols > poly->cap || cols == 0) return fail(SP_ERR_INVALID_INPUT_LENGTH, "bind_with_delayed: poly shorter than rows*cols");
   int rc_pin;
-  if ((rc_pin = ensure_pinned_vec(c, cols))) return rc_pin;
+  if ((rc_pin = sp::ensure_pinned_vec(c, cols))) return rc_pin;
   const size_t splits = rows < 64 ? rows : 64;
   fe_t* dL = (fe_t*)c->workspace(sp_ctx::WS_ROWMAT_L, rows * sizeof(fe_t), 1);
   fe_t* part = (fe_t*)c->workspace(sp_ctx::WS_ROWMAT_PART, splits * cols * sizeof(fe_t), 1);
@@ -1904,13 +1903,7 @@ int sp_rowmat_vec_eq_begin_with(sp_ctx* c, const sp_table* poly, const uint64_t*
   for (size_t i = 0; i < ell; ++i) memcpy(&rr[i], r + 4 * i, 32);
   hipStream_t st = c->stream3;
   if (ell <= 10) {  // two half tables by value, the product on the device
-    spk::EqTensorArgs a;
-    const size_t hb = ell / 2, lb = ell - hb;
-    eq_table_host(rr, hb, a.left);
-    eq_table_host(rr + hb, lb, a.right);
-    a.lo_bits = (int)lb;
-    a.n = (unsigned)rows;
-    hipLaunchKernelGGL(spk::k_eq_tensor<false>, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, a, dL);
+    sp::launch_eq_rows(st, rr, ell, rows, dL);
   } else {  // more rows than the argument block holds halves for: the table from the host
     std::vector<fe_t> w(rows);
     eq_table_host(rr, ell, w.data());
@@ -1928,7 +1921,7 @@ int sp_rowmat_vec_eq_begin_with(sp_ctx* c, const sp_table* poly, const uint64_t*
     memcpy(stage, addend, cols * sizeof(fe_t));
     SP_HIP(hipMemcpyAsync(dout + cols, stage, cols * sizeof(fe_t), hipMemcpyHostToDevice, st));
     job->d_add = dout + cols;
-    job->armed = scale_add_arm(c, st, dout, dout + cols, cols);  // waits on the stream, behind the product and the upload, for _finish_scaled's scale
+    job->armed = sp::scale_add_arm(c, st, dout, dout + cols, cols);  // waits on the stream, behind the product and the upload, for _finish_scaled's scale
   }
   *out = job;
   return SP_OK;
@@ -1938,14 +1931,13 @@ int sp_rowmat_vec_eq_begin_with(sp_ctx* c, const sp_table* poly, const uint64_t*
 static void vec_addend_wipe(sp_ctx* c, const fe_t* d_add, size_t cols, bool upload_may_be_running) {
   if (!d_add) return;
   if (upload_may_be_running) (void)sp::stream_sync(c->stream3);
-  explicit_bzero(reinterpret_cast<fe_t*>(c->h_pinned_vec) + c->h_pinned_vec_cols, cols * sizeof(fe_t));
-  (void)hipMemsetAsync(const_cast<fe_t*>(d_add), 0, cols * sizeof(fe_t), c->stream3);
+  sp::addend_wipe(c, const_cast<fe_t*>(d_add), cols, c->stream3);
 }
 int sp_rowmat_vec_eq_finish(sp_ctx* c, sp_vec_job* job, uint64_t* out) {
   if (!job || !out) return fail(SP_ERR_INVALID_INPUT_LENGTH, "sp_rowmat_vec_eq_finish: null argument");
   const size_t cols = job->cols;
   const fe_t* da = job->d_add;
-  scale_add_abort(c, job->armed);  // (a job begun with an addend and finished without its scale: the waiting kernel leaves)
+  sp::scale_add_abort(c, job->armed);  // (a job begun with an addend and finished without its scale: the waiting kernel leaves)
   delete job;
   SP_HIP(sp::event_sync(c->vec_ev));
   memcpy(out, c->h_pinned_vec, cols * sizeof(fe_t));
@@ -1962,24 +1954,14 @@ int sp_rowmat_vec_eq_finish_scaled(sp_ctx* c, sp_vec_job* job, const uint64_t sc
   fe_t sc;
   memcpy(&sc, scale, 32);
   // (unarmed: on the job's own stream, behind the product and the upload of the addend, which ended long ago)
-  const int rc = armed ? scale_add_fire(c, c->stream3, armed, dx, da, sc, cols, out, "rowmat_vec_eq_finish_scaled")
-                       : scale_add_to_host(c, c->stream3, dx, da, sc, cols, out, "rowmat_vec_eq_finish_scaled");
+  const int rc = armed ? sp::scale_add_fire(c, c->stream3, armed, dx, da, sc, cols, out, "rowmat_vec_eq_finish_scaled")
+                       : sp::scale_add_to_host(c, c->stream3, dx, da, sc, cols, out, "rowmat_vec_eq_finish_scaled");
   vec_addend_wipe(c, da, cols, rc != SP_OK);  // (the sum has arrived: the kernel that read the addend is done, and so is its upload)
   return rc;
 }
 int sp_msm_job_finish(sp_ctx* c, sp_msm_job* job, uint64_t out_aff[8]) { return sp_msm_ck_finish(c, nullptr, job, nullptr, out_aff); }
 
 // ---- FixedBaseMul tables over arbitrary points (msm.rs:653-689, 727-773) ---------------------------------------------------------------------------
-struct sp_fbtables {
-  size_t n = 0;
-  aff_t* d_tables = nullptr;  // n x 32 x 255 affine multiples
-  // sp_fbtables_create_async: the build is queued on the context's table stream; `ready_ev` is recorded behind it and `ready` remembers that it was seen
-  int device = 0;
-  hipEvent_t ready_ev = nullptr;
-  mutable std::atomic<int> ready{1};
-  aff_t* d_points = nullptr;        // the bases on the device (the build's input; freed with the tables)
-  std::vector<aff_t> h_points;      // the source of their (possibly still running) upload
-};
 // the context's table stream (lowest priority: a build runs beside whatever the context proves) and its grow-only scratch
 static int table_stream_scratch(sp_ctx* c, size_t bytes, char** scratch) {
   if (!c->stream_tab) {
@@ -2142,6 +2124,7 @@ int multi_mul_ensure(sp_ctx* c, int lane) {
 // `raw_blocks` > 0: `scalars` are that many 64-byte uniform blocks (scalar i = from_uniform of block i, reduced on the device; scalars beyond them are
 // zero up to `last`): needs the wide kernel (n >= its threshold) and `last`
 size_t multi_mul_wide_min() { return 1024; }  // scalars from which the 1024-item blocks (k_multi_mul_wide) are used
+size_t multi_mul_max_scalars() { return 4 * (size_t)spk::MULTI_MUL_MAX_BLOCKS; }
 int multi_mul_launch(sp_ctx* c, int lane, const aff_t* d_tables, const uint64_t* scalars, size_t n, unsigned* seq_out, const fe_t* d_scalars, const fe_t* last,
                      size_t raw_blocks, bool expand) {
   if (expand && (raw_blocks || d_scalars || !last || !scalars || n >= multi_mul_wide_min())) return fail(SP_ERR_INTERNAL, "multi_mul: the expanding form takes host scalars below the wide size");
@@ -2335,683 +2318,10 @@ int sp_fbtables_multi_mul(sp_ctx* c, const sp_fbtables* t, const uint64_t* scala
   return rc ? rc : sp_fbtables_multi_mul_finish(c, out_aff);
 }
 
-// ---- HyraxPCS::prove (src/provider/pcs/hyrax_pc.rs:387-478) + InnerProductArgumentLinear::prove (src/provider/pcs/ipa.rs:125-170) ----------------------
-// ONE call in the place where the reference's trait method sits, so that a caller that follows src/spartan.rs:423-437 statement by statement gets the
-// overlap below the ABI that the C++ driver used to arrange above it:
-//   * the 64-byte-per-row transcript encoding of `comm` and the Keccak blocks of absorb(b"poly_com", comm) run on the context's helper thread,
-//   * delta = <d, ck> + r_delta h (ipa.rs:147) and comm_LZ = <LZ, ck> + r_LZ h (hyrax_pc.rs:454-455) are table walks over the window tables of the
-//     whole key (ck_key_tables: one launch each, no digits / sort / buckets / host Horner) on two streams side by side; LZ = L^T poly
-//     (bind_with_delayed, :38-54) stays in device memory in front of its walk and travels to the host only for z_vec,
-//   * the host meanwhile draws d_vec from the randomness stream (the wide reductions of E::Scalar::random), forms r_LZ = <L, blind>, <R, d> (tensor
-//     form: n + sqrt(n) products) and beta.
-// Transcript order and every value are the reference's. out = delta (8) | beta (8) | z_vec (4 * cols) | z_delta (4) | z_beta (4) words.
-static void hp_point_bytes(const aff_t& a, uint8_t out[64]) {  // x BE || y BE (src/provider/traits.rs:288-305)
+// x BE || y BE (src/provider/traits.rs:288-305); the lone opening that closes every prove is capi_opening.hip
+static void hp_point_bytes(const aff_t& a, uint8_t out[64]) {
   sp::fe_to_be_bytes<B>(a.x, out);
   sp::fe_to_be_bytes<B>(a.y, out + 32);
-}
-}  // extern "C"
-// ---- PCS::prove announced ahead ----------------------------------------------------------------------------------------------------------------
-// src/spartan.rs calls PCS::prove last (:425-435), but three of its inputs exist long before: the commitment and its blinds when
-// r1cs_instance_and_witness returns (:238-245), the IPA's randomness whenever the caller draws it (the reference draws inside
-// InnerProductArgumentLinear::prove, ipa.rs:139-149: independent of everything), and the ROW half of the evaluation point when the inner sum-check has
-// drawn it — rounds before its end. A caller (the shim's r1cs_instance_and_witness wrapper; prove_reference_order here) that announces the opening
-// lets the library start under the sum-checks what sp_hyrax_prove would otherwise start behind them: the commitment's transcript encoding and its
-// Keccak blocks + the mask vector's wide reductions (helper thread), delta's table walk (auxiliary stream, at once), and — when sp_sumcheck_quad on the
-// same context reports the row challenges — L^T W and comm_LZ's walk. sp_hyrax_prove checks that what it is given is what was announced and then only
-// collects; anything that does not match is dropped and computed as before. No protocol value changes: same group elements, same transcript bytes.
-struct sp_pcs_ahead {
-  const sp_ck* ck = nullptr;
-  const sp_table* poly = nullptr;
-  size_t n = 0, npt = 0, nvr = 0, cols = 0, num_rows = 0;
-  std::vector<aff_t> comm;
-  std::vector<fe_t> blind, dvec, row_pt;
-  std::vector<uint8_t> rng;
-  fe_t r_delta;
-  sp::Keccak256State hashed;  // "poly_com" || commitment bytes hashed into a fresh sponge (valid when the transcript is fresh at the absorb: checked)
-  bool worker_busy = false, delta_launched = false, delta_collected = false;
-  // written by the helper thread's jobs (the launches behind the last row challenge, the announcement's own job) and read by the sum-check's thread between
-  // its rounds without waiting for the worker: atomics, sequentially consistent - these are a handful of accesses per prove
-  std::atomic<bool> lz_launched{false}, failed{false};
-  // <R, d> (ipa.rs:148) with R = eq(point[nvr..]) = left (x) right: T[b] = sum_a left[a] d[a * nright + b] once the first half of R's variables is drawn
-  // col_pt collects the column challenges as they arrive; col_pt_T is the snapshot T was built from (frozen when the job is submitted): sp_hyrax_prove
-  // compares ITS point with col_pt_T, so a later sum-check of the same length on this context — which overwrites col_pt — cannot make a stale T pass
-  std::vector<fe_t> col_pt, col_pt_T, T;
-  size_t hb = 0;
-  bool T_submitted = false, T_ready = false;
-  unsigned seq_delta = 0, seq_lz = 0;
-  jac_t delta_j;
-  fe_t r_LZ;
-  // r_LZ = <eq(r_rows, .), blinds> is the blinds' multilinear extension at r_rows: the vector is folded by its top variable with every row challenge
-  // (2^(nvr-k) products behind challenge k, under the device's next round), so that the last challenge leaves one product (hyrax_pc.rs:446-455)
-  std::vector<fe_t> bfold;
-  size_t rows_folded = 0;
-  // With FixedBaseMul tables of the first `nfixed` commitment rows and of h (sp_hyrax_prove_announce_tables; the other rows are blind_i h by the caller's
-  // word) comm_LZ = sum_{i < nfixed} L_i comm[i] + (sum_{i >= nfixed} L_i blind_i) h is ONE walk over those tables that needs L alone, not L^T W: it goes
-  // out right behind the last row challenge instead of behind the 17-50 us matrix-vector product. eq(r_rows, .) is expanded a level per challenge
-  // (P, new variable = index LSB, eq.rs:66-76); zfold = the zero rows' blinds folded like bfold gives h's scalar.
-  const aff_t* row_tables = nullptr;
-  size_t nfixed = 0;
-  std::vector<fe_t> P, zfold, zfold_prev;
-  bool lz_submitted = false;  // the launches behind the last row challenge are a job of the helper thread (the sum-check's thread goes on with its rounds)
-  // z_vec = r LZ + d on the device (ipa.rs:160-163): the mask vector is uploaded behind delta's walk, the scaled sum lands in mapped memory
-  fe_t* d_out = nullptr;      // [LZ (num_cols) | - | d (cols)] in the auxiliary lane's WS_ROWMAT_OUT
-  std::atomic<bool> dvec_uploaded{false};
-  std::atomic<unsigned> z_armed{0};      // sequence number of the k_scale_add_wait queued behind L^T W (0: none), released by sp_hyrax_prove's challenge or aborted
-  bool z_fired = false;
-};
-namespace sp {
-static void pcs_ahead_drain(sp_ctx* c) {  // no device job of a dropped announcement may outlive it (its mapped result slot is reused)
-  sp_pcs_ahead* S = c->pcs_ahead;
-  if (!S) return;
-  if (S->worker_busy && c->pcs_worker) c->pcs_worker->wait();
-  if (S->z_armed && !S->z_fired) {
-    scale_add_abort(c, S->z_armed);
-    S->z_fired = true;
-  }
-  jac_t sink;
-  if (S->delta_launched && !S->delta_collected) (void)multi_mul_collect(c, 1, S->seq_delta, &sink, false);
-  if (S->lz_launched) {
-    (void)multi_mul_collect(c, 1, S->seq_lz, &sink, false);
-    if (c->pcs_ev) (void)event_sync(c->pcs_ev);
-  }
-}
-bool pcs_ahead_wants(const sp_ctx* c, size_t rounds) { return c->pcs_ahead && !c->pcs_ahead->failed && rounds == c->pcs_ahead->npt + 1; }
-// The announcement holds zero-knowledge material for the span of both sum-checks (the commitment's blinds, the IPA's randomness blocks and the mask
-// vector drawn from them, the partial sums of <R, d>, r_delta, r_LZ): wiped before the memory goes back to the allocator.
-template <class T>
-static void wipe_vec(std::vector<T>& v) {
-  if (!v.empty()) explicit_bzero(v.data(), v.size() * sizeof(T));
-}
-void pcs_ahead_free(sp_ctx* c) {
-  if (!c || !c->pcs_ahead) return;
-  pcs_ahead_drain(c);
-  sp_pcs_ahead* S = c->pcs_ahead;
-  c->pcs_ahead = nullptr;
-  if (S->dvec_uploaded && S->d_out && c->h_pinned_vec) {
-    // a dropped or retracted announcement had staged the mask vector (pinned block) and uploaded it (auxiliary stream): neither copy outlives it.
-    // (a consumed one has wiped both already - sp_hyrax_prove - and wiping zeros again costs a 64 KiB memset off everybody's path)
-    (void)sp::stream_sync(c->stream2);
-    explicit_bzero(reinterpret_cast<fe_t*>(c->h_pinned_vec) + c->h_pinned_vec_cols, S->cols * sizeof(fe_t));
-    (void)hipMemsetAsync(S->d_out + S->ck->num_cols + 1, 0, S->cols * sizeof(fe_t), c->stream2);
-  }
-  auto wipe = [S] {
-    wipe_vec(S->blind);
-    wipe_vec(S->dvec);
-    wipe_vec(S->rng);
-    wipe_vec(S->T);
-    wipe_vec(S->bfold);
-    wipe_vec(S->zfold);
-    wipe_vec(S->zfold_prev);
-    explicit_bzero(&S->r_delta, sizeof(fe_t));
-    explicit_bzero(&S->r_LZ, sizeof(fe_t));
-    delete S;
-  };
-  // ~250 KB at config 2: 15-20 us of stores, on the context's helper thread when there is one (nothing else of the announcement is alive: drained above)
-  if (c->pcs_worker) c->pcs_worker->submit(wipe);
-  else wipe();
-}
-// the inner sum-check's challenges: round 0 binds the variable that separates W from (1, X); rounds 1 .. nvr are the opening's row variables
-void pcs_ahead_on_challenge(void* ctx, size_t round, const uint64_t r[4]) {
-  sp_ctx* c = (sp_ctx*)ctx;
-  sp_pcs_ahead* S = c->pcs_ahead;
-  if (!S || S->failed || S->nvr == 0 || round == 0) return;
-  if (round > S->nvr) {  // a column variable: after the first half of them the helper thread forms the partial sums of <R, d>
-    const size_t k = round - S->nvr - 1;
-    if (k < S->hb) memcpy(&S->col_pt[k], r, 32);
-    if (k + 1 == S->hb && !S->T_submitted) {
-      if (S->worker_busy) c->pcs_worker->wait();
-      S->worker_busy = true;
-      S->T_submitted = true;
-      S->col_pt_T = S->col_pt;
-      c->pcs_worker->submit([S] {
-        const size_t nleft = (size_t)1 << S->hb, nright = S->cols >> S->hb;
-        std::vector<fe_t> left(nleft);
-        eq_table_host(S->col_pt_T.data(), S->hb, left.data());
-        S->T.assign(nright, fe_zero());
-        for (size_t a = 0; a < nleft; ++a)
-          for (size_t b = 0; b < nright; ++b) S->T[b] = fe_add<spk::SF>(S->T[b], fe_mul<spk::SF>(left[a], S->dvec[a * nright + b]));
-        S->T_ready = true;
-      });
-    }
-    return;
-  }
-  if (S->lz_submitted || S->lz_launched) return;  // (lz_submitted first: while it is false no helper job is writing lz_launched)
-  if (round != S->rows_folded + 1) {  // (challenges arrive in order, once each; anything else and the plain call computes everything itself)
-    S->failed = true;
-    return;
-  }
-  memcpy(&S->row_pt[round - 1], r, 32);
-  if (round == 1 && c->pcs_worker) c->pcs_worker->keep_hot(700);  // the jobs below and the opening's own are claimed without a wake-up
-  {
-    const fe_t rk = S->row_pt[round - 1];
-    const size_t h = S->bfold.size() / 2;
-    for (size_t j = 0; j < h; ++j) S->bfold[j] = fe_add<spk::SF>(S->bfold[j], fe_mul<spk::SF>(rk, fe_sub<spk::SF>(S->bfold[j + h], S->bfold[j])));
-    explicit_bzero(S->bfold.data() + h, h * sizeof(fe_t));
-    S->bfold.resize(h);
-    S->rows_folded = round;
-    if (S->row_tables) {
-      if (h == 1) S->zfold_prev = S->zfold;  // (S0, S1): h's scalar is S0 + r (S1 - S0), which the walk's kernel can form itself
-      for (size_t j = 0; j < h; ++j) S->zfold[j] = fe_add<spk::SF>(S->zfold[j], fe_mul<spk::SF>(rk, fe_sub<spk::SF>(S->zfold[j + h], S->zfold[j])));
-      explicit_bzero(S->zfold.data() + h, h * sizeof(fe_t));
-      S->zfold.resize(h);
-      if (round < S->nvr) {  // (the last level is the helper job's: 2^(nvr-1) products)
-        std::vector<fe_t> Q(2 * S->P.size());
-        for (size_t i = 0; i < S->P.size(); ++i) {
-          const fe_t hi = fe_mul<spk::SF>(S->P[i], rk);
-          Q[2 * i + 1] = hi;
-          Q[2 * i] = fe_sub<spk::SF>(S->P[i], hi);
-        }
-        S->P.swap(Q);
-      }
-    }
-  }
-  if (round != S->nvr) return;
-  S->r_LZ = S->bfold[0];
-  if (S->worker_busy) {  // the announcement's helper job (it launched delta's walk on this lane)
-    c->pcs_worker->wait();
-    S->worker_busy = false;
-  }
-  if (S->failed || S->nvr > 10) {
-    S->failed = true;
-    return;
-  }
-  // Behind the last row challenge: delta's walk has had the whole outer sum-check and is collected (its lane's result slot is needed again), then L^T W and
-  // comm_LZ's walk go out on the same lane - half a dozen runtime calls, ~20 us, on the helper thread: this thread's next round is not held up by them.
-  S->lz_submitted = true;
-  S->worker_busy = true;
-  c->pcs_worker->submit([S, c] {
-    if (hipSetDevice(c->device) != hipSuccess) {
-      S->failed = true;
-      return;
-    }
-    if (S->delta_launched && !S->delta_collected) {
-      if (multi_mul_collect(c, 1, S->seq_delta, &S->delta_j, false)) {
-        S->failed = true;
-        return;
-      }
-      S->delta_collected = true;
-    }
-    const size_t num_rows = S->num_rows, cols = S->cols, num_cols = S->ck->num_cols, nvr = S->nvr;
-    const size_t splits = num_rows < 64 ? num_rows : 64;
-    fe_t* dL = (fe_t*)c->workspace(sp_ctx::WS_ROWMAT_L, num_rows * sizeof(fe_t), 1);
-    fe_t* part = (fe_t*)c->workspace(sp_ctx::WS_ROWMAT_PART, splits * cols * sizeof(fe_t), 1);
-    fe_t* dout = (fe_t*)c->workspace(sp_ctx::WS_ROWMAT_OUT, (num_cols + 1 + cols) * sizeof(fe_t), 1);
-    if (!dL || !part || !dout || dout != S->d_out) {  // (sized by the announcement: a buffer that moved since would have lost the uploaded mask)
-      S->failed = true;
-      return;
-    }
-    hipStream_t st = c->stream2;
-    bool walk_out = false;
-    if (S->row_tables) {  // comm_LZ from the rows' own tables: the walk first, L^T W (needed for z_vec only) behind it
-      const fe_t rl = S->row_pt[nvr - 1];
-      int mrc;
-      if (S->nfixed + 1 < multi_mul_wide_min() && S->zfold_prev.size() == 2) {  // the last level of eq(r_rows, .) on the device (k_multi_mul_coop EXPAND)
-        const size_t np = (S->nfixed + 1) / 2;
-        std::vector<fe_t> buf(np + 2);
-        memcpy(buf.data(), S->P.data(), np * sizeof(fe_t));
-        buf[np] = S->zfold_prev[0];
-        buf[np + 1] = S->zfold_prev[1];
-        mrc = multi_mul_launch(c, 1, S->row_tables, reinterpret_cast<const uint64_t*>(buf.data()), S->nfixed + 1, &S->seq_lz, nullptr, &rl, 0, true);
-        wipe_vec(buf);
-      } else {
-        std::vector<fe_t> sc(S->nfixed + 1);
-        for (size_t h2 = 0; h2 < S->P.size(); ++h2) {
-          const fe_t hi = fe_mul<spk::SF>(S->P[h2], rl), lo = fe_sub<spk::SF>(S->P[h2], hi);
-          if (2 * h2 < S->nfixed) sc[2 * h2] = lo;
-          if (2 * h2 + 1 < S->nfixed) sc[2 * h2 + 1] = hi;
-        }
-        sc[S->nfixed] = S->zfold[0];
-        mrc = multi_mul_launch(c, 1, S->row_tables, reinterpret_cast<const uint64_t*>(sc.data()), S->nfixed + 1, &S->seq_lz, nullptr, nullptr, 0);
-        wipe_vec(sc);
-      }
-      if (mrc) {
-        S->failed = true;
-        return;
-      }
-      walk_out = true;
-    }
-    spk::EqTensorArgs a;
-    const size_t hb = nvr / 2, lb = nvr - hb;
-    eq_table_host(S->row_pt.data(), hb, a.left);
-    eq_table_host(S->row_pt.data() + hb, lb, a.right);
-    a.lo_bits = (int)lb;
-    a.n = (unsigned)num_rows;
-    hipLaunchKernelGGL(spk::k_eq_tensor<false>, dim3((unsigned)((num_rows + 255) / 256)), dim3(256), 0, st, a, dL);
-    if (cols < num_cols && hipMemsetAsync(dout + cols, 0, (num_cols - cols) * sizeof(fe_t), st) != hipSuccess) {
-      S->failed = true;
-      S->lz_launched = walk_out;  // (still drained)
-      return;
-    }
-    c->timed_on(st, "rowmat_vec", 32ull * (num_rows * cols + num_rows + cols), [&] { launch_rowmat_vec(st, S->poly->d, num_rows, cols, dL, part, splits, dout); });
-    if ((!walk_out && multi_mul_launch(c, 1, S->ck->d_keytables, nullptr, num_cols + 1, &S->seq_lz, dout, &S->r_LZ, 0)) || hipEventRecord(c->pcs_ev, st) != hipSuccess) {
-      S->failed = true;  // (a launched walk is still drained by pcs_ahead_drain: lz_launched stays false only if the launch itself failed)
-      S->lz_launched = walk_out;
-      return;
-    }
-    // z_vec's kernel waits for the IPA's challenge on the second auxiliary stream, behind this one's work so far. That stream is non-blocking: a waiting
-    // kernel on a blocking stream would hold up every legacy default-stream operation of the process (a synchronous hipMemcpy between the sum-check and
-    // the opening) until its watchdog.
-    if (S->dvec_uploaded && c->stream3 && hipStreamWaitEvent(c->stream3, c->pcs_ev, 0) == hipSuccess)
-      S->z_armed = scale_add_arm(c, c->stream3, dout, dout + num_cols + 1, cols);
-    S->lz_launched = true;
-  });
-}
-}  // namespace sp
-
-extern "C" int sp_hyrax_prove_retract(sp_ctx* c) {
-  if (!c) return fail(SP_ERR_INVALID_INPUT_LENGTH, "sp_hyrax_prove_retract: null context");
-  sp::pcs_ahead_free(c);
-  return SP_OK;
-}
-static int announce_impl(sp_ctx* c, const sp_ck* ck, const uint64_t* comm_rows_aff, size_t rows, const sp_table* poly, size_t n, const uint64_t* blinds, const uint8_t* rng,
-                         size_t rng_blocks, const sp_fbtables* row_tables, size_t nfixed);
-extern "C" int sp_hyrax_prove_announce(sp_ctx* c, const sp_ck* ck, const uint64_t* comm_rows_aff, size_t rows, const sp_table* poly, size_t n, const uint64_t* blinds,
-                                       const uint8_t* rng, size_t rng_blocks) {
-  return announce_impl(c, ck, comm_rows_aff, rows, poly, n, blinds, rng, rng_blocks, nullptr, 0);
-}
-extern "C" int sp_hyrax_prove_announce_tables(sp_ctx* c, const sp_ck* ck, const uint64_t* comm_rows_aff, size_t rows, const sp_table* poly, size_t n, const uint64_t* blinds,
-                                              const uint8_t* rng, size_t rng_blocks, const sp_fbtables* row_tables, size_t nfixed) {
-  if (!row_tables || row_tables->n != nfixed + 1 || nfixed > rows)
-    return fail(SP_ERR_INVALID_INPUT_LENGTH, "sp_hyrax_prove_announce_tables: one table per fixed row and one of h");
-  return announce_impl(c, ck, comm_rows_aff, rows, poly, n, blinds, rng, rng_blocks, row_tables, nfixed);
-}
-static int announce_impl(sp_ctx* c, const sp_ck* ck, const uint64_t* comm_rows_aff, size_t rows, const sp_table* poly, size_t n, const uint64_t* blinds, const uint8_t* rng,
-                         size_t rng_blocks, const sp_fbtables* row_tables, size_t nfixed) {
-  if (!c || !ck || !comm_rows_aff || !poly || !blinds || !rng) return fail(SP_ERR_INVALID_INPUT_LENGTH, "sp_hyrax_prove_announce: null argument");
-  sp::pcs_ahead_free(c);  // at most one announcement per context; an unconsumed one is dropped
-  size_t npt = 0;
-  while (((size_t)1 << npt) < n) ++npt;
-  const size_t num_cols = ck->num_cols, num_rows = (n + num_cols - 1) / num_cols;
-  if (n != ((size_t)1 << npt) || n > poly->cap || rows != num_rows || (num_rows & (num_rows - 1)) || num_rows < 2) return SP_OK;  // nothing to start ahead: the plain call decides
-  size_t nvr = 0;
-  while (((size_t)1 << nvr) < num_rows) ++nvr;
-  const size_t cols = n / num_rows;
-  if (rng_blocks < cols + 2 || nvr > 10) return SP_OK;
-  SP_HIP(hipSetDevice(c->device));
-  if (sp::ck_key_tables(c, ck) != 0) return SP_OK;  // no window tables of the key: the bucket MSMs have nothing to gain from an early start of this kind
-  const bool delta_raw = num_cols + 1 >= sp::multi_mul_wide_min() && 64 * num_cols <= 4 * (size_t)spk::MULTI_MUL_MAX_BLOCKS * sizeof(fe_t);
-  if (!delta_raw) return SP_OK;
-  if (!c->pcs_ev) SP_HIP(hipEventCreateWithFlags(&c->pcs_ev, hipEventDisableTiming));
-  if (c->h_pcs_bytes < cols * sizeof(fe_t)) {
-    if (c->h_pcs) hipHostFree(c->h_pcs);
-    c->h_pcs = nullptr;
-    c->h_pcs_bytes = 0;
-    SP_HIP(hipHostMalloc(&c->h_pcs, cols * sizeof(fe_t)));
-    c->h_pcs_bytes = cols * sizeof(fe_t);
-  }
-  sp_pcs_ahead* S = new sp_pcs_ahead();
-  S->ck = ck;
-  S->poly = poly;
-  S->n = n, S->npt = npt, S->nvr = nvr, S->cols = cols, S->num_rows = num_rows;
-  S->comm.assign(reinterpret_cast<const aff_t*>(comm_rows_aff), reinterpret_cast<const aff_t*>(comm_rows_aff) + rows);
-  S->blind.assign(reinterpret_cast<const fe_t*>(blinds), reinterpret_cast<const fe_t*>(blinds) + rows);
-  S->rng.assign(rng, rng + 64 * (cols + 2));
-  S->row_pt.resize(nvr);
-  S->hb = (npt - nvr) / 2;
-  S->col_pt.resize(S->hb ? S->hb : 1);
-  S->dvec.resize(cols);
-  S->r_delta = fe_from_uniform<spk::SF>(S->rng.data() + 64 * cols);
-  S->bfold = S->blind;
-  // (tables still being built - sp_fbtables_create_async a moment ago - are not waited for: this opening takes the walk over the key instead)
-  if (row_tables && nfixed >= 1 && nfixed + 1 <= 4 * (size_t)spk::MULTI_MUL_MAX_BLOCKS && sp_fbtables_ready(row_tables, 0) == 1) {
-    S->row_tables = row_tables->d_tables;
-    S->nfixed = nfixed;
-    S->zfold = S->blind;
-    for (size_t i = 0; i < nfixed; ++i) S->zfold[i] = fe_zero();
-    S->P.assign(1, fe_one<spk::SF>());
-  }
-  {  // the buffers of the launches behind the last row challenge and of z_vec, sized here: the helper thread's workspace() calls are then plain look-ups
-    const size_t splits = num_rows < 64 ? num_rows : 64;
-    int rc_pin = ensure_pinned_vec(c, cols);
-    fe_t* dL = (fe_t*)c->workspace(sp_ctx::WS_ROWMAT_L, num_rows * sizeof(fe_t), 1);
-    fe_t* part = (fe_t*)c->workspace(sp_ctx::WS_ROWMAT_PART, splits * cols * sizeof(fe_t), 1);
-    S->d_out = (fe_t*)c->workspace(sp_ctx::WS_ROWMAT_OUT, (num_cols + 1 + cols) * sizeof(fe_t), 1);
-    if (rc_pin || !dL || !part || !S->d_out) {
-      delete S;
-      return SP_OK;  // the plain call will report what is wrong
-    }
-  }
-  c->pcs_ahead = S;
-  // helper thread: the commitment's transcript bytes into a fresh sponge, then the mask vector's wide reductions
-  if (!c->pcs_worker) c->pcs_worker = new sp::Worker();
-  S->worker_busy = true;
-  c->pcs_worker->submit([S, c, num_cols] {
-    // delta = <d, ck> + r_delta h first: its walk (auxiliary stream) reduces the randomness blocks itself
-    if (hipSetDevice(c->device) != hipSuccess ||
-        sp::multi_mul_launch(c, 1, S->ck->d_keytables, reinterpret_cast<const uint64_t*>(S->rng.data()), num_cols + 1, &S->seq_delta, nullptr, &S->r_delta, S->cols))
-      S->failed = true;
-    else
-      S->delta_launched = true;
-    S->hashed.init();
-    sp::absorb_commitment(S->hashed, S->comm.data(), S->comm.size());
-    for (size_t i = 0; i < S->cols; ++i) S->dvec[i] = fe_from_uniform<spk::SF>(S->rng.data() + 64 * i);
-    // the mask vector to the device, behind delta's walk on the auxiliary stream (needed when the IPA's challenge is drawn: z_vec = r LZ + d)
-    fe_t* stage = reinterpret_cast<fe_t*>(c->h_pinned_vec) + c->h_pinned_vec_cols;
-    memcpy(stage, S->dvec.data(), S->cols * sizeof(fe_t));
-    if (!S->failed && hipMemcpyAsync(S->d_out + num_cols + 1, stage, S->cols * sizeof(fe_t), hipMemcpyHostToDevice, c->stream2) == hipSuccess) S->dvec_uploaded = true;
-  });
-  return SP_OK;
-}
-extern "C" {
-
-int sp_hyrax_prove(sp_ctx* c, const sp_ck* ck, const sp_ck* ck_eval, sp_transcript* tr, const uint64_t* comm_rows_aff, size_t rows, const sp_table* poly, size_t n,
-                   const uint64_t* blinds, const uint64_t* point, size_t npt, const uint64_t comm_eval_aff[8], const uint64_t blind_eval[4], const uint8_t* rng,
-                   size_t rng_blocks, uint64_t* out) {
-  typedef spk::SF SF;
-  if (!c || !ck || !ck_eval || !tr || !comm_rows_aff || !poly || !blinds || (!point && npt) || !comm_eval_aff || !blind_eval || !rng || !out)
-    return fail(SP_ERR_INVALID_INPUT_LENGTH, "sp_hyrax_prove: null argument");
-  if (npt > 40 || n != ((size_t)1 << npt) || n > poly->cap)
-    return fail(SP_ERR_INVALID_INPUT_LENGTH, "Hyrax prove: Expected 2^point.len() elements in poly");  // hyrax_pc.rs:400-408
-  const size_t num_cols = ck->num_cols, num_rows = (n + num_cols - 1) / num_cols;
-  if (num_rows & (num_rows - 1)) return fail(SP_ERR_INVALID_INPUT_LENGTH, "Hyrax prove: the row count must be a power of two");
-  if (rows != num_rows) return fail(SP_ERR_INVALID_INPUT_LENGTH, "Hyrax prove: one commitment row and one blind per matrix row");
-  size_t nvr = 0;
-  while (((size_t)1 << nvr) < num_rows) ++nvr;
-  const size_t cols = n / num_rows;  // |R| = |LZ| = |d|
-  if (!ck_eval->d_cktables || ck_eval->num_cols < 1) return fail(SP_ERR_INVALID_INPUT_LENGTH, "Hyrax prove: ck_eval must be a narrow key with tables");
-  SP_HIP(hipSetDevice(c->device));
-  static const bool laps = getenv("SPARTAN_HOST_LAPS") != nullptr;
-  auto now_us = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  double t_lap = laps ? now_us() : 0;
-  auto lap = [&](const char* what) {
-    if (!laps) return;
-    const double t = now_us();
-    fprintf(stderr, "  hyrax_prove lap %-24s %8.1f us\n", what, t - t_lap);
-    t_lap = t;
-  };
-  const aff_t* comm = reinterpret_cast<const aff_t*>(comm_rows_aff);
-  const fe_t* blind = reinterpret_cast<const fe_t*>(blinds);
-  const fe_t* pt = reinterpret_cast<const fe_t*>(point);
-  if (rng_blocks < cols + 2) return fail(SP_ERR_INVALID_INPUT_LENGTH, "Hyrax prove: the randomness stream holds fewer than cols + 2 blocks");
-  // E::Scalar::random draws (ipa.rs:139-149): d_vec, then the blinds of delta and beta, each the wide reduction of 64 uniform bytes. The two blinds
-  // now, the mask vector further down while the device already works on LZ.
-  std::vector<fe_t> dvec_own;
-  const fe_t r_delta = fe_from_uniform<SF>(rng + 64 * cols), r_beta = fe_from_uniform<SF>(rng + 64 * (cols + 1));
-  fe_t b_eval;
-  memcpy(&b_eval, blind_eval, 32);
-  aff_t comm_eval;
-  memcpy(&comm_eval, comm_eval_aff, sizeof(aff_t));
-
-  // (0) was this opening announced (sp_hyrax_prove_announce)? Then its commitment hashing, mask vector, delta and — if the inner sum-check reported the row
-  // challenges — L^T W and comm_LZ are done or under way; anything that differs from what was announced drops the announcement.
-  sp_pcs_ahead* S = c->pcs_ahead;
-  bool ahead = S && !S->failed && S->ck == ck && S->poly == poly && S->n == n && S->comm.size() == rows && memcmp(S->comm.data(), comm, rows * sizeof(aff_t)) == 0 &&
-               memcmp(S->blind.data(), blind, rows * sizeof(fe_t)) == 0 && memcmp(S->rng.data(), rng, 64 * (cols + 2)) == 0;
-  if (S && !ahead) {
-    sp::pcs_ahead_free(c);
-    S = nullptr;
-  }
-  struct AheadDone {  // consumed or not, the announcement ends with this call
-    sp_ctx* c;
-    ~AheadDone() { sp::pcs_ahead_free(c); }
-  } ahead_done{c};
-  // (1) helper thread: transcript.absorb(b"poly_com", comm) (hyrax_pc.rs:410) into a copy of the running hasher, installed at the join below
-  tr->join();
-  if (!c->pcs_worker) c->pcs_worker = new sp::Worker();
-  sp::Keccak256State hashed = tr->t.h;
-  bool hashed_ahead = false;
-  if (ahead) {  // the announced hashing started from a fresh sponge: usable exactly when nothing has been absorbed since the last squeeze
-    c->pcs_worker->wait();
-    S->worker_busy = false;
-    if (S->failed || !S->delta_launched) {  // the helper could not launch delta's walk: as if nothing had been announced
-      sp::pcs_ahead_free(c);
-      S = nullptr;
-      ahead = false;
-    }
-  }
-  if (ahead) {
-    bool fresh = tr->t.h.fill == 0;
-    for (int i = 0; i < 25 && fresh; ++i) fresh = tr->t.h.a[i] == 0;
-    if (fresh) {
-      hashed = S->hashed;
-      hashed_ahead = true;
-    }
-  }
-  if (!hashed_ahead) {
-    sp::Keccak256State* hp = &hashed;
-    c->pcs_worker->submit([hp, comm, rows] { sp::absorb_commitment(*hp, comm, rows); });
-  }
-  // beta = ck_c <R, d> + h r_beta (ipa.rs:149) is two table walks on the host, ~11 us each. With the helper thread polling (an announced opening keeps it
-  // so) and not busy with the commitment's hashing, h's walk runs beside this thread's compare / <R, d> and ck_c's beside its collection of the two device
-  // walks; otherwise both are this thread's (sp_hyrax_commit_small). The jobs write here: declared in front of `join`, which waits on every exit path.
-  jac_t beta_h = jac_identity(), beta_c = jac_identity();
-  const bool beta_beside = hashed_ahead && ck_eval->n_tables >= 2 && ck_eval->num_cols >= 1 && c->pcs_worker->hot();
-  struct Join {  // the hashing job reads `comm` and writes `hashed`: it must have finished on every exit path (not so the z_vec helper job further down)
-    sp::Worker* w;
-    bool joined = false;
-    ~Join() {
-      if (!joined) w->wait();
-    }
-  } join{c->pcs_worker};
-
-  if (beta_beside) {
-    jac_t* dst = &beta_h;
-    const fe_t rb = r_beta;
-    c->pcs_worker->submit([ck_eval, dst, rb] { *dst = ck_mul_host(ck_eval, ck_eval->n_tables - 1, rb); });
-  }
-  lap("submit hashing");
-  // (2) device: delta's walk on the auxiliary stream, LZ and comm_LZ's walk on the main stream
-  const int kt = (nvr == 0 && cols > num_cols) ? 1 : sp::ck_key_tables(c, ck);
-  if (kt < 0) return kt;
-  const bool walk = kt == 0;
-  std::vector<fe_t> LZ;
-  fe_t r_LZ;
-  aff_t comm_LZ, delta;
-  unsigned seq_delta = 0, seq_lz = 0;
-  sp_msm_job* delta_job = nullptr;
-  struct JobGuard {  // an error exit must not leave the asynchronous MSM of the fallback path outstanding
-    sp_ctx* c;
-    sp_msm_job*& j;
-    ~JobGuard() {
-      uint64_t sink[8];
-      if (j) sp_msm_job_finish(c, j, sink);
-      j = nullptr;
-    }
-  } job_guard{c, delta_job};
-  int rc;
-  // delta = <d, ck> + r_delta h first: it needs nothing but the randomness stream, whose blocks the kernel reduces itself
-  const bool delta_raw = walk && num_cols + 1 >= sp::multi_mul_wide_min() && 64 * num_cols <= 4 * (size_t)spk::MULTI_MUL_MAX_BLOCKS * sizeof(fe_t);
-  if (ahead && !walk) {  // (cannot happen: the announcement needs the key's window tables)
-    sp::pcs_ahead_free(c);
-    S = nullptr;
-    ahead = false;
-  }
-  if (ahead) seq_delta = S->seq_delta;
-  else if (delta_raw && (rc = sp::multi_mul_launch(c, 1, ck->d_keytables, reinterpret_cast<const uint64_t*>(rng), num_cols + 1, &seq_delta, nullptr, &r_delta, cols))) return rc;
-  lap("delta launch");
-  std::vector<fe_t> L;
-  bool lz_ahead = false;
-  if (nvr == 0) {  // a single row: the commitment is the row itself (hyrax_pc.rs:417-423)
-    comm_LZ = comm[0];
-    LZ.resize(cols);
-    if ((rc = sp_table_read(c, poly, 0, n, reinterpret_cast<uint64_t*>(LZ.data())))) return rc;
-    r_LZ = blind[0];
-  } else if (ahead && S->lz_launched && memcmp(S->row_pt.data(), pt, nvr * sizeof(fe_t)) == 0) {
-    lz_ahead = true;  // L^T W and comm_LZ's walk have been running on the auxiliary stream since the inner sum-check drew the row challenges
-    r_LZ = S->r_LZ;
-    seq_lz = S->seq_lz;
-  } else {
-    L.resize((size_t)1 << nvr);
-    eq_table_host(pt, nvr, L.data());
-    LZ.resize(cols);
-    if (ahead && S->lz_launched) {  // started for other row challenges than the point given now: drain it, its lane is needed
-      if (S->z_armed && !S->z_fired) {
-        scale_add_abort(c, S->z_armed);
-        S->z_fired = true;
-      }
-      jac_t sink;
-      (void)sp::multi_mul_collect(c, 1, S->seq_lz, &sink, false);
-      (void)sp::event_sync(c->pcs_ev);
-      S->lz_launched = false;
-    }
-    r_LZ = fe_zero();
-    for (size_t i = 0; i < num_rows; ++i) r_LZ = fe_add<SF>(r_LZ, fe_mul<SF>(L[i], blind[i]));
-    if (walk) {
-      if (!c->pcs_ev) SP_HIP(hipEventCreateWithFlags(&c->pcs_ev, hipEventDisableTiming));
-      if (c->h_pcs_bytes < cols * sizeof(fe_t)) {
-        if (c->h_pcs) hipHostFree(c->h_pcs);
-        c->h_pcs = nullptr;
-        c->h_pcs_bytes = 0;
-        SP_HIP(hipHostMalloc(&c->h_pcs, cols * sizeof(fe_t)));
-        c->h_pcs_bytes = cols * sizeof(fe_t);
-      }
-      const size_t splits = num_rows < 64 ? num_rows : 64;
-      fe_t* dL = (fe_t*)c->workspace(sp_ctx::WS_ROWMAT_L, num_rows * sizeof(fe_t));
-      fe_t* part = (fe_t*)c->workspace(sp_ctx::WS_ROWMAT_PART, splits * cols * sizeof(fe_t));
-      fe_t* dout = (fe_t*)c->workspace(sp_ctx::WS_ROWMAT_OUT, (num_cols + 1) * sizeof(fe_t));
-      if (!dL || !part || !dout) return SP_ERR_NO_DEVICE;
-      if (nvr <= 10) {  // L = left (x) right from two half tables passed by value
-        spk::EqTensorArgs a;
-        const size_t hb = nvr / 2, lb = nvr - hb;
-        eq_table_host(pt, hb, a.left);
-        eq_table_host(pt + hb, lb, a.right);
-        a.lo_bits = (int)lb;
-        a.n = (unsigned)num_rows;
-        hipLaunchKernelGGL(spk::k_eq_tensor<false>, dim3((unsigned)((num_rows + 255) / 256)), dim3(256), 0, c->stream, a, dL);
-      } else {
-        SP_HIP(hipMemcpyAsync(dL, L.data(), num_rows * sizeof(fe_t), hipMemcpyHostToDevice, c->stream));  // (L outlives the stream work: joined below)
-      }
-      if (cols < num_cols) SP_HIP(hipMemsetAsync(dout + cols, 0, (num_cols - cols) * sizeof(fe_t), c->stream));
-      c->timed("rowmat_vec", 32ull * (num_rows * cols + num_rows + cols), [&] { launch_rowmat_vec(c->stream, poly->d, num_rows, cols, dL, part, splits, dout); });
-      if ((rc = sp::multi_mul_launch(c, 0, ck->d_keytables, nullptr, num_cols + 1, &seq_lz, dout, &r_LZ, 0))) return rc;
-      SP_HIP(hipMemcpyAsync(c->h_pcs, dout, cols * sizeof(fe_t), hipMemcpyDeviceToHost, c->stream));  // behind the walk: LZ is needed on the host only for z_vec
-      SP_HIP(hipEventRecord(c->pcs_ev, c->stream));
-    } else {
-      if ((rc = sp_rowmat_vec(c, poly, num_rows, cols, reinterpret_cast<const uint64_t*>(L.data()), reinterpret_cast<uint64_t*>(LZ.data())))) return rc;
-    }
-  }
-  lap("LZ + comm_LZ launch");
-  // d_vec: 2048 wide reductions at config 2, ~65 us of host work beside the device's (delta's walk reduces its own copy of the blocks)
-  if (!ahead) {  // (an announcement's helper job has drawn it)
-    dvec_own.resize(cols);
-    for (size_t i = 0; i < cols; ++i) dvec_own[i] = fe_from_uniform<SF>(rng + 64 * i);
-  }
-  const std::vector<fe_t>& dvec = ahead ? S->dvec : dvec_own;
-  lap("d_vec draw");
-  if (!walk && (rc = sp_msm_ck_begin(c, ck, reinterpret_cast<const uint64_t*>(dvec.data()), cols, &delta_job))) return rc;
-  if (walk && !delta_raw && !ahead) {  // narrow keys: the walk from the drawn scalars
-    std::vector<fe_t> sc(num_cols + 1, fe_zero());
-    memcpy(sc.data(), dvec.data(), cols * sizeof(fe_t));
-    sc[num_cols] = r_delta;
-    if ((rc = sp::multi_mul_launch(c, 1, ck->d_keytables, reinterpret_cast<const uint64_t*>(sc.data()), num_cols + 1, &seq_delta, nullptr, nullptr, 0))) return rc;
-  }
-  // (3) host work under the device's: <R, d> with R = eq(point[nvr..]) = left (x) right (ipa.rs:148), beta = ck_c * <R, d> + h_c * r_beta (:149)
-  fe_t ip = fe_zero();
-  if (ahead && S->T_ready && S->hb == (npt - nvr) / 2 && S->col_pt_T.size() >= S->hb && memcmp(S->col_pt_T.data(), pt + nvr, S->hb * sizeof(fe_t)) == 0) {
-    const size_t k = npt - nvr;
-    std::vector<fe_t> right((size_t)1 << (k - S->hb));
-    eq_table_host(pt + nvr + S->hb, k - S->hb, right.data());
-    for (size_t b2 = 0; b2 < right.size(); ++b2) ip = fe_add<SF>(ip, fe_mul<SF>(right[b2], S->T[b2]));
-  } else {
-    const size_t k = npt - nvr, hb = k / 2;
-    std::vector<fe_t> left((size_t)1 << hb), right((size_t)1 << (k - hb));
-    eq_table_host(pt + nvr, hb, left.data());
-    eq_table_host(pt + nvr + hb, k - hb, right.data());
-    for (size_t a = 0; a < left.size(); ++a) {
-      fe_t inner = fe_zero();
-      for (size_t b2 = 0; b2 < right.size(); ++b2) inner = fe_add<SF>(inner, fe_mul<SF>(right[b2], dvec[a * right.size() + b2]));
-      ip = fe_add<SF>(ip, fe_mul<SF>(left[a], inner));
-    }
-  }
-  lap("<R, d>");
-  aff_t beta;
-  if (beta_beside) {
-    c->pcs_worker->wait(1);  // h's walk (an unclaimed job is taken back and run here)
-    jac_t* dst = &beta_c;
-    const fe_t ipv = ip;
-    c->pcs_worker->submit([ck_eval, dst, ipv] { *dst = ck_mul_host(ck_eval, 0, ipv); });
-  } else if ((rc = sp_hyrax_commit_small(c, ck_eval, reinterpret_cast<const uint64_t*>(&ip), 1, reinterpret_cast<const uint64_t*>(&r_beta), reinterpret_cast<uint64_t*>(&beta)))) {
-    return rc;
-  }
-  lap("beta");
-  // (4) joins
-  if (walk) {
-    jac_t dj;
-    if (ahead && S->delta_collected) {
-      dj = S->delta_j;
-    } else {
-      if ((rc = sp::multi_mul_collect(c, 1, seq_delta, &dj, false))) return rc;
-      if (ahead) S->delta_collected = true;
-    }
-    delta = jac_to_affine(dj);
-    if (nvr != 0) {
-      jac_t lj;
-      if ((rc = sp::multi_mul_collect(c, lz_ahead ? 1 : 0, seq_lz, &lj, false))) return rc;
-      if (lz_ahead) S->lz_launched = false;
-      comm_LZ = jac_to_affine(lj);
-      if (!(lz_ahead && S->dvec_uploaded)) {  // (an announced opening forms z_vec on the device: LZ never comes to the host)
-        if (lz_ahead) {
-          LZ.resize(cols);
-          SP_HIP(hipMemcpyAsync(c->h_pcs, S->d_out, cols * sizeof(fe_t), hipMemcpyDeviceToHost, c->stream2));
-          SP_HIP(hipEventRecord(c->pcs_ev, c->stream2));
-        }
-        SP_HIP(sp::event_sync(c->pcs_ev));
-        memcpy(LZ.data(), c->h_pcs, cols * sizeof(fe_t));
-      }
-    }
-  } else {
-    if (nvr != 0 && (rc = sp_msm_ck(c, ck, reinterpret_cast<const uint64_t*>(LZ.data()), cols, reinterpret_cast<const uint64_t*>(&r_LZ), reinterpret_cast<uint64_t*>(&comm_LZ))))
-      return rc;
-    sp_msm_job* j = delta_job;
-    delta_job = nullptr;
-    if ((rc = sp_msm_ck_finish(c, ck, j, reinterpret_cast<const uint64_t*>(&r_delta), reinterpret_cast<uint64_t*>(&delta)))) return rc;
-  }
-  if (beta_beside) {
-    c->pcs_worker->wait(1);
-    beta = jac_to_affine(jac_add(beta_c, beta_h));
-  }
-  lap("join walks");
-  if (!hashed_ahead) c->pcs_worker->wait();
-  join.joined = true;
-  lap("join hashing");
-  tr->t.h = hashed;
-  // (5) InnerProductArgumentLinear::prove, transcript part (ipa.rs:132-158)
-  fe_t rr;
-  if (!sp::ipa_transcript(tr->t, comm_LZ, comm_eval, delta, beta, &rr)) return fail(SP_ERR_INTERNAL_TRANSCRIPT, "transcript round counter overflow");
-  // (6) z_vec = r * LZ + d, z_delta = r * r_LZ + r_delta, z_beta = r * blind_eval + r_beta (ipa.rs:160-168)
-  memcpy(out, &delta, sizeof(aff_t));
-  memcpy(out + 8, &beta, sizeof(aff_t));
-  fe_t* zv = reinterpret_cast<fe_t*>(out + 16);
-  if (lz_ahead && S->dvec_uploaded) {
-    // on the device, behind comm_LZ's walk on the auxiliary stream (collected above): one launch, the sum lands in mapped memory (2048 products on this
-    // thread and its helper were ~32 us)
-    if (S->z_armed && !S->z_fired) {
-      S->z_fired = true;
-      if ((rc = scale_add_fire(c, c->stream3, S->z_armed, S->d_out, S->d_out + num_cols + 1, rr, cols, out + 16, "hyrax_prove z_vec"))) return rc;
-    } else if ((rc = scale_add_to_host(c, c->stream2, S->d_out, S->d_out + num_cols + 1, rr, cols, out + 16, "hyrax_prove z_vec"))) {
-      return rc;
-    }
-    explicit_bzero(reinterpret_cast<fe_t*>(c->h_pinned_vec) + c->h_pinned_vec_cols, cols * sizeof(fe_t));  // the mask's staging copy
-    (void)hipMemsetAsync(S->d_out + num_cols + 1, 0, cols * sizeof(fe_t), c->stream2);                       // and its device copy
-    S->dvec_uploaded = false;  // (both copies are gone: pcs_ahead_free has nothing left to wipe)
-  } else {
-    // shared with the helper thread chunk by chunk: whoever is awake takes the next 128 elements. The owner never waits for the helper to WAKE (a sleeping
-    // thread can take milliseconds when the process is at its CPU quota), only for chunks the helper has actually claimed.
-    struct Share {
-      std::atomic<size_t> next{0}, done{0};
-    };
-    auto sh = std::make_shared<Share>();
-    const fe_t* lz = LZ.data();
-    const fe_t* dv = dvec.data();
-    constexpr size_t CH = 128;
-    const size_t nch = (cols + CH - 1) / CH;
-    auto work = [sh, zv, lz, dv, rr, cols, nch] {
-      for (;;) {
-        const size_t ci = sh->next.fetch_add(1, std::memory_order_acq_rel);
-        if (ci >= nch) return;
-        const size_t hi = (ci + 1) * CH < cols ? (ci + 1) * CH : cols;
-        for (size_t i = ci * CH; i < hi; ++i) zv[i] = fe_add<SF>(fe_mul<SF>(rr, lz[i]), dv[i]);
-        sh->done.fetch_add(1, std::memory_order_acq_rel);
-      }
-    };
-    if (nch > 2) c->pcs_worker->submit(work);
-    work();
-    while (sh->done.load(std::memory_order_acquire) < nch) sp::relax();
-  }
-  zv[cols] = fe_add<SF>(fe_mul<SF>(rr, r_LZ), r_delta);
-  zv[cols + 1] = fe_add<SF>(fe_mul<SF>(rr, b_eval), r_beta);
-  lap("transcript + z_vec");
-  return SP_OK;
 }
 
 // PCS::commit of a HOST vector on a narrow key (hyrax_pc.rs:221-260: every row a FixedBaseMul::multi_mul + h * blind), the latency form: the (row, column)
@@ -3285,6 +2595,16 @@ namespace sp {
 jac_t ck_table_mul_host(const sp_ck* ck, size_t t, const fe_t& scalar) { return ck_mul_host(ck, t, scalar); }
 void eq_evals_host(const fe_t* r, size_t k, fe_t* out) { eq_table_host(r, k, out); }
 void point_transcript_bytes(const aff_t& a, uint8_t out[64]) { hp_point_bytes(a, out); }
+// eq(pt, .) over num_rows = 2^nvr rows into dL, nvr <= 10: L = left (x) right from two half tables passed by value
+void launch_eq_rows(hipStream_t st, const fe_t* pt, size_t nvr, size_t num_rows, fe_t* dL) {
+  spk::EqTensorArgs a;
+  const size_t hb = nvr / 2, lb = nvr - hb;
+  eq_table_host(pt, hb, a.left);
+  eq_table_host(pt + hb, lb, a.right);
+  a.lo_bits = (int)lb;
+  a.n = (unsigned)num_rows;
+  hipLaunchKernelGGL(spk::k_eq_tensor<false>, dim3((unsigned)((num_rows + 255) / 256)), dim3(256), 0, st, a, dL);
+}
 void absorb_commitment(Keccak256State& h, const aff_t* comm, size_t rows) {
   static const char* b = "poly_commitment_begin";
   static const char* e = "poly_commitment_end";

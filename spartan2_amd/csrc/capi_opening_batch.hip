@@ -1,5 +1,5 @@
 // sp_hyrax_prove_batch (include/spartan_hip.h): `count` instances of HyraxPCS::prove (hyrax_pc.rs:387-478) + InnerProductArgumentLinear::prove
-// (ipa.rs:125-170) on one commitment key, opened in one pass. sp_hyrax_prove (capi_group.hip) is latency-shaped: two 65-block table walks, one L^T W,
+// (ipa.rs:125-170) on one commitment key, opened in one pass. sp_hyrax_prove (capi_opening.hip) is latency-shaped: two 65-block table walks, one L^T W,
 // ~65 us of host mask draws and a 32 KiB Keccak per opening, hidden under the sum-checks by an announcement that exists once per context. A batch has
 // no sum-check to hide under, so here every device stage is ONE plain launch for all instances (kernels_opening_batch.hpp) on the main stream:
 //   upload (blocks, instances, points) -> k_ob_mask -> copy of the <R, d> block sums, event

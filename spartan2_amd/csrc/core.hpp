@@ -40,7 +40,7 @@ hipError_t event_sync(hipEvent_t e);
 // event - these are the places a rare multi-millisecond prove comes from (a profiler serialising the streams, a result that only became visible at
 // the end of its kernel, a helper's job queued behind a waiting kernel)
 void slow_note(const char* site, long spins);
-// capi_group.hip: called by sp_sumcheck_quad after the challenge of `round` has gone to the device, when the context holds an announced opening
+// capi_opening.hip: called by sp_sumcheck_quad after the challenge of `round` has gone to the device, when the context holds an announced opening
 void pcs_ahead_on_challenge(void* ctx, size_t round, const uint64_t r[4]);
 void pcs_ahead_free(sp_ctx* c);
 bool pcs_ahead_wants(const sp_ctx* c, size_t rounds);  // is an opening announced whose point a sum-check of this many rounds draws?
@@ -242,7 +242,7 @@ struct sp_ctx {
   hipEvent_t opening_ev = nullptr;
   // a batch opened ahead (sp_hyrax_prove_batch_begin): at most one per context; it owns the WS_OPENING_* workspaces and h_opening until it is finished or dropped
   struct sp_opening_job* opening_job = nullptr;
-  // an opening announced ahead of PCS::prove (sp_hyrax_prove_announce, capi_group.hip): the inner sum-check's round loop reports its challenges to it
+  // an opening announced ahead of PCS::prove (sp_hyrax_prove_announce, capi_opening.hip): the inner sum-check's round loop reports its challenges to it
   struct sp_pcs_ahead* pcs_ahead = nullptr;
   void* h_pinned_lane[2] = {nullptr, nullptr};  // pinned landing buffers for per-window MSM sums (one per stream), 8 KiB each
   size_t pinned_elems = 0;

@@ -1,5 +1,6 @@
-// Shared by the group-side translation units of libspartan_hip.so (capi_group.hip, capi_comb.hip).
+// Shared by the group-side translation units of libspartan_hip.so (capi_group.hip, capi_comb.hip, capi_opening.hip, capi_opening_batch.hip).
 #pragma once
+#include <atomic>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -35,7 +36,7 @@ struct sp_ck {
   mutable aff_t* d_comb = nullptr;
   mutable int comb_c = 0, comb_windows = 0;
   mutable bool comb_failed = false, comb_building = false;
-  // 8-bit window tables of every base and of h (capi_group.hip ck_key_tables), built on first use by sp_hyrax_prove
+  // 8-bit window tables of every base and of h (capi_group.hip ck_key_tables), built on first use by sp_hyrax_prove (capi_opening.hip)
   mutable aff_t* d_keytables = nullptr;
   mutable bool keytables_failed = false, keytables_building = false;
   // The two lazily built table sets above are written through a `const sp_ck*` that several contexts / helper threads may share. lazy_mu guards the
@@ -45,6 +46,17 @@ struct sp_ck {
   mutable std::mutex lazy_mu;
 };
 
+// FixedBaseMul tables over arbitrary points (capi_group.hip sp_fbtables_*; an announced opening walks the tables of its commitment rows)
+struct sp_fbtables {
+  size_t n = 0;
+  aff_t* d_tables = nullptr;  // n x 32 x 255 affine multiples
+  // sp_fbtables_create_async: the build is queued on the context's table stream; `ready_ev` is recorded behind it and `ready` remembers that it was seen
+  int device = 0;
+  hipEvent_t ready_ev = nullptr;
+  mutable std::atomic<int> ready{1};
+  aff_t* d_points = nullptr;        // the bases on the device (the build's input; freed with the tables)
+  std::vector<aff_t> h_points;      // the source of their (possibly still running) upload
+};
 
 struct DevBuf {  // RAII device allocation
   void* p = nullptr;
@@ -77,11 +89,12 @@ void launch_rowmat_vec(hipStream_t st, const fe_t* poly, size_t rows, size_t col
 // capi_group.hip: one-launch table-walk MSM (k_multi_mul_coop) on lane 0 (main stream) or 1 (auxiliary stream), and the window tables of a key
 int multi_mul_ensure(sp_ctx* c, int lane);
 size_t multi_mul_wide_min();
+size_t multi_mul_max_scalars();  // the most scalars one walk takes
 int multi_mul_launch(sp_ctx* c, int lane, const aff_t* d_tables, const uint64_t* scalars, size_t n, unsigned* seq_out, const fe_t* d_scalars, const fe_t* last,
                      size_t raw_blocks, bool expand = false);
 int multi_mul_collect(sp_ctx* c, int lane, unsigned seq, jac_t* out, bool yield);
 int ck_key_tables(sp_ctx* c, const sp_ck* ck);  // 0 = ready, 1 = not available (take the bucket MSM), < 0 = error
-// capi_group.hip: host-side pieces of sp_hyrax_prove that sp_hyrax_prove_batch (capi_opening_batch.hip) runs per instance
+// capi_group.hip: host-side pieces of sp_hyrax_prove (capi_opening.hip) that sp_hyrax_prove_batch (capi_opening_batch.hip) runs per instance
 jac_t ck_table_mul_host(const sp_ck* ck, size_t t, const fe_t& scalar);  // table t of a key (t = n_tables - 1: h) times a scalar
 void eq_evals_host(const fe_t* r, size_t k, fe_t* out);                 // eq table of k variables, r[0] on the index MSB (2^k elements)
 void point_transcript_bytes(const aff_t& a, uint8_t out[64]);            // x BE || y BE (src/provider/traits.rs:288-305)
@@ -91,6 +104,16 @@ void absorb_commitment(Keccak256State& h, const aff_t* comm, size_t rows);
 // the round counter overflowed
 bool ipa_transcript(Transcript& t, const aff_t& comm_LZ, const aff_t& comm_eval, const aff_t& delta, const aff_t& beta, fe_t* r);
 int opening_pinned_reserve(sp_ctx* c, size_t bytes);  // c->h_opening holds at least `bytes` (grow-only, a quarter of headroom)
+// capi_group.hip: what the lone opening (capi_opening.hip) launches through - the row eq-table (nvr <= 10: two half tables by value), the mapped pinned
+// block [product | addend staging | scaled sum | flags] with the second auxiliary stream, and out = sc x + a into that block: launched behind the scale
+// (_to_host), or armed ahead on `st` (_arm: sequence number, 0 = not armed), then released with the scale (_fire) or without one (_abort)
+void launch_eq_rows(hipStream_t st, const fe_t* pt, size_t nvr, size_t num_rows, fe_t* dL);
+int ensure_pinned_vec(sp_ctx* c, size_t cols);
+unsigned scale_add_arm(sp_ctx* c, hipStream_t st, const fe_t* dx, const fe_t* da, size_t cols);
+void scale_add_abort(sp_ctx* c, unsigned seq);
+int scale_add_fire(sp_ctx* c, hipStream_t st, unsigned seq, const fe_t* dx, const fe_t* da, const fe_t& sc, size_t cols, uint64_t* out, const char* site);
+int scale_add_to_host(sp_ctx* c, hipStream_t st, const fe_t* dx, const fe_t* da, const fe_t& sc, size_t cols, uint64_t* out, const char* site);
+void addend_wipe(sp_ctx* c, fe_t* d_add, size_t cols, hipStream_t st);  // the mask's pinned staging copy (explicit_bzero) and its device copy (memset on `st`)
 // capi_pippenger.hip: the general (multi-block) Pippenger for caller-supplied bases; window = 0 -> pippenger_window(n)
 int pippenger_window(size_t n);
 int msm_pippenger(sp_ctx* c, const fe_t* d_canon, const aff_t* d_bases, size_t n, bool full_width, int window, jac_t* result);

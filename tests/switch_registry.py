@@ -50,7 +50,7 @@ _ENTRIES = [
            "Other values fall back to 13."),
     Switch("COMB_MINW", "3", PATH, {"2": _child(ABI_GAPS)}, "spartan2_amd/csrc/capi_comb.hip:95", "waves per SIMD of the comb kernels"),
     Switch("PIP_MINW", "3", PATH, {"2": _child(ABI_GAPS)}, "spartan2_amd/csrc/capi_pippenger.hip:31", "waves per SIMD of the Pippenger bucket kernels"),
-    Switch("FBTABLES_OLD", "0", PATH, {"1": _child(ABI_GAPS)}, "spartan2_amd/csrc/capi_group.hip:420", "round-5 fixed-base table build"),
+    Switch("FBTABLES_OLD", "0", PATH, {"1": _child(ABI_GAPS)}, "spartan2_amd/csrc/capi_group.hip:547", "round-5 fixed-base table build"),
     Switch("FOLD_STAGE2", "0", PATH, {"1": _child(ABI_GAPS)}, "spartan2_amd/csrc/capi_core.hip:608", "second stage folded into the streaming producers"),
     Switch("FOLD_SLOTS", "64", PATH, {"1": _child(SWITCHED), "7": _child(SWITCHED)}, "spartan2_amd/csrc/capi_core.hip:627",
            "slots of the folded second stage, clamped to 1..64; read only with FOLD_STAGE2=1. 7 is halved to a count that divides the groups (7 -> 3 -> 1)."),
@@ -84,9 +84,9 @@ _ENTRIES = [
     Switch("PREFIX_CACHE", "0", PATH, {"1": _child(SWITCHED)}, "spartan2_amd/host/spartan_snark.cpp:220", "FLAG_PREFIX_CACHE: the transcript prefix kept per prep"),
     Switch("DELTA_ROUNDS_LEFT", "17", PATH, {"1": _child(SWITCHED), "64": _child(SWITCHED)}, "spartan2_amd/host/spartan_snark.cpp:71",
            "inner-sum-check rounds left when the opening's delta MSM is issued (>= 1); above the round count it falls through to the publish"),
-    Switch("ZVEC_ARMED", "1", PATH, {"0": _child(SWITCHED)}, "spartan2_amd/csrc/capi_group.hip:1523", "z_vec launched behind the scale, not armed ahead"),
-    Switch("WALK_GROUPS", "1", PATH, {"0": _child(SWITCHED)}, "spartan2_amd/csrc/capi_group.hip:1860", "multi-mul walks joined once on the device"),
-    Switch("HOST_T16", "1", PATH, {"0": _child(SWITCHED)}, "spartan2_amd/csrc/capi_group.hip:441", "no host copies of the 16-bit-window tables: the split commitments are refused and the verifier circuit's round commitments take the device walk"),
+    Switch("ZVEC_ARMED", "1", PATH, {"0": _child(SWITCHED)}, "spartan2_amd/csrc/capi_group.hip:1780", "z_vec launched behind the scale, not armed ahead"),
+    Switch("WALK_GROUPS", "1", PATH, {"0": _child(SWITCHED)}, "spartan2_amd/csrc/capi_group.hip:2106", "multi-mul walks joined once on the device"),
+    Switch("HOST_T16", "1", PATH, {"0": _child(SWITCHED)}, "spartan2_amd/csrc/capi_group.hip:568", "no host copies of the 16-bit-window tables: the split commitments are refused and the verifier circuit's round commitments take the device walk"),
     Switch("LZ_DIRECT", "0", PATH, {"1": (Cover(DRIVER_PATHS, 'monkeypatch.setenv("SPARTAN_LZ_DIRECT", "1")'),)}, "spartan2_amd/host/spartan_snark.cpp:220",
            "comm_LZ in the reference's order"),
     Switch("MAIL_DEV", "1", PATH, {"0": (Cover(DRIVER_PATHS, 'monkeypatch.setenv("SPARTAN_MAIL_DEV", "0")'),)}, "spartan2_amd/csrc/capi_core.hip:217",
@@ -96,7 +96,7 @@ _ENTRIES = [
     Switch("KEY_TABLES", "1", PATH,
            {"0": (Cover(DRIVER_PATHS, 'monkeypatch.setenv("SPARTAN_KEY_TABLES", "0")'),
                   Cover("tests/test_gpu_group.py::test_hyrax_prove_is_the_oracles_pcs_prove", '(16, "0")'))},
-           "spartan2_amd/csrc/capi_group.hip:2003", "bucket MSMs instead of the key's window tables (read at every call)"),
+           "spartan2_amd/csrc/capi_group.hip:2250", "bucket MSMs instead of the key's window tables (read at every call)"),
     Switch("SHARD_GATHER_LOG2", "16", PATH,
            {"0": (Cover("tests/test_gpu_sharded_snark.py::test_sharded_prove_is_the_unsharded_proof", '(2, "synthetic", 0)'),),
             "8": (Cover("tests/test_gpu_sharded_snark.py::test_sharded_prove_is_the_unsharded_proof", '(2, "segments", 8)'),)},
@@ -108,7 +108,7 @@ _ENTRIES = [
     Switch("SYNC_SPIN_US", "0", SCHEDULING, {"50": _child(SCHEDULING_RUN)}, "spartan2_amd/csrc/capi_core.hip:36", "poll for n us before the runtime's wait"),
     Switch("WALKERS_PIN", "1", SCHEDULING, {"0": _child(SCHEDULING_RUN)}, "spartan2_amd/csrc/walk_pool.hpp:70", "walkers not pinned near the caller"),
     Switch("WALKERS_IDLE", "0", SCHEDULING, {"1": _child(SCHEDULING_RUN)}, "spartan2_amd/csrc/walk_pool.hpp:153", "walkers in SCHED_IDLE"),
-    Switch("HOST_T16_THP", "1", SCHEDULING, {"0": _child(SCHEDULING_RUN)}, "spartan2_amd/csrc/capi_group.hip:465", "no huge pages for the host tables"),
+    Switch("HOST_T16_THP", "1", SCHEDULING, {"0": _child(SCHEDULING_RUN)}, "spartan2_amd/csrc/capi_group.hip:592", "no huge pages for the host tables"),
     # ---- trace -----------------------------------------------------------------------------------------------------------------------------------------
     Switch("HOST_LAPS", "unset", TRACE, {"1": _child(TRACE_RUN), "2": _child(SWITCHED)}, "spartan2_amd/host/spartan_snark.cpp:1168 and ten more",
            "laps on stderr; some sites take any value, others only 1 or 2 (batched rounds); adds stream_sync calls mid-path"),

@@ -58,3 +58,16 @@ def test_limb_sum_reduction_matches_modular_additions(tmp_path):
     out = subprocess.run([exe, "20000"], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stdout + out.stderr
     assert "scalar field: 20000 sums, 0 mismatches" in out.stdout and "base field: 20000 sums, 0 mismatches" in out.stdout
+
+
+@pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc not on PATH")
+def test_opening_host_arithmetic_matches_its_definitions(tmp_path):
+    """csrc/opening_host.hpp, the host arithmetic of an announced opening, against the definitions it shortens (seeded, scalar field): folding by the
+    top variable r_0 .. r_(k-1) leaves <eq(r), v> for k = 1..6; the level-by-level eq expansion, its last level formed as (P[i] - P[i] r, P[i] r), gives
+    the eq table; the tensor partial sums closed by <right, T> equal <eq(point), d> for 0, 1 and 5 column variables (hb = 0 included)."""
+    exe = str(tmp_path / "opening_fold_check")
+    subprocess.run(["hipcc", "-O2", "-std=c++17", "--offload-arch=gfx950", "-w", "-o", exe, os.path.join(HERE, "native", "opening_fold_check.hip")], check=True, capture_output=True, timeout=600)
+    out = subprocess.run([exe, "20"], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stdout + out.stderr
+    for what in ("fold_top", "eq_expand", "tensor"):
+        assert f"{what}: 20 trials, 0 mismatches" in out.stdout

@@ -215,20 +215,30 @@ def test_rowmat_vec_eq_job_and_its_scaled_finish(ctx):
         hip.rowmat_vec_eq(ctx, t, r, cols, scale=scale)
 
 
-@pytest.mark.parametrize("npt,key_tables", [(11, "1"), (13, "1"), (16, "1"), (16, "0"), (9, "1"), (20, "1")])
+@pytest.mark.parametrize("npt,key_tables", [(11, "1"), (13, "1"), (16, "1"), (16, "0"), (9, "1"), (20, "1"), pytest.param((13, 4), "1", id="13_on_4_columns-1")])
 def test_hyrax_prove_is_the_oracles_pcs_prove(ctx, key, gens, npt, key_tables, monkeypatch):
     """sp_hyrax_prove == HyraxPCS::prove + InnerProductArgumentLinear::prove (hyrax_pc.rs:387-478, ipa.rs:125-170) of the oracle on the same commitment,
     polynomial, point, blinds and randomness: every output word and the transcript state afterwards. npt = 11: one row; 9: a polynomial narrower than
-    the key; 16 with SPARTAN_KEY_TABLES=0: the bucket-MSM fallback; 20 = 512 rows, BASELINE config 2's opening (one-launch rowmat kernel)."""
+    the key; 16 with SPARTAN_KEY_TABLES=0: the bucket-MSM fallback; 20 = 512 rows, BASELINE config 2's opening (one-launch rowmat kernel); 13 on a
+    4-column key: 2048 rows = 11 row variables, the smallest shape whose L is built on the host and uploaded, with the narrow key's delta (the walk from
+    the drawn scalars)."""
     monkeypatch.setenv("SPARTAN_KEY_TABLES", key_tables)
-    rng = np.random.default_rng(SEED + 900 + npt)
+    npt, width = npt if isinstance(npt, tuple) else (npt, 2048)
+    rng = np.random.default_rng(SEED + 900 + npt + (width if width != 2048 else 0))
     n = 1 << npt
-    rows = max(1, n // 2048)
+    rows = max(1, n // width)
     cols = n // rows
     poly = ol.random_field_array(rng, n)
     blinds = ol.random_field_array(rng, rows)
     point = ol.random_field_array(rng, npt)
-    okey = oracle_key()
+    if width == 2048:
+        okey = oracle_key()
+    else:
+        label = b"ck%d" % width
+        g_w = np.zeros((width + 1, 8), dtype=np.uint64)
+        olib().orc_from_label(label, ctypes.c_size_t(width + 1), p64(g_w))
+        key = hip.CommitmentKey(ctx, g_w[:width], g_w[width])
+        okey = ctypes.c_void_p(olib().orc_hyrax_setup(label, ctypes.c_size_t(width)))
     okey_s = ctypes.c_void_p(olib().orc_hyrax_setup(b"ck_s", ctypes.c_size_t(1)))
     g_s = np.zeros((2, 8), dtype=np.uint64)
     olib().orc_from_label(b"ck_s", ctypes.c_size_t(2), p64(g_s))
@@ -256,18 +266,23 @@ def test_hyrax_prove_is_the_oracles_pcs_prove(ctx, key, gens, npt, key_tables, m
     olib().orc_hyrax_free(okey_s)
 
 
-@pytest.mark.parametrize("case", ["match_fresh", "match_warm", "other_blinds", "other_rng", "other_table", "retracted", "replaced", "no_key_tables"])
+@pytest.mark.parametrize("case", ["match_fresh", "match_warm", "other_blinds", "other_rng", "other_table", "retracted", "replaced", "no_key_tables", "narrow_key"])
 def test_hyrax_prove_announced_ahead_is_the_same_opening(ctx, key, gens, case, monkeypatch):
     """sp_hyrax_prove_announce changes WHEN the opening's first half is computed, never a word of it: an announcement that matches is consumed (fresh
     transcript: the commitment's hashing too; warm one: delta and the mask vector only), one that differs in blinds / randomness / table is dropped,
-    a retracted or replaced one leaves nothing behind, and a key without window tables ignores it. Every case equals the unannounced sp_hyrax_prove,
-    which test_hyrax_prove_is_the_oracles_pcs_prove pins to the oracle."""
+    a retracted or replaced one leaves nothing behind, and a key without window tables ignores it; so does a narrow key (256 columns, npt = 10: no
+    delta from the raw blocks). Every case equals the unannounced sp_hyrax_prove, which test_hyrax_prove_is_the_oracles_pcs_prove pins to the oracle."""
     if case == "no_key_tables":
         monkeypatch.setenv("SPARTAN_KEY_TABLES", "0")
-    npt = 14
+    npt, width = 14, 2048
+    if case == "narrow_key":
+        npt, width = 10, 256
+        g256 = np.zeros((257, 8), dtype=np.uint64)
+        olib().orc_from_label(b"ck256", ctypes.c_size_t(257), p64(g256))
+        key = hip.CommitmentKey(ctx, g256[:256], g256[256])
     rng = np.random.default_rng(SEED + 950)
     n = 1 << npt
-    rows = n // 2048
+    rows = n // width
     cols = n // rows
     poly = ol.random_field_array(rng, n)
     blinds = ol.random_field_array(rng, rows)

@@ -690,6 +690,19 @@ int sp_nifs_begin(sp_nifs* n, const uint64_t* E_eq, const uint64_t* rhos, size_t
 /* The rounds only READ the instance layers and their mirrors (folds go to storage of their own), so an object whose layers were written once -
  * prep_prove's cached_step_matvec / cached_step_i64 (:1520-1590) - serves any number of proves: each starts with sp_nifs_begin. */
 int sp_nifs_prepare_small(sp_nifs* n);
+/* cached_step_matvec (:1520-1600) for `count` states of one shape in ONE launch: for every state k < count and every layer b < n_padded of nifs[k], layers
+ * (Az, Bz, Cz)[b] receive (A, B, C) * [W | 1 | X] of instance inst(b) = b < n ? b : 0 of state k (padding clones instance 0, :549-552) - word for word
+ * what n_padded sp_multiply_vec calls on the assembled z leave there. Ws = count * n resident witness tables of num_vars elements (state-major; the same
+ * table may appear more than once), X = count * n * num_public Montgomery elements. z is never assembled: a gathered column reads W or the vector's
+ * tail [1 | X], which the call uploads once for all vectors; chunks of sp_nifs_layers_chunk() vectors share every index / code / coefficient load, and
+ * the chunks' descriptors live in device memory, so the launch count does not depend on count * n_padded. The objects' i64 mirrors are stale afterwards
+ * (sp_nifs_prepare_small). Every argument is checked before anything is uploaded or launched; a refusal names the state and instance in sp_last_error
+ * ("..., state 1, instance 2") and nothing is written: count == 0, n == 0, a null array or element, a W whose length is not num_vars
+ * (SP_ERR_INVALID_WITNESS_LENGTH), an sp_nifs whose n_padded is smaller than n or whose layers are not num_cons long, a shape with verifier challenges
+ * (the others SP_ERR_INVALID_INPUT_LENGTH). The descriptor upload is waited for (the arrays are the call's own); the kernel is asynchronous on the
+ * context's stream, like sp_multiply_vec. */
+size_t sp_nifs_layers_chunk(void);
+int sp_nifs_layers_batch(sp_ctx* ctx, const sp_shape* s, size_t count, sp_nifs* const* nifs, size_t n, const sp_table* const* Ws, const uint64_t* X);
 int sp_nifs_round(sp_nifs* n, size_t t, uint64_t out_coeffs[16]);
 int sp_nifs_challenge(sp_nifs* n, const uint64_t r_b[4]);
 int sp_nifs_finish(sp_nifs* n, sp_table* A_out, sp_table* B_out, sp_table* C_out, uint64_t out_T_out[4], uint64_t out_eq_rho_at_rb[4]);

@@ -202,6 +202,50 @@ int sp_nifs_layer(sp_nifs* n, int which, size_t idx, sp_table** view) {
   return SP_OK;
 }
 
+// cached_step_matvec (src/neutronnova_zk.rs:1520-1600) for `count` states in one launch: layer b of nifs[k] receives (A, B, C) [W | 1 | X] of instance
+// inst(b) = b < n ? b : 0 of state k - the words n_padded sp_multiply_vec calls on an assembled z leave there. This side checks every argument and names
+// the layers; the shape, the upload and the kernel are sp::nifs_layers_launch's (capi_sparse.hip).
+int sp_nifs_layers_batch(sp_ctx* c, const sp_shape* s, size_t count, sp_nifs* const* nifs, size_t n, const sp_table* const* Ws, const uint64_t* X) {
+  if (count == 0) return fail(SP_ERR_INVALID_INPUT_LENGTH, "sp_nifs_layers_batch: count must be at least 1");
+  if (!c || !s || !nifs || !Ws) return fail(SP_ERR_INVALID_INPUT_LENGTH, "sp_nifs_layers_batch: null argument");
+  if (n == 0) return fail(SP_ERR_INVALID_INPUT_LENGTH, "sp_nifs_layers_batch: no instances");
+  const sp_dims& dims = sp::shape_dims(s);
+  const size_t d = dims.num_public, num_vars = dims.num_shared + dims.num_precommitted + dims.num_rest;
+  if (dims.num_challenges) return fail(SP_ERR_INVALID_INPUT_LENGTH, "sp_nifs_layers_batch: a shape with verifier challenges (z = [W | 1 | X] is not all of its vector)");
+  if (d && !X) return fail(SP_ERR_INVALID_INPUT_LENGTH, "sp_nifs_layers_batch: null public values");
+  size_t nvec = 0;
+  for (size_t k = 0; k < count; ++k) {
+    const std::string at = ", state " + std::to_string(k);
+    if (!nifs[k]) return fail(SP_ERR_INVALID_INPUT_LENGTH, "sp_nifs_layers_batch: null sp_nifs" + at);
+    if (nifs[k]->n_padded < n) return fail(SP_ERR_INVALID_INPUT_LENGTH, "sp_nifs_layers_batch: n_padded is smaller than the number of instances" + at);
+    if (nifs[k]->total != dims.num_cons) return fail(SP_ERR_INVALID_INPUT_LENGTH, "sp_nifs_layers_batch: the layers do not have num_cons elements" + at);
+    for (size_t i = 0; i < n; ++i) {
+      const sp_table* W = Ws[k * n + i];
+      if (!W) return fail(SP_ERR_INVALID_INPUT_LENGTH, "sp_nifs_layers_batch: null table" + at + ", instance " + std::to_string(i));
+      if (W->len != num_vars || W->cap < num_vars)
+        return fail(SP_ERR_INVALID_WITNESS_LENGTH, "sp_nifs_layers_batch: W does not have num_vars elements" + at + ", instance " + std::to_string(i));
+    }
+    nvec += nifs[k]->n_padded;
+  }
+  std::vector<fe_t> tails(count * n * (1 + d));
+  std::vector<sp::NifsLayerVec> vecs;
+  vecs.reserve(nvec);
+  for (size_t k = 0; k < count; ++k) {
+    sp_nifs* nf = nifs[k];
+    for (size_t i = 0; i < n; ++i) {
+      fe_t* t = tails.data() + (k * n + i) * (1 + d);
+      t[0] = h_one();
+      for (size_t j = 0; j < d; ++j) t[1 + j] = load_fe(X + 4 * ((k * n + i) * d + j));
+    }
+    for (size_t b = 0; b < nf->n_padded; ++b) {  // padding clones instance 0 (:549-552)
+      const size_t src = k * n + (b < n ? b : 0);
+      vecs.push_back(sp::NifsLayerVec{Ws[src]->d, (const fe_t*)(uintptr_t)src, {nf->A[0] + b * nf->total, nf->B[0] + b * nf->total, nf->C + b * nf->total}});
+    }
+    nf->mirrors_ready = false;
+  }
+  return sp::nifs_layers_launch(c, s, vecs, tails, 1 + d);
+}
+
 // The i64 mirrors and the global large-position list of the current layers (prep_prove's cached_step_i64, src/neutronnova_zk.rs:1548-1586):
 // transcript-independent, so a caller that follows the reference builds them at prep time and passes small_values = 2 to sp_nifs_begin.
 int sp_nifs_prepare_small(sp_nifs* n) {

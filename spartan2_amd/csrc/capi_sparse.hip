@@ -6,6 +6,8 @@
 //                      booleanity rows) one block each.
 //   k_matrix_evals_batched  evaluate_with_tables_fast (src/r1cs/mod.rs:1216-1226) for a chunk of (T_x, T_y) pairs in one walk (kernels_mateval.hpp)
 //   k_spmv3_multi      multiply_vec_batched (sparse.rs:237-302) for a chunk of vectors in one walk (kernels_spmv_multi.hpp)
+//   k_nifs_layers      cached_step_matvec (src/neutronnova_zk.rs:1520-1600): (A, B, C) [W | 1 | X] of every instance of every state into its NIFS
+//                      layers in one launch, z never assembled (kernels_nifs_layers.hpp; the entry is sp_nifs_layers_batch, capi_nifs.hip)
 //   k_pab_*            evals_rx + poly_ABC (src/polys/eq.rs:59-117, src/r1cs/mod.rs:1235-1321) for a chunk of proofs in one walk over interleaved eq tables (kernels_polyabc_batch.hpp)
 //   k_r1cs_residual    R1CSShape::is_sat / is_sat_relaxed (src/r1cs/mod.rs:358-394, :430-471): the row check behind multiply_vec (kernels_sat.hpp)
 // Entries keep the reference's classes: +-1 and |k| in 2..7 as an int8 code (add / sub / double-add chains, sparse.rs:137-155),
@@ -248,6 +250,7 @@ __global__ void __launch_bounds__(256) k_polyabc_short_and_long(PolyAbcArgs a, c
 #include "kernels_mateval.hpp"
 #include "kernels_polyabc_batch.hpp"
 #include "kernels_spmv_multi.hpp"
+#include "kernels_nifs_layers.hpp"
 
 // ---- host side: classification and upload ---------------------------------------------------------------------------
 namespace {
@@ -878,3 +881,39 @@ int sp_shape_is_sat(sp_ctx* c, const sp_shape* s, const sp_table* z, const uint6
 }
 
 }  // extern "C"
+
+// ---- sp_nifs_layers_batch's half on this side of the shape (core.hpp) ----------------------------------------------------------------------------------
+size_t sp_nifs_layers_chunk(void) { return (size_t)spk::NIFS_LAYERS_KC; }
+namespace sp {
+const sp_dims& shape_dims(const sp_shape* s) { return s->dims; }
+int nifs_layers_launch(sp_ctx* c, const sp_shape* s, std::vector<NifsLayerVec>& vecs, const std::vector<fe_t>& tails, size_t tail_len) {
+  const size_t nvec = vecs.size(), nrows = s->dims.num_cons, KC = (size_t)spk::NIFS_LAYERS_KC;
+  if (nvec == 0 || nrows == 0) return SP_OK;
+  if (nvec > 0xffffffffull - KC || s->num_vars > 0xffffffffull) return fail(SP_ERR_INVALID_INPUT_LENGTH, "sp_nifs_layers_batch: too many vectors / variables for 32-bit indices");
+  const size_t tail_bytes = tails.size() * sizeof(fe_t), bytes_all = tail_bytes + nvec * sizeof(NifsLayerVec);
+  char* d = (char*)c->workspace(sp_ctx::WS_NIFS_LAYERS, bytes_all);
+  if (!d) return SP_ERR_NO_DEVICE;
+  const fe_t* d_tails = (const fe_t*)d;
+  for (NifsLayerVec& v : vecs) v.tail = d_tails + (size_t)(uintptr_t)v.tail * tail_len;
+  if (tail_bytes) SP_HIP(hipMemcpyAsync(d, tails.data(), tail_bytes, hipMemcpyHostToDevice, c->stream));
+  SP_HIP(hipMemcpyAsync(d + tail_bytes, vecs.data(), nvec * sizeof(NifsLayerVec), hipMemcpyHostToDevice, c->stream));
+  SP_HIP(sp::stream_sync(c->stream));  // the host arrays are only borrowed for the duration of the call
+  spk::NifsLayersArgs a;
+  for (int m = 0; m < 3; ++m) a.m[m] = s->row[m].view();
+  a.vecs = (const NifsLayerVec*)(d + tail_bytes);
+  a.nvec = (unsigned)nvec;
+  a.num_vars = (unsigned)s->num_vars;
+  size_t blocks = (nrows + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  const uint64_t nnz = s->nnz[0] + s->nnz[1] + s->nnz[2];
+  const size_t chunks = (nvec + KC - 1) / KC;
+  for (size_t c0 = 0; c0 < chunks; c0 += 65535) {  // (gridDim.z is 16 bits wide)
+    const size_t nz = std::min<size_t>(65535, chunks - c0), nv = std::min(nvec - c0 * KC, nz * KC);
+    a.chunk0 = (unsigned)c0;
+    // per chunk the structure once (4-byte index + code, row pointers of both classes); per vector one 32-byte gather per entry and the 3 outputs
+    const uint64_t bytes = nz * (5ull * nnz + 24ull * nrows) + nv * (32ull * nnz + 96ull * nrows);
+    c->timed_kernel("nifs_layers", bytes, spk::k_nifs_layers, dim3((unsigned)blocks, 3, (unsigned)nz), dim3(256), a, nrows);
+  }
+  return SP_OK;
+}
+}  // namespace sp

@@ -259,6 +259,7 @@ struct sp_ctx {
          WS_LOCKSTEP_EQ, WS_LOCKSTEP_PARTIALS, WS_LOCKSTEP_PARAMS,  // the lockstep sum-checks: eq pyramids per instance, block partials, taus / (lo_eff, hi_eff) per round
          WS_OPENING_BLOCKS, WS_OPENING_VECS, WS_OPENING_PARAMS, WS_OPENING_WALK,  // the batched opening's Plan (capi_opening_batch.hip): uniform blocks | d, LZ, z | instances, points | tickets, block sums, results, <R, d> block sums
          WS_POLYABC_BATCH_EQ, WS_POLYABC_BATCH_PYRAMIDS, WS_POLYABC_BATCH_PARTIALS, WS_POLYABC_BATCH_TICKETS,  // sp_poly_abc_batch: a chunk's interleaved eq tables, its eq pyramids, the long columns' partial triples, their arrival counters
+         WS_NIFS_LAYERS,  // sp_nifs_layers_batch: the tails [1 | X] of its vectors, then their descriptors
          WS_PER_LANE,
          WS_SLOTS = 2 * WS_PER_LANE };  // lane 1 = the auxiliary stream used by asynchronous MSM jobs
   void* ws_ptr[WS_SLOTS] = {};
@@ -399,4 +400,15 @@ inline void after_bind(sp_table* t) {  // multilinear.rs:160-163
   t->hi_eff = eff > n / 2 ? eff - n / 2 : 0;
 }
 int alloc_table(sp_ctx* ctx, size_t len, sp_table** out);
+// sp_nifs_layers_batch: its entry (capi_nifs.hip) knows the sp_nifs objects, capi_sparse.hip the shape and the kernel (kernels_nifs_layers.hpp).
+// One vector of the call: z = [W | tail], tail = [1 | X] (1 + num_public elements), and the layers that receive (A, B, C) z.
+struct NifsLayerVec {
+  const fe_t* W;
+  const fe_t* tail;
+  fe_t* out[3];
+};
+const sp_dims& shape_dims(const sp_shape* s);
+// vecs[v].tail = (const fe_t*)(index of the vector's tail in `tails`); tails = n_tails x tail_len elements. Uploads both (one copy, waited for: the
+// arrays are the caller's) and queues ONE k_nifs_layers launch over all vectors on the context's stream.
+int nifs_layers_launch(sp_ctx* c, const sp_shape* s, std::vector<NifsLayerVec>& vecs, const std::vector<fe_t>& tails, size_t tail_len);
 }  // namespace sp

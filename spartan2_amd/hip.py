@@ -1130,10 +1130,15 @@ class Nifs:
         check(lib().sp_nifs_layer(self.h, int(which), ctypes.c_size_t(idx), ctypes.byref(h)))
         return Table(self.ctx, h)
 
+    def prepare_small(self):
+        """sp_nifs_prepare_small: the i64 mirrors of the layers as they are now; begin(small_values=2) then uses them"""
+        check(lib().sp_nifs_prepare_small(self.h))
+
     def begin(self, E_eq, rhos, small_values=False):
+        """small_values: False / 0 = field layers only, True / 1 = build the mirrors now, 2 = use prepare_small()'s"""
         E_eq = np.ascontiguousarray(E_eq, dtype=np.uint64).reshape(self.left + self.right, 4)
         rhos = np.ascontiguousarray(rhos, dtype=np.uint64).reshape(-1, 4)
-        check(lib().sp_nifs_begin(self.h, p64(E_eq), p64(rhos), ctypes.c_size_t(rhos.shape[0]), 1 if small_values else 0))
+        check(lib().sp_nifs_begin(self.h, p64(E_eq), p64(rhos), ctypes.c_size_t(rhos.shape[0]), int(small_values)))
 
     def round(self, t: int):
         out = np.zeros((4, 4), dtype=np.uint64)
@@ -1205,6 +1210,24 @@ class Nifs:
             self.free()
         except Exception:
             pass
+
+
+def nifs_layers_chunk() -> int:
+    """vectors that share one walk in sp_nifs_layers_batch (sp_nifs_layers_chunk): where a call crosses into the next chunk"""
+    lib().sp_nifs_layers_chunk.restype = ctypes.c_size_t
+    return int(lib().sp_nifs_layers_chunk())
+
+
+def nifs_layers_batch(ctx: Context, shape: "Shape", nifs, n: int, W_tables, X):
+    """sp_nifs_layers_batch: cached_step_matvec (src/neutronnova_zk.rs:1520-1600) for len(nifs) states in one launch. Layer b of nifs[k] receives
+    (A, B, C) [W | 1 | X] of instance (b if b < n else 0) of state k; W_tables = len(nifs) * n Tables of num_vars elements (state-major),
+    X = (len(nifs) * n, num_public, 4) Montgomery limbs."""
+    count = len(nifs)
+    assert len(W_tables) == count * n
+    X = np.ascontiguousarray(X, dtype=np.uint64).reshape(-1)
+    narr = (ctypes.c_void_p * max(count, 1))(*[o.h for o in nifs])
+    warr = (ctypes.c_void_p * max(count * n, 1))(*[t.h for t in W_tables])
+    check(lib().sp_nifs_layers_batch(ctx.h, shape.h, ctypes.c_size_t(count), narr, ctypes.c_size_t(n), warr, p64(X) if X.shape[0] else None))
 
 
 # ---- NeutronNova batched ZK sum-checks (src/sumcheck.rs:702-917) ---------------------------------------------------------------

@@ -104,6 +104,10 @@ SS_PREP_PER_STATE_MATVEC = 2  # ... one sp_multiply_vec per state (what the driv
 SS_PREP_CHUNKED_MATVEC = 4  # ... the cached products through sp_multiply_vec_chunked
 NNZ_VERIFY_BATCH_PER_PROOF = 1  # nnz_verify_batch_opts flag (host/neutronnova_zk.cpp): one nnz_verify per proof
 NNZ_VERIFY_BATCH_SHARED = 2  # ... the shared device stage and the combined opening from two proofs on
+NNZ_PREP_PER_STATE_COMMIT = 1  # nnz_prep_prove_batch_opts / nnz_prep_prove_sha256_batch_opts flags: one sp_hyrax_commit per polynomial ...
+NNZ_PREP_PER_STATE_LAYERS = 2  # ... nifs_prepare (a z and one sp_multiply_vec per layer) per state
+NNZ_PREP_SHARED_COMMIT = 4  # ... sp_hyrax_commit_batch whatever the driver's default
+NNZ_PREP_SHARED_LAYERS = 8  # ... sp_nifs_layers_batch whatever the driver's default
 PHASES = ("witness_commit", "matrix_vector_multiply", "outer_sumcheck", "prepare_poly_ABC", "inner_sumcheck", "pcs_prove", "total")
 
 
@@ -763,57 +767,149 @@ class NeutronNovaZkSNARK:
         self.info = dict(zip(("nb", "nx", "ny", "vc_rounds", "vc_vars", "vc_cons", "vc_cons_unpadded", "vc_public"), [int(x) for x in info]))
         self.vk_digest = dig
         self.ps = None
+        self.batch = []  # prep_prove_batch's states
+        self.batch_prep_phases = None
         self._sha_plan = None
         lib().nnz_proof_words.restype = ctypes.c_size_t
 
-    def prep_prove(self, tape: np.ndarray, is_small=True):
-        sw = np.ascontiguousarray(np.stack([np.asarray(i.witness, dtype=np.uint64) for i in self.steps]))
-        sp = np.ascontiguousarray(np.stack([np.asarray(i.publics, dtype=np.uint64) for i in self.steps]))
-        cw = np.ascontiguousarray(self.core.witness, dtype=np.uint64)
-        cp = np.ascontiguousarray(self.core.publics, dtype=np.uint64)
-        used = ctypes.c_size_t(0)
-        ps = ctypes.c_void_p()
-        _check(lib().nnz_prep_prove(self.pk, ctypes.c_size_t(len(self.steps)), hip.p64(sw), ctypes.c_size_t(sw.shape[1]), hip.p64(sp), ctypes.c_size_t(sp.shape[1]), hip.p64(cw),
-                                    hip.p64(cp), int(is_small), hip.p8(tape), ctypes.c_size_t(tape.shape[0]), ctypes.byref(used), ctypes.byref(ps)))
-        if self.ps:
-            lib().nnz_prep_free(self.ps)
-        self.ps = ps
-        return used.value
+    @staticmethod
+    def _words(steps, core):
+        """(step witnesses (n, len), step publics (n, npub), core witness, core publics) as contiguous machine words"""
+        sw = np.ascontiguousarray(np.stack([np.asarray(i.witness, dtype=np.uint64).reshape(-1) for i in steps]))
+        sp = np.ascontiguousarray(np.stack([np.asarray(i.publics, dtype=np.uint64).reshape(-1) for i in steps]))
+        return sw, sp, np.ascontiguousarray(core.witness, dtype=np.uint64), np.ascontiguousarray(core.publics, dtype=np.uint64)
 
-    def prep_prove_sha256(self, blocks, tape: np.ndarray, is_small=True):
-        """prep_prove with every step's witness and the core circuit's generated on the device in one launch (nnz_prep_prove_sha256) for a key set up from
-        frontend.sha256_step_circuit instances: blocks = one 64-byte block per step; the core circuit is the zero block, every public value is x = 0."""
-        blocks = [bytes(b) for b in blocks]
-        assert all(len(b) == 64 for b in blocks)
+    def _ensure_sha_plan(self):
         if self._sha_plan is None:
             from . import frontend
 
             self._sha_plan = hip.Sha256Plan(self.ctx, frontend.sha256_step_witness_plan())
-        buf = np.frombuffer(b"".join(blocks), dtype=np.uint8).copy()
+
+    def prep_prove(self, tape: np.ndarray, is_small=True, _steps=None, _core=None, _keep=True):
+        sw, sp, cw, cp = self._words(self.steps if _steps is None else _steps, self.core if _core is None else _core)
         used = ctypes.c_size_t(0)
         ps = ctypes.c_void_p()
-        _check(lib().nnz_prep_prove_sha256(self.pk, self._sha_plan.h, hip.p8(buf), ctypes.c_size_t(len(blocks)), int(is_small), hip.p8(tape), ctypes.c_size_t(tape.shape[0]),
-                                           ctypes.byref(used), ctypes.byref(ps)))
+        _check(lib().nnz_prep_prove(self.pk, ctypes.c_size_t(sw.shape[0]), hip.p64(sw), ctypes.c_size_t(sw.shape[1]), hip.p64(sp), ctypes.c_size_t(sp.shape[1]), hip.p64(cw),
+                                    hip.p64(cp), int(is_small), hip.p8(tape), ctypes.c_size_t(tape.shape[0]), ctypes.byref(used), ctypes.byref(ps)))
+        if not _keep:  # prep_prove_batch(one_pass=False): the state is the batch's
+            return used.value, ps
         if self.ps:
             lib().nnz_prep_free(self.ps)
         self.ps = ps
         return used.value
 
-    def prove(self, tape: np.ndarray, reference_order=False):
-        """reference_order: the one-thread driver in the statement order of src/neutronnova_zk.rs:1609-2093 (no side jobs, the opening as one sp_hyrax_prove)"""
+    def prep_prove_sha256(self, blocks, tape: np.ndarray, is_small=True, _keep=True):
+        """prep_prove with every step's witness and the core circuit's generated on the device in one launch (nnz_prep_prove_sha256) for a key set up from
+        frontend.sha256_step_circuit instances: blocks = one 64-byte block per step; the core circuit is the zero block, every public value is x = 0."""
+        blocks = [bytes(b) for b in blocks]
+        assert all(len(b) == 64 for b in blocks)
+        self._ensure_sha_plan()
+        buf = np.frombuffer(b"".join(blocks), dtype=np.uint8).copy() if blocks else np.zeros(1, dtype=np.uint8)
+        used = ctypes.c_size_t(0)
+        ps = ctypes.c_void_p()
+        _check(lib().nnz_prep_prove_sha256(self.pk, self._sha_plan.h, hip.p8(buf), ctypes.c_size_t(len(blocks)), int(is_small), hip.p8(tape), ctypes.c_size_t(tape.shape[0]),
+                                           ctypes.byref(used), ctypes.byref(ps)))
+        if not _keep:
+            return used.value, ps
+        if self.ps:
+            lib().nnz_prep_free(self.ps)
+        self.ps = ps
+        return used.value
+
+    def _free_batch(self):
+        for ps in self.batch:
+            lib().nnz_prep_free(ps)
+        self.batch = []
+
+    def prep_prove_batch(self, tapes, witnesses=None, blocks=None, is_small=True, one_pass=True, per_state_commit=False, per_state_layers=False, shared_commit=False,
+                         shared_layers=False):
+        """K = len(tapes) prep states on this one key, kept in self.batch (self.ps is left alone): from `witnesses` (witnesses[k] = (step instances, core
+        instance) of this key's shapes), from `blocks` (blocks[k] = one 64-byte block per step, as prep_prove_sha256) or, with neither, the key's own
+        instances K times. Returns the blocks used of each tape. State k is the state prep_prove / prep_prove_sha256 makes of input k with tape k; prove and
+        check it with prove(tape, state=k) / is_sat(state=k). By default all K are prepared in one pass (nnz_prep_prove_batch_opts /
+        nnz_prep_prove_sha256_batch_opts: one witness launch for SHA-256 keys, the commitments through sp_hyrax_commit_batch, every layer of every state from
+        one sp_nifs_layers_batch, one synchronise); per_state_commit (NNZ_PREP_PER_STATE_COMMIT) keeps one sp_hyrax_commit per polynomial,
+        per_state_layers (NNZ_PREP_PER_STATE_LAYERS) one nifs_prepare per state; shared_commit / shared_layers ask for the shared stage whatever the driver
+        takes by default (measured: profiles/nn_prep_prove_batch.md); one_pass=False is a loop of the single calls. The phases of the last one-pass batch, ms: self.batch_prep_phases."""
+        K = len(tapes)
+        if blocks is not None and witnesses is not None:
+            raise ValueError("prep_prove_batch: blocks or witnesses, not both")
+        for name, v in (("blocks", blocks), ("witnesses", witnesses)):
+            if v is not None and len(v) != K:
+                raise ValueError(f"prep_prove_batch: {len(v)} {name} for {K} tapes")
+        self._free_batch()
+        tapes = [np.ascontiguousarray(t, dtype=np.uint8) for t in tapes]
+        if blocks is not None:
+            blocks = [[bytes(b) for b in bl] for bl in blocks]
+            assert all(len(b) == 64 for bl in blocks for b in bl)
+            self._ensure_sha_plan()
+        srcs = None if blocks is not None else ([(self.steps, self.core)] * K if witnesses is None else list(witnesses))
+        if not one_pass:
+            used_all = []
+            try:
+                for k in range(K):
+                    if blocks is not None:
+                        used, ps = self.prep_prove_sha256(blocks[k], tapes[k], is_small, _keep=False)
+                    else:
+                        used, ps = self.prep_prove(tapes[k], is_small, _steps=srcs[k][0], _core=srcs[k][1], _keep=False)
+                    self.batch.append(ps)
+                    used_all.append(used)
+            except Exception:
+                self._free_batch()  # a failed batch leaves no state behind
+                raise
+            return used_all
+        flags = ((NNZ_PREP_PER_STATE_COMMIT if per_state_commit else 0) | (NNZ_PREP_PER_STATE_LAYERS if per_state_layers else 0)
+                 | (NNZ_PREP_SHARED_COMMIT if shared_commit else 0) | (NNZ_PREP_SHARED_LAYERS if shared_layers else 0))
+        sz = ctypes.c_size_t
+        A = max(K, 1)  # (ctypes arrays of at least one slot)
+        tptr = (hip.c_u8p * A)(*[hip.p8(t) for t in tapes])
+        tblk = (sz * A)(*[t.shape[0] for t in tapes])
+        used = (sz * A)()
+        pss = (ctypes.c_void_p * A)()
+        ms = (ctypes.c_double * 8)()
+        if blocks is not None:
+            bufs = [np.frombuffer(b"".join(bl), dtype=np.uint8).copy() if bl else np.zeros(1, dtype=np.uint8) for bl in blocks]
+            _check(lib().nnz_prep_prove_sha256_batch_opts(self.pk, self._sha_plan.h, sz(K), (hip.c_u8p * A)(*[hip.p8(b) for b in bufs]), (sz * A)(*[len(bl) for bl in blocks]),
+                                                          int(is_small), tptr, tblk, used, pss, ms, ctypes.c_uint(flags)))
+        else:
+            ws = [self._words(steps, core) for steps, core in srcs]
+            npub = ws[0][1].shape[1] if K else 0
+            for k, w in enumerate(ws):  # (the entry point takes one width of public values for all states)
+                if w[1].shape[1] != npub:
+                    raise hip.SpartanHipError(f"prep_prove_batch: state {k}: InvalidWitnessLength ({w[1].shape[1]} public values a step, state 0 has {npub})")
+            arr = lambda i: (hip.c_u64p * A)(*[w[i].ctypes.data_as(hip.c_u64p) for w in ws])
+            _check(lib().nnz_prep_prove_batch_opts(self.pk, sz(K), (sz * A)(*[w[0].shape[0] for w in ws]), arr(0), (sz * A)(*[w[0].shape[1] for w in ws]), arr(1), sz(npub), arr(2),
+                                                   arr(3), int(is_small), tptr, tblk, used, pss, ms, ctypes.c_uint(flags)))
+        self.batch = [ctypes.c_void_p(pss[k]) for k in range(K)]
+        self.batch_prep_phases = dict(blinds_alloc=ms[0], witness=ms[1], commit=ms[2], layers=ms[3], mirrors=ms[4], sync=ms[5], total=ms[6])
+        return [int(used[k]) for k in range(K)]
+
+    def _state(self, state):
+        """the prep state a call works on: self.ps, or self.batch[state]"""
+        if state is None:
+            return self.ps
+        if not 0 <= state < len(self.batch):
+            raise hip.SpartanHipError(f"state {state} of a batch of {len(self.batch)}")
+        return self.batch[state]
+
+    def prove(self, tape: np.ndarray, reference_order=False, state=None):
+        """reference_order: the one-thread driver in the statement order of src/neutronnova_zk.rs:1609-2093 (no side jobs, the opening as one sp_hyrax_prove).
+        state=k proves self.batch[k] (prep_prove_batch) instead of self.ps."""
+        ps = self._state(state)
         n = lib().nnz_proof_words(self.pk)
         words = np.zeros(n, dtype=np.uint64)
         used = ctypes.c_size_t(0)
         ms = (ctypes.c_double * 8)()
         fn = lib().nnz_prove_reference_order if reference_order else lib().nnz_prove
-        _check(fn(self.pk, self.ps, hip.p8(tape), ctypes.c_size_t(tape.shape[0]), ctypes.byref(used), hip.p64(words), ctypes.c_size_t(n), ms))
+        _check(fn(self.pk, ps, hip.p8(tape), ctypes.c_size_t(tape.shape[0]), ctypes.byref(used), hip.p64(words), ctypes.c_size_t(n), ms))
         return words, used.value, dict(zip(NN_PHASES, list(ms)))
 
-    def is_sat(self):
+    def is_sat(self, state=None):
         """R1CSShape::is_sat (src/r1cs/mod.rs:358-394) of every instance the prepared state holds, on the device: a list of hip.SatReport, the step instances
         (against S_step, one batched launch), then the core instance (against S_core); bad_commitment_rows counts over an instance's [shared | precommitted]
-        rows. A finding is a return value; a later prove() on the state is unaffected."""
-        if not self.ps:
+        rows. A finding is a return value; a later prove() on the state is unaffected. state=k checks self.batch[k] instead of self.ps."""
+        ps = self._state(state)
+        if not ps:
             raise hip.SpartanHipError("is_sat before prep_prove")
         n = len(self.steps) + 1
         reps = (hip._SatReport * n)()
@@ -821,7 +917,7 @@ class NeutronNovaZkSNARK:
         while True:  # (instance, row) pairs; a list longer than the buffer is asked for again with room for all of it
             bad = np.zeros((cap, 2), dtype=np.uint64)
             nbad = ctypes.c_size_t(0)
-            rc = lib().nnz_prep_is_sat(self.pk, self.ps, reps, hip.p64(bad), ctypes.c_size_t(cap), ctypes.byref(nbad))
+            rc = lib().nnz_prep_is_sat(self.pk, ps, reps, hip.p64(bad), ctypes.c_size_t(cap), ctypes.byref(nbad))
             if rc not in (0, SP_ERR_UNSAT):
                 _check(rc)
             if nbad.value <= cap:
@@ -899,6 +995,8 @@ class NeutronNovaZkSNARK:
         if self.ps:
             lib().nnz_prep_free(self.ps)
             self.ps = None
+        if getattr(self, "batch", None):
+            self._free_batch()
         if getattr(self, "_sha_plan", None) is not None:
             self._sha_plan.free()
             self._sha_plan = None

@@ -339,7 +339,8 @@ static NNZkPrep* nn_prep_prove(const NNZkKey& pk, size_t n, const uint64_t* step
 // prep_prove for Sha256StepCircuit / CoreCircuit (benches/sha256_neutronnova.rs:49-183) with the witnesses generated on the device: the reference synthesises
 // every step inside prep_prove (src/neutronnova_zk.rs:1487-1518); here all n step witnesses and the core circuit's (the same plan on the zero block, :161-182)
 // are ONE sp_sha256_witness launch. blocks = n x 64 bytes; the circuits' one public value is x = 0.
-static NNZkPrep* nn_prep_prove_sha256(const NNZkKey& pk, const sp_sha256_plan* plan, const uint8_t* blocks, size_t n, bool is_small, Tape& tape) {
+// the key is a Sha256StepCircuit / CoreCircuit key of `n` steps and `plan` the step circuit's witness plan
+static void check_sha256_step_key(const NNZkKey& pk, const sp_sha256_plan* plan, size_t n) {
   const sp_dims &d = pk.dims, &dc = pk.dims_core;
   uint64_t info[5];
   ck(sp_sha256_plan_info(plan, info), "plan info");
@@ -348,6 +349,10 @@ static NNZkPrep* nn_prep_prove_sha256(const NNZkKey& pk, const sp_sha256_plan* p
     throw Error(SP_ERR_INVALID_WITNESS_LENGTH, "InvalidWitnessLength: the plan's variable count is not the key's");
   if (info[3] != 64 || info[4] || d.num_public != 1 || dc.num_public != 1 || d.num_shared != dc.num_shared)
     throw Error(SP_ERR_INVALID_INPUT_LENGTH, "not the step circuit's plan / key");
+}
+static NNZkPrep* nn_prep_prove_sha256(const NNZkKey& pk, const sp_sha256_plan* plan, const uint8_t* blocks, size_t n, bool is_small, Tape& tape) {
+  const sp_dims& d = pk.dims;
+  check_sha256_step_key(pk, plan, n);
   sp_ctx* ctx = pk.ctx;
   const std::vector<uint64_t> zeros(n + 1, 0);  // x = 0 for every step and the core
   return nn_prep_prove_from(pk, n, nullptr, zeros.data(), 1, zeros.data(), is_small, tape, [&](sp_table* const* Ws) {
@@ -355,6 +360,207 @@ static NNZkPrep* nn_prep_prove_sha256(const NNZkKey& pk, const sp_sha256_plan* p
     memcpy(msgs.data(), blocks, 64 * n);
     ck(sp_sha256_witness(ctx, plan, msgs.data(), 64, n + 1, Ws, d.num_shared, nullptr), "sha256 witness");
   });
+}
+
+// prep_prove (:1477-1603) for `count` states of one key, phase by phase over all of them (one state included): state k is word for word the state
+// nn_prep_prove_from makes of input k with tape k - the same blinds in the same order (shared, step 0 .. n-1, core), the same commitments (canonical affine
+// points), the same layers (exact field sums) and mirrors, the same tape blocks used - because none of them depends on how the work was grouped.
+//   blinds       all of state k's, from tape k, before any device work
+//   witnesses    fill_W(Ws): the zeroed tables of state k are Ws[k (n + 1) .. + n) (its steps) and Ws[k (n + 1) + n] (its core)
+//   commitments  sp_hyrax_commit_batch over the K shared segments (step 0's table of every state), over the K n step tables' precommitted segment and
+//                over the K core tables' - the cores ride in the step call when both circuits pad the segments alike (the (2, 30, 2) key does not)
+//   layers       one sp_nifs_create per state, ONE sp_nifs_layers_batch for all states (no z is assembled), sp_nifs_prepare_small per state
+//   one synchronise
+// flags: NNZ_PREP_PER_STATE_COMMIT = one sp_hyrax_commit per polynomial, NNZ_PREP_PER_STATE_LAYERS = nifs_prepare per state - nn_prep_prove_from's calls;
+// NNZ_PREP_SHARED_COMMIT / NNZ_PREP_SHARED_LAYERS ask for the shared stage whatever the default is (a per-state flag wins over them) - there so that one
+// process can compare the forms (tools/nn_prep_batch_timing.py). What the driver takes by default - the shared stage from NN_PREP_SHARED_*_MIN states
+// on - was measured: profiles/nn_prep_prove_batch.md.
+// step_pub(k) / core_pub(k): the public values of state k (n x npub and the core's) as machine words. An error names the state at fault; every state made
+// so far goes with it. phase_ms (8, optional): blinds + allocations, witnesses, commitments, layers, mirrors, synchronise, total.
+enum : unsigned { NNZ_PREP_PER_STATE_COMMIT = 1, NNZ_PREP_PER_STATE_LAYERS = 2, NNZ_PREP_SHARED_COMMIT = 4, NNZ_PREP_SHARED_LAYERS = 8 };
+// Measured at config 3 (32 steps + core), one process, legs alternating, ms a batch: with both stages shared 0.86 / 3.50 / 14.49 (median) at K = 1 / 4 / 16;
+// with one sp_hyrax_commit per polynomial 7.80 / 31.33 / 125.56 (minimum), with nifs_prepare per state 1.64 / 6.48 / 26.03 (minimum); the loop of single
+// calls 8.62 / 34.99 / 141.80. Both shared stages are below the per-state forms' minima at every K, one state included (it is a batch of n + 1 polynomials
+// and n_padded layers already): both are the default from one state on.
+static constexpr size_t NN_PREP_SHARED_COMMIT_MIN = 1, NN_PREP_SHARED_LAYERS_MIN = 1;  // (size_t)-1 = never by default
+static std::vector<NNZkPrep*> nn_prep_prove_batch_from(const NNZkKey& pk, size_t count, bool is_small, Tape* tapes, unsigned flags,
+                                                       const std::function<const uint64_t*(size_t)>& step_pub, const std::function<const uint64_t*(size_t)>& core_pub,
+                                                       const std::function<void(sp_table* const* Ws)>& fill_W, double* phase_ms) {
+  const sp_dims &d = pk.dims, &dc = pk.dims_core;
+  const size_t n = pk.num_steps, CW = DEFAULT_COMMITMENT_WIDTH;
+  std::vector<std::unique_ptr<NNZkPrep>> st(count);
+  size_t at = (size_t)-1;  // the state a per-state step is working on (names the state in an error)
+  try {
+    sp_ctx* ctx = pk.ctx;
+    double ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    const double t_begin = now();
+    double t_last = t_begin;
+    auto phase = [&](int k) {
+      const double t = now();
+      ms[k] += t - t_last;
+      t_last = t;
+    };
+    const bool batch_commit = !(flags & NNZ_PREP_PER_STATE_COMMIT) && ((flags & NNZ_PREP_SHARED_COMMIT) || count >= NN_PREP_SHARED_COMMIT_MIN);
+    const bool batch_layers = !(flags & NNZ_PREP_PER_STATE_LAYERS) && ((flags & NNZ_PREP_SHARED_LAYERS) || count >= NN_PREP_SHARED_LAYERS_MIN);
+    // 1. blinds (PCS::blind, hyrax_pc.rs:192-205) and public values
+    const size_t rows_sh = d.num_shared_unpadded ? d.num_shared / CW : 0, rows_step = d.num_precommitted_unpadded ? d.num_precommitted / CW : 0,
+                 rows_core = dc.num_precommitted_unpadded ? dc.num_precommitted / CW : 0;
+    for (at = 0; at < count; ++at) {
+      st[at].reset(new NNZkPrep());
+      NNZkPrep* ps = st[at].get();
+      ps->is_small = is_small;
+      ps->steps.resize(n);
+      ps->r_shared.resize(rows_sh);
+      for (auto& b : ps->r_shared) b = tapes[at].next();
+      ps->comm_shared.resize(rows_sh);
+      const uint64_t *sp = step_pub(at), *cp = core_pub(at);
+      for (size_t i = 0; i <= n; ++i) {
+        NNPre& p = i < n ? ps->steps[i] : ps->core;
+        const sp_dims& dd = i < n ? d : dc;
+        p.publics.resize(dd.num_public);
+        for (size_t j = 0; j < dd.num_public; ++j) p.publics[j] = fe_from_u64<S>(i < n ? sp[i * d.num_public + j] : cp[j]);
+        p.r_pre.resize(i < n ? rows_step : rows_core);
+        for (auto& b : p.r_pre) b = tapes[at].next();
+        p.comm_pre.resize(p.r_pre.size());
+      }
+    }
+    std::vector<sp_table*> Ws(count * (n + 1));
+    for (at = 0; at < count; ++at)
+      for (size_t i = 0; i <= n; ++i) {
+        const sp_dims& dd = i < n ? d : dc;
+        NNPre& p = i < n ? st[at]->steps[i] : st[at]->core;
+        ck(sp_table_zeros(ctx, dd.num_shared + dd.num_precommitted + dd.num_rest, (size_t)-1, (size_t)-1, &p.W), "alloc W");
+        Ws[at * (n + 1) + i] = p.W;
+      }
+    at = (size_t)-1;
+    phase(0);
+    // 2. witnesses
+    fill_W(Ws.data());
+    phase(1);
+    // 3. commitments
+    struct Poly {
+      const sp_table* W;
+      const fe_t* blinds;
+      aff_t* out;
+      size_t state;
+    };
+    auto commit = [&](const std::vector<Poly>& ps, size_t off, size_t len, const char* what) {
+      if (ps.empty() || !len) return;
+      if (batch_commit) {
+        std::vector<const sp_table*> v(ps.size());
+        std::vector<const uint64_t*> bl(ps.size());
+        std::vector<uint64_t*> out(ps.size());
+        for (size_t j = 0; j < ps.size(); ++j) v[j] = ps[j].W, bl[j] = u64p(ps[j].blinds), out[j] = u64p(&ps[j].out[0].x);
+        ck(sp_hyrax_commit_batch(ctx, pk.ck, ps.size(), v.data(), off, len, bl.data(), out.data()), what);
+        return;
+      }
+      for (const Poly& p : ps) {
+        at = p.state;
+        ck(sp_hyrax_commit(ctx, pk.ck, p.W, off, len, u64p(p.blinds), is_small ? 1 : 0, u64p(&p.out[0].x)), what);
+      }
+      at = (size_t)-1;
+    };
+    std::vector<Poly> shared, steps, cores;
+    for (size_t k = 0; k < count; ++k) {
+      NNZkPrep* ps = st[k].get();
+      if (rows_sh) shared.push_back(Poly{ps->steps[0].W, ps->r_shared.data(), ps->comm_shared.data(), k});  // every circuit carries step 0's shared segment
+      if (rows_step)
+        for (NNPre& p : ps->steps) steps.push_back(Poly{p.W, p.r_pre.data(), p.comm_pre.data(), k});
+      if (rows_core) cores.push_back(Poly{ps->core.W, ps->core.r_pre.data(), ps->core.comm_pre.data(), k});
+    }
+    if (batch_commit && rows_step && dc.num_shared == d.num_shared && dc.num_precommitted == d.num_precommitted) {
+      steps.insert(steps.end(), cores.begin(), cores.end());
+      cores.clear();
+    }
+    commit(shared, 0, d.num_shared, "commit shared");
+    commit(steps, d.num_shared, d.num_precommitted, "commit precommitted");
+    commit(cores, dc.num_shared, dc.num_precommitted, "commit precommitted (core)");
+    phase(2);
+    // 4. layers: can_cache_matvec (:1523) always holds here (nn_setup rejects rest variables beside committed ones and challenges): z = [W | 1 | X] is known
+    std::vector<fe_t> X(count * n * d.num_public);
+    std::vector<const sp_table*> Wsteps(count * n);
+    for (size_t k = 0; k < count; ++k)
+      for (size_t i = 0; i < n; ++i) {
+        std::copy(st[k]->steps[i].publics.begin(), st[k]->steps[i].publics.end(), X.begin() + (k * n + i) * d.num_public);
+        Wsteps[k * n + i] = st[k]->steps[i].W;
+      }
+    if (batch_layers) {
+      size_t n_padded = 2, ell_cons, left, right;
+      while (n_padded < n) n_padded <<= 1;
+      compute_tensor_decomp(d.num_cons, &ell_cons, &left, &right);
+      std::vector<sp_nifs*> nifs(count);
+      for (at = 0; at < count; ++at) {
+        ck(sp_nifs_create(ctx, n_padded, left, right, &st[at]->nifs_cached), "nifs_create");
+        nifs[at] = st[at]->nifs_cached;
+      }
+      at = (size_t)-1;
+      ck(sp_nifs_layers_batch(ctx, pk.S_step, count, nifs.data(), n, Wsteps.data(), u64p(X.data())), "nifs layers");
+      phase(3);
+      for (at = 0; at < count; ++at) ck(sp_nifs_prepare_small(nifs[at]), "prepare_small");
+      phase(4);
+    } else {
+      for (at = 0; at < count; ++at) st[at]->nifs_cached = nifs_prepare(ctx, pk.S_step, d, n, X.data() + at * n * d.num_public, Wsteps.data() + at * n, true);
+      phase(3);
+    }
+    at = (size_t)-1;
+    ck(sp_ctx_synchronize(ctx), "sync");
+    phase(5);
+    ms[6] = now() - t_begin;
+    if (phase_ms) memcpy(phase_ms, ms, sizeof ms);
+  } catch (const Error& e) {
+    // every state made so far goes with `st`
+    throw Error(e.code, std::string("prep_prove_batch: ") + (at == (size_t)-1 ? std::string() : "state " + std::to_string(at) + ": ") + e.what());
+  }
+  std::vector<NNZkPrep*> out(count);
+  for (size_t k = 0; k < count; ++k) out[k] = st[k].release();
+  return out;
+}
+
+// the batch from the frontend's machine words: state k = n x wit_len step words, the core's words, the public values
+static std::vector<NNZkPrep*> nn_prep_prove_batch(const NNZkKey& pk, size_t count, const size_t* n, const uint64_t* const* step_wit, const size_t* wit_len,
+                                                  const uint64_t* const* step_pub, size_t npub, const uint64_t* const* core_wit, const uint64_t* const* core_pub, bool is_small,
+                                                  Tape* tapes, unsigned flags, double* phase_ms) {
+  const sp_dims& d = pk.dims;
+  const size_t want = d.num_shared_unpadded + d.num_precommitted_unpadded + d.num_rest_unpadded, ns = pk.num_steps;
+  for (size_t k = 0; k < count; ++k) {
+    if (n[k] != ns || wit_len[k] != want || npub != d.num_public)
+      throw Error(SP_ERR_INVALID_WITNESS_LENGTH, "prep_prove_batch: state " + std::to_string(k) + ": InvalidWitnessLength");
+    if (!step_wit[k] || !core_wit[k] || (npub && !step_pub[k]) || (pk.dims_core.num_public && !core_pub[k]))
+      throw Error(SP_ERR_INVALID_INPUT_LENGTH, "prep_prove_batch: state " + std::to_string(k) + ": null witness");
+  }
+  sp_ctx* ctx = pk.ctx;
+  return nn_prep_prove_batch_from(
+      pk, count, is_small, tapes, flags, [&](size_t k) { return step_pub[k]; }, [&](size_t k) { return core_pub[k]; },
+      [&](sp_table* const* Ws) {
+        for (size_t k = 0; k < count; ++k) {  // every circuit of a state shares its step 0's shared witness (:1485-1488)
+          for (size_t i = 0; i < ns; ++i) upload_witness(ctx, d, step_wit[k] + i * want, step_wit[k], d.num_shared_unpadded, Ws[k * (ns + 1) + i]);
+          upload_witness(ctx, pk.dims_core, core_wit[k], step_wit[k], d.num_shared_unpadded, Ws[k * (ns + 1) + ns]);
+        }
+      },
+      phase_ms);
+}
+
+// the batch for Sha256StepCircuit / CoreCircuit keys: blocks[k] = the n[k] 64-byte blocks of state k; the witnesses of all K (n + 1) circuits - every state's
+// core is the zero block - are ONE sp_sha256_witness launch
+static std::vector<NNZkPrep*> nn_prep_prove_sha256_batch(const NNZkKey& pk, const sp_sha256_plan* plan, size_t count, const uint8_t* const* blocks, const size_t* n, bool is_small,
+                                                         Tape* tapes, unsigned flags, double* phase_ms) {
+  const size_t ns = pk.num_steps;
+  for (size_t k = 0; k < count; ++k) {
+    if (n[k] != ns) throw Error(SP_ERR_INVALID_WITNESS_LENGTH, "prep_prove_batch: state " + std::to_string(k) + ": InvalidWitnessLength");
+    if (!blocks[k]) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "prep_prove_batch: state " + std::to_string(k) + ": null blocks");
+  }
+  check_sha256_step_key(pk, plan, ns);
+  const std::vector<uint64_t> zeros(ns + 1, 0);  // x = 0 for every step and the core
+  auto pub = [&](size_t) { return zeros.data(); };
+  return nn_prep_prove_batch_from(
+      pk, count, is_small, tapes, flags, pub, pub,
+      [&](sp_table* const* Ws) {
+        std::vector<uint8_t> msgs(64 * count * (ns + 1), 0);
+        for (size_t k = 0; k < count; ++k) memcpy(msgs.data() + 64 * k * (ns + 1), blocks[k], 64 * ns);
+        ck(sp_sha256_witness(pk.ctx, plan, msgs.data(), 64, count * (ns + 1), Ws, pk.dims.num_shared, nullptr), "sha256 witness");
+      },
+      phase_ms);
 }
 
 static void absorb_instance(Tr& tr, const char* label, const std::vector<aff_t>& comm, const std::vector<fe_t>& X) {  // R1CSInstance bytes (src/r1cs/mod.rs:728-736)
@@ -2096,6 +2302,64 @@ int nnz_prep_prove(void* pk, size_t n, const uint64_t* step_wit, size_t wit_len,
   } catch (...) {
     return catch_all_nn();
   }
+}
+// prep_prove for `count` states of one key in one pass (nn_prep_prove_batch_from): per state k its step count n[k] (the key's), step_wit[k] = n[k] x wit_len[k]
+// words, step_pub[k] = n[k] x npub, core_wit[k], core_pub[k], tapes[k] / tape_blocks[k]; tape_used[k] = the blocks it consumed, out_ps[k] = its state - the
+// state nnz_prep_prove makes of the same input and tape, to be proved, checked and freed on its own. phase_ms (8, optional): blinds + allocations, witnesses,
+// commitments, layers, mirrors, synchronise, total. flags: NNZ_PREP_PER_STATE_COMMIT (1) = one sp_hyrax_commit per polynomial, NNZ_PREP_PER_STATE_LAYERS (2)
+// = nifs_prepare per state, NNZ_PREP_SHARED_COMMIT (4) / NNZ_PREP_SHARED_LAYERS (8) = the shared stage whatever the driver's default. count == 0 and null arguments are refused before a context is touched; a wrong step count or witness length is
+// InvalidWitnessLength naming the state ("prep_prove_batch: state 2: ..."), as is a short tape; on any failure every state made so far is freed and out_ps
+// is not written.
+static std::vector<Tape> nnz_batch_tapes(size_t count, const uint8_t* const* tapes, const size_t* tape_blocks) {
+  std::vector<Tape> ts;
+  for (size_t k = 0; k < count; ++k) {
+    if (!tapes[k]) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "prep_prove_batch: state " + std::to_string(k) + ": null tape");
+    ts.push_back(Tape{tapes[k], tape_blocks[k]});
+  }
+  return ts;
+}
+static void nnz_batch_out(const std::vector<NNZkPrep*>& st, const std::vector<Tape>& ts, size_t* tape_used, void** out_ps) {
+  for (size_t k = 0; k < st.size(); ++k) {
+    out_ps[k] = st[k];
+    if (tape_used) tape_used[k] = ts[k].pos;
+  }
+}
+int nnz_prep_prove_batch_opts(void* pk, size_t count, const size_t* n, const uint64_t* const* step_wit, const size_t* wit_len, const uint64_t* const* step_pub, size_t npub,
+                              const uint64_t* const* core_wit, const uint64_t* const* core_pub, int is_small, const uint8_t* const* tapes, const size_t* tape_blocks,
+                              size_t* tape_used, void** out_ps, double* phase_ms, unsigned flags) {
+  try {
+    if (count == 0) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "prep_prove_batch: count must be at least 1");
+    if (!pk || !n || !step_wit || !wit_len || !step_pub || !core_wit || !core_pub || !tapes || !tape_blocks || !out_ps)
+      throw Error(SP_ERR_INVALID_INPUT_LENGTH, "prep_prove_batch: null argument");
+    std::vector<Tape> ts = nnz_batch_tapes(count, tapes, tape_blocks);
+    nnz_batch_out(nn_prep_prove_batch(*(NNZkKey*)pk, count, n, step_wit, wit_len, step_pub, npub, core_wit, core_pub, is_small != 0, ts.data(), flags, phase_ms), ts, tape_used,
+                  out_ps);
+    return 0;
+  } catch (...) {
+    return catch_all_nn();
+  }
+}
+int nnz_prep_prove_batch(void* pk, size_t count, const size_t* n, const uint64_t* const* step_wit, const size_t* wit_len, const uint64_t* const* step_pub, size_t npub,
+                         const uint64_t* const* core_wit, const uint64_t* const* core_pub, int is_small, const uint8_t* const* tapes, const size_t* tape_blocks, size_t* tape_used,
+                         void** out_ps, double* phase_ms) {
+  return nnz_prep_prove_batch_opts(pk, count, n, step_wit, wit_len, step_pub, npub, core_wit, core_pub, is_small, tapes, tape_blocks, tape_used, out_ps, phase_ms, 0);
+}
+// the same with the witnesses generated on the device in ONE launch (see nn_prep_prove_sha256_batch): blocks[k] = n[k] x 64 bytes
+int nnz_prep_prove_sha256_batch_opts(void* pk, const sp_sha256_plan* plan, size_t count, const uint8_t* const* blocks, const size_t* n, int is_small, const uint8_t* const* tapes,
+                                     const size_t* tape_blocks, size_t* tape_used, void** out_ps, double* phase_ms, unsigned flags) {
+  try {
+    if (count == 0) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "prep_prove_batch: count must be at least 1");
+    if (!pk || !plan || !blocks || !n || !tapes || !tape_blocks || !out_ps) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "prep_prove_batch: null argument");
+    std::vector<Tape> ts = nnz_batch_tapes(count, tapes, tape_blocks);
+    nnz_batch_out(nn_prep_prove_sha256_batch(*(NNZkKey*)pk, plan, count, blocks, n, is_small != 0, ts.data(), flags, phase_ms), ts, tape_used, out_ps);
+    return 0;
+  } catch (...) {
+    return catch_all_nn();
+  }
+}
+int nnz_prep_prove_sha256_batch(void* pk, const sp_sha256_plan* plan, size_t count, const uint8_t* const* blocks, const size_t* n, int is_small, const uint8_t* const* tapes,
+                                const size_t* tape_blocks, size_t* tape_used, void** out_ps, double* phase_ms) {
+  return nnz_prep_prove_sha256_batch_opts(pk, plan, count, blocks, n, is_small, tapes, tape_blocks, tape_used, out_ps, phase_ms, 0);
 }
 void nnz_prep_free(void* ps) { delete (NNZkPrep*)ps; }
 // is_sat of the step instances and the core instance of a prepared state (nn_is_sat): reports = num_steps + 1 entries, the steps, then the core; bad_rows =

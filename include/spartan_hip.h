@@ -663,6 +663,26 @@ int sp_sumcheck_quad_batched(sp_ctx* ctx, const uint64_t claims[8], size_t num_r
 int sp_sumcheck_cubic_outer_pow_batched(sp_ctx* ctx, size_t num_rounds, sp_table* pow_left, const sp_table* pow_right, sp_table* A_step, sp_table* B_step,
                                         sp_table* C_step, sp_table* A_core, sp_table* B_core, sp_table* C_core, const uint64_t t_out_step[4], size_t start_round,
                                         sp_round_hook hook, void* user, uint64_t* out_r);
+/* The same two sum-checks for `count` (step, core) pairs of one length in lockstep (NeutronNovaZkSNARK.prove_batch: the pairs of `count` proofs of one
+ * key). Per round: one launch for all 2 x count instances (and a second stage where a round has more than one block per instance), one wait, the host
+ * algebra of the single calls, hook(users[p], start_round + i, ...) for p = 0 .. count - 1 in that order, then the next launch with the `count`
+ * challenges by value. Nothing is queued ahead of a hook and nothing waits on a mailbox, so a hook may use the context (sp_ctx_round_hooks_host_only
+ * plays no part) - for anything but a lockstep sum-check of its own. For every pair p the coefficients handed to the hook, the challenges, out_final,
+ * element 0 of every bound table and (cubic) element 0 of pow_left[p] (base_tau) are exactly what the single call produces on pair p alone with
+ * hook(users[p], ...); the quadratic form honours every table's (lo_eff, hi_eff). Arrays are pair-major: t_out_step count x 4 words, claims count x 8
+ * ({step, core} per pair), out_r count x num_rounds x 4, out_final count x 16. The entries of `users` are the caller's (any value). A hook's non-zero
+ * return ends the call with that code; no later hook is called.
+ * Refused with SP_ERR_INVALID_INPUT_LENGTH before anything is launched or written, naming the pair: count == 0 or count > SP_LOCKSTEP_PAIRS_MAX, a null
+ * argument or array entry, a null hook, tables not 2^num_rounds long, pow tables that do not factor 2^num_rounds or whose split differs from pair 0's,
+ * the same table twice. */
+#define SP_LOCKSTEP_PAIRS_MAX (SP_LOCKSTEP_MAX / 2)
+int sp_sumcheck_cubic_outer_pow_batched_lockstep(sp_ctx* ctx, size_t count, size_t num_rounds, sp_table* const* pow_left, const sp_table* const* pow_right,
+                                                 sp_table* const* A_step, sp_table* const* B_step, sp_table* const* C_step, sp_table* const* A_core,
+                                                 sp_table* const* B_core, sp_table* const* C_core, const uint64_t* t_out_step, size_t start_round, sp_round_hook hook,
+                                                 void* const* users, uint64_t* out_r);
+int sp_sumcheck_quad_batched_lockstep(sp_ctx* ctx, size_t count, const uint64_t* claims, size_t num_rounds, sp_table* const* A0, sp_table* const* A1,
+                                      sp_table* const* B0, sp_table* const* B1, size_t start_round, sp_round_hook hook, void* const* users, uint64_t* out_r,
+                                      uint64_t* out_final);
 
 /* ---- NeutronNova NIFS rounds (src/neutronnova_zk.rs:511-1273, NeutronNovaNIFS::prove) ---------------------
  * The layers Az_b, Bz_b, Cz_b of the n_padded (power of two) instances live in three contiguous device arrays [layer][left*right];

@@ -1158,44 +1158,13 @@ static int tail_check(sp_ctx* c) {
 }
 
 // ---- host-side O(1) glue: UniPoly (src/polys/univariate.rs) ----------------------------------------------------------
-// (UniPoly, two_inv, poly_eval, absorb_poly and the round polynomials of the host-table provers: sumcheck_round.hpp)
+// (UniPoly, two_inv, poly_eval, absorb_poly, from_evals_deg2 / _deg3 and the round polynomials of the host-table provers: sumcheck_round.hpp)
 using sp::UniPoly;
 using sp::two_inv;
 using sp::poly_eval;
 using sp::absorb_poly;
-namespace {
-fe_t six_inv() {
-  static fe_t v = fe_inv_vartime<S>(fe_from_u64<S>(6));
-  return v;
-}
-UniPoly from_evals_deg2(const fe_t e[3]) {  // univariate.rs:84-93
-  UniPoly p;
-  p.n = 3;
-  fe_t c0 = e[0];
-  fe_t a = fe_mul<S>(fe_add<S>(fe_sub<S>(e[0], fe_dbl<S>(e[1])), e[2]), two_inv());
-  fe_t b = fe_sub<S>(fe_sub<S>(e[1], c0), a);
-  p.c[0] = c0;
-  p.c[1] = b;
-  p.c[2] = a;
-  return p;
-}
-UniPoly from_evals_deg3(const fe_t e[4]) {  // univariate.rs:102-118
-  UniPoly p;
-  p.n = 4;
-  fe_t d = e[0];
-  fe_t e1_3 = fe_add<S>(fe_dbl<S>(e[1]), e[1]), e2_3 = fe_add<S>(fe_dbl<S>(e[2]), e[2]);
-  fe_t delta3 = fe_sub<S>(fe_add<S>(fe_sub<S>(e[3], e2_3), e1_3), e[0]);
-  fe_t a = fe_mul<S>(delta3, six_inv());
-  fe_t delta2 = fe_add<S>(fe_sub<S>(e[2], fe_dbl<S>(e[1])), e[0]);
-  fe_t b = fe_sub<S>(fe_mul<S>(delta2, two_inv()), fe_add<S>(fe_dbl<S>(a), a));
-  fe_t c1 = fe_sub<S>(fe_sub<S>(fe_sub<S>(e[1], d), b), a);
-  p.c[0] = d;
-  p.c[1] = c1;
-  p.c[2] = b;
-  p.c[3] = a;
-  return p;
-}
-}  // namespace
+using sp::from_evals_deg2;
+using sp::from_evals_deg3;
 
 extern "C" {
 

@@ -2,6 +2,7 @@
 // for all of them (capi_lockstep.hip).
 //   k_ls_eval_cubic / k_ls_bind_eval_cubic   the round sums of sp_sumcheck_cubic3_host (t0, t_inf and the third sum of the tau p = 0 fallback)
 //   k_ls_eval_quad / k_ls_bind_eval_quad     eval_0 and t_inf of prove_quad on tables with (lo_eff, hi_eff)
+//   k_ls_eval_cubic_pow / k_ls_bind_eval_cubic_pow   the sums at 0, 2, 3 of the batched NeutronNova outer rounds (split power table), two instances a pair
 //   k_ls_eq_levels                           the two eq pyramids of every instance (split eq tables, as k_eq_levels_pair builds them for one)
 //   k_ls_sum_partials                        second stage: the block partials of an instance -> its record
 //   k_ls_bind_last                           the bind behind the last challenge: element 0 of every table, which is also the final claim
@@ -156,6 +157,91 @@ __global__ void __launch_bounds__(256) k_ls_eval_cubic(LsTables3 t, unsigned lon
 __global__ void __launch_bounds__(256) k_ls_bind_eval_cubic(LsTables3 t, LsChallenges ch, unsigned long long q, LsEq e, LsOut o) {
   const unsigned k = blockIdx.y;
   ls_cubic_block<true>(t.a[k], t.b[k], t.c[k], q, ch.r[k], e, o);
+}
+
+// ---- cubic with the split power table: the batched NeutronNova outer rounds of `count` (step, core) pairs ---------------------------------------------
+// Instance 2p + b is branch b (0 = step, 1 = core) of pair p; both branches of a pair share the pair's power tables and its challenge. A round of q pairs
+// of elements writes the three sums at 0, 2, 3 of w (A B - C), as k_eval_cubic_outer_pow does for one instance:
+//   q >= left                  w_lo = pl[low % left] pr[low / left], w_hi = pl[low % left] pr[low / left + q / left]
+//   q <  left (FALLBACK)       w_lo = pl[low], w_hi = pl[low + q]
+// left = 2^lg_left is one value for the launch (the pairs' tables have one length and one split). The power tables are read only: base_tau is the host's.
+constexpr int LS_PAIRS_MAX = LS_MAX / 2;  // SP_LOCKSTEP_PAIRS_MAX
+struct LsPow {
+  const fe_t* pl[LS_PAIRS_MAX];
+  const fe_t* pr[LS_PAIRS_MAX];
+};
+struct LsPairChallenges {
+  fe_t r[LS_PAIRS_MAX];
+};
+// the arguments of k_ls_bind_eval_cubic_pow: tables (1536 B), power tables (512 B), ONE challenge a pair (1024 B; LsChallenges' 2048 B would not fit),
+// q and lg_left (8 B each with padding), LsOut (24 B) = 3112 B of the 4 KiB argument block
+static_assert(sizeof(LsTables3) + sizeof(LsPow) + sizeof(LsPairChallenges) + 2 * sizeof(unsigned long long) + sizeof(LsOut) == 3112,
+              "k_ls_bind_eval_cubic_pow: the argument block");
+template <bool BIND, bool FALLBACK>
+__device__ __forceinline__ void ls_cubic_pow_block(fe_t* __restrict__ A, fe_t* __restrict__ B, fe_t* __restrict__ C, const fe_t* __restrict__ pl,
+                                                   const fe_t* __restrict__ pr, unsigned long long q, unsigned lg_left, const fe_t& r, const LsOut& o) {
+  __shared__ fe_t smem[3 * 4];
+  const unsigned long long base = (unsigned long long)blockIdx.x * LS_CHUNK;
+  fe_t acc[3] = {fe_zero(), fe_zero(), fe_zero()};
+#pragma unroll 1
+  for (unsigned j = 0; j < LS_CHUNK / 256; ++j) {
+    const unsigned long long id = base + j * 256 + threadIdx.x;
+    if (id >= q) break;
+    fe_t al, ah, bl, bh, cl, ch;
+    if (BIND) {
+      al = ls_bind(A[id], A[id + 2 * q], r);
+      ah = ls_bind(A[id + q], A[id + 3 * q], r);
+      bl = ls_bind(B[id], B[id + 2 * q], r);
+      bh = ls_bind(B[id + q], B[id + 3 * q], r);
+      cl = ls_bind(C[id], C[id + 2 * q], r);
+      ch = ls_bind(C[id + q], C[id + 3 * q], r);
+      A[id] = al;
+      A[id + q] = ah;
+      B[id] = bl;
+      B[id + q] = bh;
+      C[id] = cl;
+      C[id + q] = ch;
+    } else {
+      al = A[id];
+      ah = A[id + q];
+      bl = B[id];
+      bh = B[id + q];
+      cl = C[id];
+      ch = C[id + q];
+    }
+    fe_t tl, th;
+    if (FALLBACK) {
+      tl = pl[id];
+      th = pl[id + q];
+    } else {
+      const unsigned long long i = id & ((1ull << lg_left) - 1), jj = id >> lg_left;
+      const fe_t p = pl[i];
+      tl = fe_mul<S>(p, pr[jj]);
+      th = fe_mul<S>(p, pr[jj + (q >> lg_left)]);
+    }
+    acc[0] = fe_add<S>(acc[0], fe_mul<S>(tl, fe_sub<S>(fe_mul<S>(al, bl), cl)));
+    fe_t tb = fe_sub<S>(fe_dbl<S>(th), tl), ab = fe_sub<S>(fe_dbl<S>(ah), al), bb = fe_sub<S>(fe_dbl<S>(bh), bl), cb = fe_sub<S>(fe_dbl<S>(ch), cl);
+    acc[1] = fe_add<S>(acc[1], fe_mul<S>(tb, fe_sub<S>(fe_mul<S>(ab, bb), cb)));
+    tb = fe_sub<S>(fe_add<S>(tb, th), tl);
+    ab = fe_sub<S>(fe_add<S>(ab, ah), al);
+    bb = fe_sub<S>(fe_add<S>(bb, bh), bl);
+    cb = fe_sub<S>(fe_add<S>(cb, ch), cl);
+    acc[2] = fe_add<S>(acc[2], fe_mul<S>(tb, fe_sub<S>(fe_mul<S>(ab, bb), cb)));
+  }
+  block_sum<3>(acc, smem);
+  if (threadIdx.x == 0) ls_emit<3>(acc, o);
+}
+// grid = (blocks per instance, 2 * pairs); the tables hold 2q elements
+template <bool FALLBACK>
+__global__ void __launch_bounds__(256) k_ls_eval_cubic_pow(LsTables3 t, LsPow pw, unsigned long long q, unsigned lg_left, LsOut o) {
+  const unsigned k = blockIdx.y, p = k >> 1;
+  ls_cubic_pow_block<false, FALLBACK>(t.a[k], t.b[k], t.c[k], pw.pl[p], pw.pr[p], q, lg_left, fe_zero(), o);
+}
+// the tables hold 4q elements and are bound with their pair's challenge first
+template <bool FALLBACK>
+__global__ void __launch_bounds__(256) k_ls_bind_eval_cubic_pow(LsTables3 t, LsPow pw, LsPairChallenges ch, unsigned long long q, unsigned lg_left, LsOut o) {
+  const unsigned k = blockIdx.y, p = k >> 1;
+  ls_cubic_pow_block<true, FALLBACK>(t.a[k], t.b[k], t.c[k], pw.pl[p], pw.pr[p], q, lg_left, ch.r[p], o);
 }
 
 // ---- quadratic -----------------------------------------------------------------------------------------------------------------------------------

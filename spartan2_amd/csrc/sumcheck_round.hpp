@@ -23,6 +23,38 @@ inline fe_t poly_eval(const UniPoly& p, const fe_t& r) {  // univariate.rs:136-1
   }
   return ev;
 }
+// UniPoly::from_evals of the batched ZK sum-checks (prove_quad_batched_zk, prove_cubic_with_additive_term_batched_zk): evaluations at 0, 1, 2 (, 3)
+inline fe_t six_inv() {
+  static const fe_t v = fe_inv_vartime<FqP>(fe_from_u64<FqP>(6));
+  return v;
+}
+inline UniPoly from_evals_deg2(const fe_t e[3]) {  // univariate.rs:84-93
+  UniPoly p;
+  p.n = 3;
+  fe_t c0 = e[0];
+  fe_t a = fe_mul<FqP>(fe_add<FqP>(fe_sub<FqP>(e[0], fe_dbl<FqP>(e[1])), e[2]), two_inv());
+  fe_t b = fe_sub<FqP>(fe_sub<FqP>(e[1], c0), a);
+  p.c[0] = c0;
+  p.c[1] = b;
+  p.c[2] = a;
+  return p;
+}
+inline UniPoly from_evals_deg3(const fe_t e[4]) {  // univariate.rs:102-118
+  UniPoly p;
+  p.n = 4;
+  fe_t d = e[0];
+  fe_t e1_3 = fe_add<FqP>(fe_dbl<FqP>(e[1]), e[1]), e2_3 = fe_add<FqP>(fe_dbl<FqP>(e[2]), e[2]);
+  fe_t delta3 = fe_sub<FqP>(fe_add<FqP>(fe_sub<FqP>(e[3], e2_3), e1_3), e[0]);
+  fe_t a = fe_mul<FqP>(delta3, six_inv());
+  fe_t delta2 = fe_add<FqP>(fe_sub<FqP>(e[2], fe_dbl<FqP>(e[1])), e[0]);
+  fe_t b = fe_sub<FqP>(fe_mul<FqP>(delta2, two_inv()), fe_add<FqP>(fe_dbl<FqP>(a), a));
+  fe_t c1 = fe_sub<FqP>(fe_sub<FqP>(fe_sub<FqP>(e[1], d), b), a);
+  p.c[0] = d;
+  p.c[1] = c1;
+  p.c[2] = b;
+  p.c[3] = a;
+  return p;
+}
 // absorb(b"p", &poly): compressed coefficients, to_repr LE each (univariate.rs:182-190)
 inline void absorb_poly(Transcript& t, const UniPoly& p) {
   uint8_t buf[32 * 3];

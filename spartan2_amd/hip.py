@@ -1270,6 +1270,67 @@ def sumcheck_cubic_outer_pow_batched(ctx, num_rounds, pow_left: Table, pow_right
     return out_r
 
 
+LOCKSTEP_PAIRS_MAX = LOCKSTEP_MAX // 2  # SP_LOCKSTEP_PAIRS_MAX
+
+
+def _pair_hooks(py_hooks):
+    """ONE sp_round_hook for a list of Python hooks, one per pair: it dispatches on the user pointer, which is the pair's index + 1 -> (callback, users).
+    A hook may return an int other than 0 (a list entry, not an array) to fail the call with that code; an exception is -5."""
+
+    def raw(user, rnd, cs, cc, ncoeffs, out_ptr):
+        try:
+            s = np.ctypeslib.as_array(cs, shape=(4 * ncoeffs,)).reshape(ncoeffs, 4).copy()
+            k = np.ctypeslib.as_array(cc, shape=(4 * ncoeffs,)).reshape(ncoeffs, 4).copy()
+            got = py_hooks[int(user) - 1](int(rnd), s, k)
+            if isinstance(got, int):
+                return got
+            r = np.ascontiguousarray(got, dtype=np.uint64).reshape(4)
+            for i in range(4):
+                out_ptr[i] = int(r[i])
+            return 0
+        except Exception:  # surfaces as SP_ERR_INTERNAL from the sum-check
+            return -5
+
+    users = (ctypes.c_void_p * max(len(py_hooks), 1))(*[p + 1 for p in range(len(py_hooks))])
+    return ROUND_HOOK(raw), users
+
+
+def _batched_lockstep_lib():
+    L = lib()
+    vpp, sz = ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t
+    L.sp_sumcheck_cubic_outer_pow_batched_lockstep.argtypes = [ctypes.c_void_p, sz, sz, vpp, vpp, vpp, vpp, vpp, vpp, vpp, vpp, c_u64p, sz, ROUND_HOOK, vpp, c_u64p]
+    L.sp_sumcheck_cubic_outer_pow_batched_lockstep.restype = ctypes.c_int
+    L.sp_sumcheck_quad_batched_lockstep.argtypes = [ctypes.c_void_p, sz, c_u64p, sz, vpp, vpp, vpp, vpp, sz, ROUND_HOOK, vpp, c_u64p, c_u64p]
+    L.sp_sumcheck_quad_batched_lockstep.restype = ctypes.c_int
+    return L
+
+
+def sumcheck_quad_batched_lockstep(ctx, claims, num_rounds, A0s, A1s, B0s, B1s, start_round, py_hooks):
+    """sp_sumcheck_quad_batched_lockstep: sumcheck_quad_batched of len(py_hooks) (step, core) pairs, one launch per round for all of them.
+    claims (K, 2, 4), py_hooks[p](round, coeffs_step, coeffs_core) -> r: pair p's hook -> r_y (K, num_rounds, 4), finals (K, 4, 4)."""
+    K = len(py_hooks)
+    claims = np.ascontiguousarray(claims, dtype=np.uint64).reshape(-1, 4)
+    out_r = np.zeros((max(K, 1), num_rounds, 4), dtype=np.uint64)
+    fin = np.zeros((max(K, 1), 4, 4), dtype=np.uint64)
+    cb, users = _pair_hooks(py_hooks)
+    check(_batched_lockstep_lib().sp_sumcheck_quad_batched_lockstep(ctx.h, K, p64(claims), num_rounds, _handles(A0s), _handles(A1s), _handles(B0s), _handles(B1s),
+                                                                    start_round, cb, users, p64(out_r), p64(fin)))
+    return out_r, fin
+
+
+def sumcheck_cubic_outer_pow_batched_lockstep(ctx, num_rounds, pow_lefts, pow_rights, steps, cores, t_out_steps, start_round, py_hooks):
+    """sp_sumcheck_cubic_outer_pow_batched_lockstep: sumcheck_cubic_outer_pow_batched of len(py_hooks) pairs in lockstep; steps[p] / cores[p] = pair p's
+    (A, B, C) tables, t_out_steps (K, 4) -> r_x (K, num_rounds, 4)."""
+    K = len(py_hooks)
+    out_r = np.zeros((max(K, 1), num_rounds, 4), dtype=np.uint64)
+    t = np.ascontiguousarray(t_out_steps, dtype=np.uint64).reshape(-1, 4)
+    cb, users = _pair_hooks(py_hooks)
+    cols = [_handles([s[m] for s in steps]) for m in range(3)] + [_handles([c[m] for c in cores]) for m in range(3)]
+    check(_batched_lockstep_lib().sp_sumcheck_cubic_outer_pow_batched_lockstep(ctx.h, K, num_rounds, _handles(pow_lefts), _handles(pow_rights), *cols, p64(t), start_round, cb,
+                                                                               users, p64(out_r)))
+    return out_r
+
+
 # ---- sum-checks on a table slice (SURVEY 8(e)) -----------------------------------------------------------------------------------
 REDUCE_HOOK = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, c_u64p, ctypes.c_size_t)
 

@@ -108,6 +108,9 @@ NNZ_PREP_PER_STATE_COMMIT = 1  # nnz_prep_prove_batch_opts / nnz_prep_prove_sha2
 NNZ_PREP_PER_STATE_LAYERS = 2  # ... nifs_prepare (a z and one sp_multiply_vec per layer) per state
 NNZ_PREP_SHARED_COMMIT = 4  # ... sp_hyrax_commit_batch whatever the driver's default
 NNZ_PREP_SHARED_LAYERS = 8  # ... sp_nifs_layers_batch whatever the driver's default
+NNZ_BATCH_PER_PROOF = 1  # nnz_prove_batch_opts flags: a loop of nn_prove ...
+NNZ_BATCH_LOCKSTEP = 2  # ... the two batched sum-checks of all proofs in lockstep, whatever the driver's default
+NN_BATCH_PROVE_PHASES = ("head", "outer_before", "outer_sumcheck", "outer_after", "inner_before", "inner_sumcheck", "inner_after", "tail", "total", "lockstep")
 PHASES = ("witness_commit", "matrix_vector_multiply", "outer_sumcheck", "prepare_poly_ABC", "inner_sumcheck", "pcs_prove", "total")
 
 
@@ -769,6 +772,7 @@ class NeutronNovaZkSNARK:
         self.ps = None
         self.batch = []  # prep_prove_batch's states
         self.batch_prep_phases = None
+        self.batch_prove_phases = None
         self._sha_plan = None
         lib().nnz_proof_words.restype = ctypes.c_size_t
 
@@ -903,6 +907,31 @@ class NeutronNovaZkSNARK:
         fn = lib().nnz_prove_reference_order if reference_order else lib().nnz_prove
         _check(fn(self.pk, ps, hip.p8(tape), ctypes.c_size_t(tape.shape[0]), ctypes.byref(used), hip.p64(words), ctypes.c_size_t(n), ms))
         return words, used.value, dict(zip(NN_PHASES, list(ms)))
+
+    def prove_batch(self, tapes, states=None, per_proof=None):
+        """prove() for every state of self.batch (or `states`: indices into self.batch or prep-state handles, all distinct) in one call (nnz_prove_batch_opts):
+        one tape per proof -> [(proof words, blocks used)], each what prove(tapes[k], state=k) returns. per_proof: True = one prove after the other
+        (NNZ_BATCH_PER_PROOF), False = the batched outer and inner sum-checks of all proofs in lockstep, one launch a round for all of them
+        (NNZ_BATCH_LOCKSTEP), None = the form the driver measured to be faster at this batch size (profiles/nn_prove_batch.md). A failure names the proof
+        and leaves every state usable. The phases of the last batch, ms: self.batch_prove_phases."""
+        states = list(range(len(self.batch))) if states is None else list(states)
+        pss = [self._state(s) if isinstance(s, int) else s for s in states]
+        K = len(pss)
+        if len(tapes) != K:
+            raise ValueError(f"prove_batch: {len(tapes)} tapes for {K} states")
+        tapes = [np.ascontiguousarray(t, dtype=np.uint8) for t in tapes]
+        sz = ctypes.c_size_t
+        A = max(K, 1)
+        n = lib().nnz_proof_words(self.pk)
+        words = [np.zeros(n, dtype=np.uint64) for _ in range(K)]
+        used = (sz * A)()
+        ms = (ctypes.c_double * 10)()
+        flags = 0 if per_proof is None else (NNZ_BATCH_PER_PROOF if per_proof else NNZ_BATCH_LOCKSTEP)
+        _check(lib().nnz_prove_batch_opts(self.pk, (ctypes.c_void_p * A)(*[p.value if isinstance(p, ctypes.c_void_p) else p for p in pss]), sz(K),
+                                          (hip.c_u8p * A)(*[hip.p8(t) for t in tapes]), (sz * A)(*[t.shape[0] for t in tapes]), used,
+                                          (hip.c_u64p * A)(*[hip.p64(w) for w in words]), sz(n), ms, ctypes.c_uint(flags)))
+        self.batch_prove_phases = dict(zip(NN_BATCH_PROVE_PHASES, list(ms)))
+        return [(words[k], int(used[k])) for k in range(K)]
 
     def is_sat(self, state=None):
         """R1CSShape::is_sat (src/r1cs/mod.rs:358-394) of every instance the prepared state holds, on the device: a list of hip.SatReport, the step instances

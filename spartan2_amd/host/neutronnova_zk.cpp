@@ -1173,23 +1173,29 @@ static void nn_fill_z(NNProveState& st, sp_table* z, const sp_table* W, const st
   ck(sp_table_write(st.ctx, z, st.nv, u64p(tl.data()), tl.size()), "z tail");
 }
 
-// core products, batched outer sum-check (:1786-1850)
-static void nn_prove_outer(NNProveState& st) {
+// core products, batched outer sum-check (:1786-1850), in three parts: what stands in front of the sum-check, the sum-check of this proof's (step, core)
+// pair, what stands behind it. nn_prove runs them back to back; nn_prove_batch runs ONE lockstep sum-check for the pairs of all its proofs in the middle.
+static void nn_prove_outer_before(NNProveState& st) {
+  sp_ctx* ctx = st.ctx;
+  sp_table** core_abc = st.core_abc;
+  nn_fill_z(st, st.zc, st.ps.core.W, st.ps.core.publics);
+  ck(sp_multiply_vec(ctx, st.pk.S_core, st.zc, core_abc[0], core_abc[1], core_abc[2]), "multiply_vec (core)");
+  ck(sp_table_write(ctx, st.pl, 0, st.E_eq.data(), st.left), "pow left");
+  ck(sp_table_write(ctx, st.pr, 0, st.E_eq.data() + 4 * st.left, st.right), "pow right");
+  st.r_x.resize(st.pk.nx);
+}
+static void nn_prove_outer_sumcheck(NNProveState& st) {
+  sp_table** core_abc = st.core_abc;
+  int rc = sp_sumcheck_cubic_outer_pow_batched(st.ctx, st.pk.nx, st.pl, st.pr, st.A, st.B, st.C, core_abc[0], core_abc[1], core_abc[2], st.tail.data(), st.hc.outer_start,
+                                               nn_batched_hook, &st.hc, u64p(st.r_x.data()));
+  if (st.hc.err) std::rethrow_exception(st.hc.err);
+  ck(rc, "outer sum-check (batched)");
+}
+static void nn_prove_outer_after(NNProveState& st) {
   sp_ctx* ctx = st.ctx;
   const NNZkKey& pk = st.pk;
   vcirc::Circuit& vc = *st.vc;
   sp_table** core_abc = st.core_abc;
-  nn_fill_z(st, st.zc, st.ps.core.W, st.ps.core.publics);
-  ck(sp_multiply_vec(ctx, pk.S_core, st.zc, core_abc[0], core_abc[1], core_abc[2]), "multiply_vec (core)");
-  ck(sp_table_write(ctx, st.pl, 0, st.E_eq.data(), st.left), "pow left");
-  ck(sp_table_write(ctx, st.pr, 0, st.E_eq.data() + 4 * st.left, st.right), "pow right");
-  st.r_x.resize(pk.nx);
-  {
-    int rc = sp_sumcheck_cubic_outer_pow_batched(ctx, pk.nx, st.pl, st.pr, st.A, st.B, st.C, core_abc[0], core_abc[1], core_abc[2], st.tail.data(), st.hc.outer_start,
-                                                 nn_batched_hook, &st.hc, u64p(st.r_x.data()));
-    if (st.hc.err) std::rethrow_exception(st.hc.err);
-    ck(rc, "outer sum-check (batched)");
-  }
   {
     sp_table* cl[6] = {st.A, st.B, st.C, core_abc[0], core_abc[1], core_abc[2]};
     fe_t v[6];
@@ -1203,14 +1209,21 @@ static void nn_prove_outer(NNProveState& st) {
   st.r = vcirc::process_round(ctx, *st.vst, pk.vc, pk.vc_ck, vc, st.hc.outer_start + pk.nx, *st.tr, st.tape)[0];
   st.t_outer = st.now();
 }
+static void nn_prove_outer(NNProveState& st) {
+  nn_prove_outer_before(st);
+  nn_prove_outer_sumcheck(st);
+  nn_prove_outer_after(st);
+}
 
-// evals_rx, both poly_ABC, the z tables, batched inner sum-check (:1852-1945)
-static void nn_prove_inner(NNProveState& st) {
+// evals_rx, both poly_ABC, the z tables, batched inner sum-check (:1852-1945), in the same three parts. lz_ahead: L^T folded_W goes out as a job of the
+// context's vector stream, which carries ONE job at a time - nn_prove_batch, with several states alive on one context, leaves it out (nn_open_side then
+// folds W and takes the product where it needs it: same proof).
+static void nn_prove_inner_before(NNProveState& st) {
   sp_ctx* ctx = st.ctx;
   const NNZkKey& pk = st.pk;
   NNZkPrep& ps = st.ps;
   vcirc::Circuit& vc = *st.vc;
-  const size_t nv = st.nv, dpub = st.dpub, nvr = st.nvr;
+  const size_t nv = st.nv, dpub = st.dpub;
   const fe_t r = st.r, r2 = fe_mul<S>(r, r);
   st.claims[0] = joint_inner_claim(vc.claim_step, r, r2);
   st.claims[1] = joint_inner_claim(vc.claim_core, r, r2);
@@ -1227,12 +1240,20 @@ static void nn_prove_inner(NNProveState& st) {
   fill_z(st.zcc, ps.core.W, ps.core.publics);
   for (sp_table* t : {st.abc_s, st.abc_c, st.zs, st.zcc}) ck(sp_table_set_len(t, 2 * nv, nv, 1 + dpub), "halves");
   st.r_y.resize(pk.ny);
+}
+static void nn_prove_inner_sumcheck(NNProveState& st) {
+  int rc = sp_sumcheck_quad_batched(st.ctx, u64p(st.claims), st.pk.ny, st.abc_s, st.abc_c, st.zs, st.zcc, st.hc.inner_start, nn_batched_hook, &st.hc, u64p(st.r_y.data()),
+                                    u64p(st.fin));
+  if (st.hc.err) std::rethrow_exception(st.hc.err);
+  ck(rc, "inner sum-check (batched)");
+}
+static void nn_prove_inner_after(NNProveState& st, bool lz_ahead) {
+  sp_ctx* ctx = st.ctx;
+  const NNZkKey& pk = st.pk;
+  NNZkPrep& ps = st.ps;
+  vcirc::Circuit& vc = *st.vc;
+  const size_t nvr = st.nvr;
   const std::vector<fe_t>& r_y = st.r_y;
-  {
-    int rc = sp_sumcheck_quad_batched(ctx, u64p(st.claims), pk.ny, st.abc_s, st.abc_c, st.zs, st.zcc, st.hc.inner_start, nn_batched_hook, &st.hc, u64p(st.r_y.data()), u64p(st.fin));
-    if (st.hc.err) std::rethrow_exception(st.hc.err);
-    ck(rc, "inner sum-check (batched)");
-  }
   if (st.t_fold) {  // r_y is known: the halves of comm_LZ and beta, under the verifier-circuit phase
     NNOpeningPointsJob& j = st.points_job;
     j.pk = &pk, j.ps = &ps, j.f_comm = &st.f_comm, j.core_comm = &st.core_comm, j.rows = st.rows;
@@ -1240,7 +1261,7 @@ static void nn_prove_inner(NNProveState& st) {
     j.Rv = eq_evals_host(r_y.data() + 1 + nvr, pk.ny - 1 - nvr);
     st.t_open = st.submit(j);
   }
-  if (st.side) {  // L^T folded_W goes out (NNLzAhead)
+  if (st.side && lz_ahead) {  // L^T folded_W goes out (NNLzAhead)
     st.lz.cols = (size_t)1 << (pk.ny - 1 - nvr);
     st.lz.begin(ctx, st.fW, r_y.data(), nvr);
   }
@@ -1253,6 +1274,11 @@ static void nn_prove_inner(NNProveState& st) {
   for (size_t k = 0; k < 3; ++k) vcirc::process_round(ctx, *st.vst, pk.vc, pk.vc_ck, vc, st.inner_final + k, *st.tr, st.tape);
   if (st.side) ck(sp_fold_commitments2_begin(ctx, u64p(&st.vst->comm_per_round[st.inner_final + 2][0].x), 1, &st.fold2.eval), "fold eval commitments (ladder)");
   st.t_inner = st.now();
+}
+static void nn_prove_inner(NNProveState& st) {
+  nn_prove_inner_before(st);
+  nn_prove_inner_sumcheck(st);
+  nn_prove_inner_after(st, true);
 }
 
 // finalize_multiround_witness (:1948-1952): U_verifier, its regular form, W_verifier
@@ -1622,6 +1648,148 @@ static ProofBuf nn_prove(const NNZkKey& pk, NNZkPrep& ps, Tape& tape, double* ph
   nn_prove_relaxed_spartan(st);
   nn_prove_opening(st);
   return nn_prove_emit(st, phase_ms);
+}
+
+// ---- prove for many prepared states of one key: the two batched sum-checks of all proofs in lockstep ---------------------------------------------------
+// `count` NNProveStates over `count` distinct prep states, on the calling thread. Per proof, in order: setup .. NIFS (the NIFS stays per proof). Then the
+// part of the outer step in front of its sum-check per proof, ONE sp_sumcheck_cubic_outer_pow_batched_lockstep over the (step, core) pairs of all proofs
+// with nn_batched_hook on each proof's NNHookCtx, the part behind it per proof; the inner step likewise around ONE sp_sumcheck_quad_batched_lockstep;
+// then verifier-circuit instance .. emit per proof. Each proof's transcript, tape and verifier circuit see exactly the calls nn_prove makes, so the proofs
+// and the tape use are nn_prove's. Several states alive on ONE context - what a step leaves begun on st.ctx was checked for being per state:
+//   the transcript's asynchronous absorb            per sp_transcript (its own pending job)
+//   ps.wk, ps.ctx2 and every job on them            per prep state
+//   sp_fold_commitments2_begin (rows, eval)         walker-backed, per job; without a free walk slot _finish computes the plain form
+//   sp_ctx_round_hooks_host_only                    per CONTEXT: every state sets the same value and every state's destructor resets it - the states of a
+//                                                   group die together, and the lockstep calls queue nothing ahead of a hook whatever it says
+//   sp_rowmat_vec_eq_begin (NNLzAhead)              per CONTEXT, one job at a time: left out (nn_prove_inner_after(st, false))
+// Batches above SP_LOCKSTEP_PAIRS_MAX run in groups of that size. A failure is rethrown naming the proof; every state's destructor runs with all of the
+// group's states alive (drain, collect, drop), so every prep state stays usable.
+enum : unsigned { NNZ_BATCH_PER_PROOF = 1, NNZ_BATCH_LOCKSTEP = 2 };
+// lockstep from this many proofs on (profiles/nn_prove_batch.md: the smallest count whose lockstep median lies below the minimum of sequential proves)
+static const size_t NN_PROVE_BATCH_LOCKSTEP_MIN = (size_t)-1;
+struct NNBatchPhases {  // milliseconds, summed over the groups
+  double head = 0, outer_before = 0, outer_sc = 0, outer_after = 0, inner_before = 0, inner_sc = 0, inner_after = 0, tail = 0, total = 0, lockstep = 0;
+};
+template <class F>
+static void nn_batch_named(size_t k, F&& f) {
+  try {
+    f();
+  } catch (const Error& e) {
+    throw Error(e.code, "prove_batch: proof " + std::to_string(k) + ": " + e.what());
+  } catch (const std::exception& e) {
+    throw Error(SP_ERR_INTERNAL, "prove_batch: proof " + std::to_string(k) + ": " + e.what());
+  }
+}
+// the lockstep call's failure: a hook's exception belongs to its proof; anything else to the call
+static void nn_batch_sumcheck_failed(std::vector<std::unique_ptr<NNProveState>>& st, size_t first, int rc, const char* what) {
+  for (size_t k = 0; k < st.size(); ++k)
+    if (st[k]->hc.err) nn_batch_named(first + k, [&] { std::rethrow_exception(st[k]->hc.err); });
+  ck(rc, what);
+}
+static void nn_prove_group_lockstep(const NNZkKey& pk, NNZkPrep* const* ps, Tape* tapes, size_t first, size_t count, ProofBuf* out, NNBatchPhases& ph) {
+  std::vector<std::unique_ptr<NNProveState>> st;
+  for (size_t k = 0; k < count; ++k) st.emplace_back(new NNProveState(pk, *ps[k], tapes[k], false));
+  auto each = [&](auto&& step) {
+    for (size_t k = 0; k < count; ++k) nn_batch_named(first + k, [&] { step(*st[k]); });
+  };
+  double t0 = NNLaps::now();
+  auto lap = [&](double& into) {
+    const double t = NNLaps::now();
+    into += t - t0;
+    t0 = t;
+  };
+  each([](NNProveState& s) {
+    s.t_start = s.now();
+    s.laps.start(s.t_start);
+    nn_prove_setup(s);
+    nn_prove_rerandomize(s);
+    nn_prove_rest_commitments(s);
+    nn_prove_instances(s);
+    nn_prove_nifs(s);
+  });
+  lap(ph.head);
+  std::vector<void*> users(count);
+  std::vector<sp_table*> tb[8];
+  std::vector<const sp_table*> pr(count);
+  for (auto& v : tb) v.resize(count);
+  for (size_t k = 0; k < count; ++k) users[k] = &st[k]->hc;
+  // outer
+  each(nn_prove_outer_before);
+  lap(ph.outer_before);
+  {
+    std::vector<uint64_t> t_out(4 * count), r_x(4 * count * pk.nx);
+    for (size_t k = 0; k < count; ++k) {
+      NNProveState& s = *st[k];
+      sp_table* const six[6] = {s.A, s.B, s.C, s.core_abc[0], s.core_abc[1], s.core_abc[2]};
+      for (int q = 0; q < 6; ++q) tb[q][k] = six[q];
+      tb[6][k] = s.pl;
+      pr[k] = s.pr;
+      memcpy(&t_out[4 * k], s.tail.data(), 32);
+    }
+    const int rc = sp_sumcheck_cubic_outer_pow_batched_lockstep(pk.ctx, count, pk.nx, tb[6].data(), pr.data(), tb[0].data(), tb[1].data(), tb[2].data(), tb[3].data(),
+                                                                tb[4].data(), tb[5].data(), t_out.data(), st[0]->hc.outer_start, nn_batched_hook, users.data(), r_x.data());
+    if (rc) nn_batch_sumcheck_failed(st, first, rc, "outer sum-check (batched, lockstep)");
+    for (size_t k = 0; k < count; ++k) memcpy(st[k]->r_x.data(), &r_x[4 * k * pk.nx], 32 * pk.nx);
+  }
+  lap(ph.outer_sc);
+  each(nn_prove_outer_after);
+  lap(ph.outer_after);
+  // inner
+  each(nn_prove_inner_before);
+  lap(ph.inner_before);
+  {
+    std::vector<uint64_t> claims(8 * count), r_y(4 * count * pk.ny), fin(16 * count);
+    for (size_t k = 0; k < count; ++k) {
+      NNProveState& s = *st[k];
+      tb[0][k] = s.abc_s, tb[1][k] = s.abc_c, tb[2][k] = s.zs, tb[3][k] = s.zcc;
+      memcpy(&claims[8 * k], s.claims, 64);
+    }
+    const int rc = sp_sumcheck_quad_batched_lockstep(pk.ctx, count, claims.data(), pk.ny, tb[0].data(), tb[1].data(), tb[2].data(), tb[3].data(), st[0]->hc.inner_start,
+                                                     nn_batched_hook, users.data(), r_y.data(), fin.data());
+    if (rc) nn_batch_sumcheck_failed(st, first, rc, "inner sum-check (batched, lockstep)");
+    for (size_t k = 0; k < count; ++k) {
+      memcpy(st[k]->r_y.data(), &r_y[4 * k * pk.ny], 32 * pk.ny);
+      memcpy(st[k]->fin, &fin[16 * k], 128);
+    }
+  }
+  lap(ph.inner_sc);
+  each([](NNProveState& s) { nn_prove_inner_after(s, false); });
+  lap(ph.inner_after);
+  for (size_t k = 0; k < count; ++k)
+    nn_batch_named(first + k, [&] {
+      NNProveState& s = *st[k];
+      nn_prove_vc_instance(s);
+      nn_prove_random_instance(s);
+      nn_prove_nova_nifs(s);
+      nn_prove_relaxed_spartan(s);
+      nn_prove_opening(s);
+      out[k] = nn_prove_emit(s, nullptr);
+    });
+  lap(ph.tail);
+}
+static std::vector<ProofBuf> nn_prove_batch(const NNZkKey& pk, NNZkPrep* const* ps, Tape* tapes, size_t count, unsigned flags, NNBatchPhases* phases) {
+  for (size_t k = 0; k < count; ++k) {
+    if (!ps[k]) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "prove_batch: proof " + std::to_string(k) + ": null state");
+    for (size_t j = 0; j < k; ++j)
+      if (ps[j] == ps[k]) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "prove_batch: the same state twice, proofs " + std::to_string(j) + " and " + std::to_string(k));
+  }
+  if ((flags & NNZ_BATCH_PER_PROOF) && (flags & NNZ_BATCH_LOCKSTEP)) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "prove_batch: both forms forced");
+  const bool lockstep = (flags & NNZ_BATCH_LOCKSTEP) || (!(flags & NNZ_BATCH_PER_PROOF) && count >= NN_PROVE_BATCH_LOCKSTEP_MIN);
+  std::vector<ProofBuf> out(count);
+  std::vector<Tape> work(tapes, tapes + count);  // the callers' tapes move only when every proof is made
+  NNBatchPhases ph;
+  const double t0 = NNLaps::now();
+  if (lockstep) {
+    for (size_t at = 0; at < count; at += SP_LOCKSTEP_PAIRS_MAX)
+      nn_prove_group_lockstep(pk, ps + at, work.data() + at, at, std::min<size_t>(SP_LOCKSTEP_PAIRS_MAX, count - at), out.data() + at, ph);
+  } else {
+    for (size_t k = 0; k < count; ++k) nn_batch_named(k, [&] { out[k] = nn_prove(pk, *ps[k], work[k], nullptr); });
+  }
+  ph.total = NNLaps::now() - t0;
+  ph.lockstep = lockstep ? 1 : 0;
+  if (phases) *phases = ph;
+  std::copy(work.begin(), work.end(), tapes);
+  return out;
 }
 
 
@@ -2408,6 +2576,43 @@ int nnz_prove(void* pk, void* ps, const uint8_t* tape, size_t tape_blocks, size_
 // the reference-order driver (see nn_prove): the time of an unchanged neutronnova_zk.rs over the ABI; the proof is the same
 int nnz_prove_reference_order(void* pk, void* ps, const uint8_t* tape, size_t tape_blocks, size_t* tape_used, uint64_t* out_words, size_t out_cap, double* phase_ms) {
   return nnz_prove_impl(pk, ps, tape, tape_blocks, tape_used, out_words, out_cap, phase_ms, true);
+}
+// prove for `count` distinct prepared states of one key (nn_prove_batch): per proof k its state ps[k], tapes[k] / tape_blocks[k], out_words[k] = a buffer of
+// out_cap words; tape_used[k] = the blocks it consumed. Proof k and its tape use are those of nnz_prove(pk, ps[k], tapes[k], ..). flags: NNZ_BATCH_PER_PROOF (1)
+// = a loop of nn_prove, NNZ_BATCH_LOCKSTEP (2) = the two batched sum-checks of all proofs in lockstep, 0 = the driver's default (NN_PROVE_BATCH_LOCKSTEP_MIN).
+// phase_ms (10, optional): setup .. NIFS, outer before / sum-check / after, inner before / sum-check / after, verifier-circuit instance .. emit, total,
+// 1.0 when the lockstep form ran (the per-proof form fills the total only). count == 0 and null arguments are refused before a context is touched; the same
+// state twice is refused; a failure names the proof ("prove_batch: proof 2: random tape exhausted"), writes no output and leaves every state usable.
+int nnz_prove_batch_opts(void* pk, void* const* ps, size_t count, const uint8_t* const* tapes, const size_t* tape_blocks, size_t* tape_used, uint64_t* const* out_words,
+                         size_t out_cap, double* phase_ms, unsigned flags) {
+  try {
+    if (count == 0) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "prove_batch: count must be at least 1");
+    if (!pk || !ps || !tapes || !tape_blocks || !out_words) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "prove_batch: null argument");
+    std::vector<Tape> ts;
+    for (size_t k = 0; k < count; ++k) {
+      if (!tapes[k] || !out_words[k]) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "prove_batch: proof " + std::to_string(k) + ": null tape or output");
+      ts.push_back(Tape{tapes[k], tape_blocks[k]});
+    }
+    const NNZkKey& key = *(NNZkKey*)pk;
+    if (key.layout.words() > out_cap) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "proof buffer too small");
+    NNBatchPhases ph;
+    std::vector<ProofBuf> pf = nn_prove_batch(key, (NNZkPrep* const*)ps, ts.data(), count, flags, &ph);
+    for (size_t k = 0; k < count; ++k) {
+      memcpy(out_words[k], pf[k].words.data(), pf[k].words.size() * 8);
+      if (tape_used) tape_used[k] = ts[k].pos;
+    }
+    if (phase_ms) {
+      const double v[10] = {ph.head, ph.outer_before, ph.outer_sc, ph.outer_after, ph.inner_before, ph.inner_sc, ph.inner_after, ph.tail, ph.total, ph.lockstep};
+      memcpy(phase_ms, v, sizeof v);
+    }
+    return 0;
+  } catch (...) {
+    return catch_all_nn();
+  }
+}
+int nnz_prove_batch(void* pk, void* const* ps, size_t count, const uint8_t* const* tapes, const size_t* tape_blocks, size_t* tape_used, uint64_t* const* out_words,
+                    size_t out_cap, double* phase_ms) {
+  return nnz_prove_batch_opts(pk, ps, count, tapes, tape_blocks, tape_used, out_words, out_cap, phase_ms, 0);
 }
 // NeutronNovaZkSNARK as bincode bytes (the reference's serde framing; include/spartan_hip.h "wire formats"). `_to_bytes`: out may be NULL to learn *len.
 int nnz_proof_to_bytes(void* pk, const uint64_t* words, size_t nwords, uint8_t* out, size_t cap, size_t* len) {

@@ -275,6 +275,32 @@ void sp_shape_free(sp_shape* s);
 /* entry counts of the precomputed structures: out = {nnz A, B, C (multiply_vec / poly_ABC), filtered nnz A, B, C (multiply_vec_incremental_into),
  * long columns, short columns} — the algorithmic-byte accounting of SURVEY.md 8(d) needs them */
 int sp_shape_info(const sp_shape* s, uint64_t out[8]);
+/* A shape from the bincode bytes of SplitR1CSShape (the derived Serialize, src/r1cs/mod.rs:742-773: what sp_wire_shape(.., digest_form = 0) writes),
+ * `r` positioned at its first byte and left behind its last. Writes the ten dimensions and, by default, a ROW-ONLY shape: the row-major structures
+ * sp_multiply_vec[_batched|_chunked], sp_shape_matrix_evals_batched, sp_nifs_layers_batch and sp_shape_is_sat walk - what a verifier needs. sp_poly_abc,
+ * sp_poly_abc_batch, sp_multiply_vec_incremental and sp_multiply_vec_incremental_round0 refuse such a shape ("row-only shape"); sp_shape_info reports
+ * zeros for what it does not hold. flags: SP_SHAPE_WIRE_DEVICE = build the structures on the device from the uploaded bytes (one lane an entry checks,
+ * classifies and narrows; counts per row, an exclusive scan, a scatter; the host loops over no per-entry array), SP_SHAPE_WIRE_HOST = build them on the host
+ * (the code behind sp_shape_from_csr, rows only), neither = the form that measured faster (sp_shape_wire_device_default); SP_SHAPE_WIRE_FULL = the full
+ * shape of sp_shape_from_csr through the host decode; SP_SHAPE_WIRE_TIMED = device events around the stages (sp_shape_from_wire_stages).
+ * Refused with SP_ERR_INVALID_INPUT_LENGTH, before anything is launched: short input, a length prefix the input cannot hold, data and indices of
+ * different lengths, an indptr that has not num_cons + 1 entries, does not start at 0, decreases or does not end at the entry count, a cols field other
+ * than num_vars + 1 + num_public + num_challenges, 2^32 or more rows, columns or entries, an unpadded count above its padded one. Refused after the
+ * entry pass (nothing is returned, every allocation of the call is freed): a coefficient that is not below the modulus, a column index >= cols; the
+ * message names the first such entry. */
+#define SP_SHAPE_WIRE_DEVICE 1
+#define SP_SHAPE_WIRE_HOST 2
+#define SP_SHAPE_WIRE_FULL 4
+#define SP_SHAPE_WIRE_TIMED 8
+typedef struct sp_unwire sp_unwire;
+int sp_shape_from_wire(sp_ctx* ctx, sp_unwire* r, unsigned flags, sp_dims* dims_out, sp_shape** out);
+/* the last sp_shape_from_wire of the calling thread, ms: upload, entry kernel, counts + scan, scatter (device events; zero without SP_SHAPE_WIRE_TIMED),
+ * parse + checks, decode, whole call (host clock), 1 / 0 = device / host decode */
+void sp_shape_from_wire_stages(double out[8]);
+/* compile-time constants of the decode kernels: threads a block, rows a scan tile; and which decode a call without a forcing flag takes (1 = device) */
+size_t sp_shape_wire_block(void);
+size_t sp_shape_wire_scan_tile(void);
+int sp_shape_wire_device_default(void);
 /* SplitR1CSShape::multiply_vec (:1075-1107). z has num_vars + 1 + num_public + num_challenges elements. */
 int sp_multiply_vec(sp_ctx* ctx, const sp_shape* s, const sp_table* z, sp_table* az, sp_table* bz, sp_table* cz);
 /* SplitR1CSShape::multiply_vec_batched (:1130-1166 -> PrecomputedSparseMatrix::multiply_vec_batched, sparse.rs:237-302): the three products for
@@ -781,7 +807,6 @@ size_t sp_wire_len(const sp_wire* w); /* bytes written so far */
 int sp_wire_bytes(sp_wire* w, uint8_t* out, size_t cap);
 int sp_wire_digest(sp_wire* w, uint8_t out[32]);
 /* byte source (borrows `bytes`): what bincode's deserializer does for the same types; every call fails on short input */
-typedef struct sp_unwire sp_unwire;
 int sp_unwire_new(const uint8_t* bytes, size_t n, sp_unwire** out);
 void sp_unwire_free(sp_unwire* r);
 size_t sp_unwire_left(const sp_unwire* r);
@@ -792,10 +817,16 @@ int sp_unwire_scalars(sp_unwire* r, size_t n, uint64_t* out);
 int sp_unwire_affines(sp_unwire* r, size_t n, uint64_t* out);    /* on-curve check */
 int sp_unwire_points(sp_unwire* r, size_t n, uint64_t* out_aff); /* any representative -> Aff; on-curve check */
 int sp_unwire_done(const sp_unwire* r);                          /* fails on trailing bytes, as bincode's DefaultOptions do */
+/* the inverse of sp_wire_hyrax_key: num_cols, the length-prefixed generators (on-curve check), h. A generator count other than num_cols is refused.
+ * ck == NULL: *num_cols alone and nothing is consumed (to size the buffer); else ck holds cap >= num_cols affine points and h one. */
+int sp_unwire_hyrax_key(sp_unwire* r, uint64_t* ck, size_t cap, size_t* num_cols, uint64_t* h);
 /* DigestHelperTrait::digest of SpartanVerifierKey (src/spartan.rs:73-104): SHA-256(bincode(vk_ee) || bincode(ck_s) || S.write_bytes()).
  * (ck, num_cols, h) = the witness key (vk_ee holds the same three fields), (ck_s, num_cols_s, h_s) = the width-1 key of src/spartan.rs:152. */
 int sp_vk_digest(const sp_dims* dims, const sp_csr* A, const sp_csr* B, const sp_csr* C, const uint64_t* ck, size_t num_cols, const uint64_t* h,
                  const uint64_t* ck_s, size_t num_cols_s, const uint64_t* h_s, uint8_t out[32]);
+/* the same digest from the bincode bytes of the key itself (vk_ee, ck_s, S): the two Hyrax keys as they stand, then S.write_bytes() as slices of the
+ * input in write_bytes' order - nothing is converted. Refuses short input and trailing bytes. Host only, no shared state: may run on any thread. */
+int sp_vk_digest_from_wire(const uint8_t* bytes, size_t n, uint8_t out[32]);
 /* SpartanSNARK (src/spartan.rs:125-137) between bincode bytes and this build's flat word layout:
  *   comm_W rows (Aff: shared, precommitted, rest) | public_values | challenges | outer polys (rounds_x x 3 F) | claims_outer (3 F) |
  *   inner polys (rounds_y x 2 F) | eval_W | blind_eval_W | delta | beta (Aff) | z_vec (z_len F) | z_delta | z_beta.

@@ -251,6 +251,7 @@ __global__ void __launch_bounds__(256) k_polyabc_short_and_long(PolyAbcArgs a, c
 #include "kernels_polyabc_batch.hpp"
 #include "kernels_spmv_multi.hpp"
 #include "kernels_nifs_layers.hpp"
+#include "kernels_wire_decode.hpp"
 
 // ---- host side: classification and upload ---------------------------------------------------------------------------
 namespace {
@@ -365,7 +366,13 @@ struct sp_shape {
   size_t n_long_cols = 0;
   bool col_permuted = false;  // col[] is stored in walk order: position i = d_short_order[i] for i < n_short, then the long columns
   uint64_t nnz[3] = {0, 0, 0}, nnz_filtered[3] = {0, 0, 0};
+  bool row_only = false;  // sp_shape_from_wire's verifier form: row[] alone; filtered[], col[] and the walk order are absent (null)
 };
+// the entry points that walk filtered[] or col[] refuse a row-only shape before they touch either
+static int refuse_row_only(const sp_shape* s, const char* who) {
+  if (s && s->row_only) return fail(SP_ERR_INVALID_INPUT_LENGTH, std::string(who) + ": row-only shape (loaded by sp_shape_from_wire without SP_SHAPE_WIRE_FULL)");
+  return SP_OK;
+}
 
 extern "C" {
 
@@ -546,6 +553,305 @@ int sp_shape_info(const sp_shape* s, uint64_t out[8]) {
   return SP_OK;
 }
 
+}  // extern "C"
+
+// ---- sp_shape_from_wire: a shape from the bincode bytes of SplitR1CSShape (src/r1cs/mod.rs:742-773) ----------------------------------------------------
+// The stream is what sp_wire_shape(.., digest_form = 0) writes: the ten dimensions, then per matrix data (u64 length, 32 bytes an element), indices and
+// indptr (u64 length, 8 bytes an element) and cols. wire_parse_shape takes the arrays as slices of the input and checks everything a later stage
+// dereferences through - that is O(rows) host work and ends a refused call before the first launch. The row-major structure is then built either on the
+// device from the raw bytes (wire_decode_device, kernels_wire_decode.hpp: the host touches no per-entry array) or on the host with the code behind
+// sp_shape_from_csr (wire_decode_host: sp_unwire_scalars, index narrowing, Classifier, build_split), which is also the way to a full shape.
+namespace {
+
+struct WireSlices {  // one matrix of the stream
+  const uint8_t *data = nullptr, *idx = nullptr, *indptr = nullptr;
+  uint64_t nnz = 0;
+};
+inline uint64_t le64(const uint8_t* p) {  // (little-endian host; the input need not be aligned)
+  uint64_t v;
+  memcpy(&v, p, 8);
+  return v;
+}
+struct DevOwner {  // the device allocations of one call: freed when the call ends unless the shape took them
+  std::vector<void*> held;
+  ~DevOwner() {
+    for (void* q : held) hipFree(q);
+  }
+  template <class T>
+  int alloc(T** out, size_t n) {
+    hipError_t e = hipMalloc((void**)out, (n ? n : 1) * sizeof(T));
+    if (e != hipSuccess) return fail(SP_ERR_NO_DEVICE, std::string("sp_shape_from_wire: hipMalloc: ") + hipGetErrorString(e));
+    held.push_back(*out);
+    return SP_OK;
+  }
+  void release(void* q) { held.erase(std::remove(held.begin(), held.end(), q), held.end()); }
+};
+// what the last sp_shape_from_wire on this thread spent where (ms): upload, entry kernel, counts + scan, scatter (device events, SP_SHAPE_WIRE_TIMED),
+// parse + checks, the decode as a whole, the whole call (host clock), and 1 / 0 for the device / host decode
+thread_local double g_wire_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+constexpr bool WIRE_DEVICE_DEFAULT = true;  // which decode a call without a forcing flag takes: measured, profiles/verifier_key.md
+
+double wall_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+int wire_parse_shape(sp_unwire* r, sp_dims* d, uint64_t* cols_out, WireSlices W[3]) {
+  static const char* const names[3] = {"A", "B", "C"};
+  const uint8_t* base = r->p;
+  uint64_t w[10];
+  int rc = sp_unwire_u64s(r, 10, w);
+  if (rc) return rc;
+  for (int i = 0; i < 10; ++i)
+    if (w[i] >> 32) return fail(SP_ERR_INVALID_INPUT_LENGTH, "sp_shape_from_wire: a dimension is 2^32 or more");
+  d->num_cons = w[0], d->num_cons_unpadded = w[1];
+  d->num_shared_unpadded = w[2], d->num_precommitted_unpadded = w[3], d->num_rest_unpadded = w[4];
+  d->num_shared = w[5], d->num_precommitted = w[6], d->num_rest = w[7];
+  d->num_public = w[8], d->num_challenges = w[9];
+  if (d->num_cons == 0) return fail(SP_ERR_INVALID_INPUT_LENGTH, "sp_shape_from_wire: num_cons must be at least 1");
+  if (d->num_cons_unpadded > d->num_cons) return fail(SP_ERR_INVALID_INPUT_LENGTH, "sp_shape_from_wire: num_cons_unpadded exceeds num_cons");
+  if (d->num_shared_unpadded > d->num_shared || d->num_precommitted_unpadded > d->num_precommitted || d->num_rest_unpadded > d->num_rest)
+    return fail(SP_ERR_INVALID_INPUT_LENGTH, "sp_shape_from_wire: an unpadded variable count exceeds its padded one");
+  const uint64_t cols = d->num_shared + d->num_precommitted + d->num_rest + 1 + d->num_public + d->num_challenges, rows = d->num_cons;
+  if (cols >> 32) return fail(SP_ERR_INVALID_INPUT_LENGTH, "sp_shape_from_wire: 2^32 columns or more");
+  *cols_out = cols;
+  for (int m = 0; m < 3; ++m) {
+    const std::string at = std::string(" (matrix ") + names[m] + ")";
+    size_t nd, ni, np;
+    if ((rc = sp_unwire_len(r, 32, &nd))) return rc;
+    W[m].data = r->p;
+    r->p += 32 * nd;
+    if ((rc = sp_unwire_len(r, 8, &ni))) return rc;
+    W[m].idx = r->p;
+    r->p += 8 * ni;
+    if ((rc = sp_unwire_len(r, 8, &np))) return rc;
+    W[m].indptr = r->p;
+    r->p += 8 * np;
+    uint64_t cols_m;
+    if ((rc = sp_unwire_u64s(r, 1, &cols_m))) return rc;
+    W[m].nnz = nd;
+    if (nd != ni) return fail(SP_ERR_INVALID_INPUT_LENGTH, "sp_shape_from_wire: data and indices differ in length" + at);
+    if ((uint64_t)nd >> 32) return fail(SP_ERR_INVALID_INPUT_LENGTH, "sp_shape_from_wire: 2^32 entries or more" + at);
+    if (np != rows + 1) return fail(SP_ERR_INVALID_INPUT_LENGTH, "sp_shape_from_wire: indptr must hold num_cons + 1 offsets" + at);
+    if (cols_m != cols) return fail(SP_ERR_INVALID_INPUT_LENGTH, "sp_shape_from_wire: cols is not num_vars + 1 + num_public + num_challenges" + at);
+    // u64 prefixes, 32- and 8-byte elements: every array starts at a multiple of 8 from the start of the shape (the device loads rely on it)
+    if (((W[m].data - base) | (W[m].idx - base) | (W[m].indptr - base)) & 7) return fail(SP_ERR_INTERNAL, "sp_shape_from_wire: an array is not 8-byte aligned in the stream");
+    uint64_t prev = le64(W[m].indptr);
+    if (prev != 0) return fail(SP_ERR_INVALID_INPUT_LENGTH, "sp_shape_from_wire: indptr does not start at 0" + at);
+    for (uint64_t i = 1; i <= rows; ++i) {
+      const uint64_t v = le64(W[m].indptr + 8 * i);
+      if (v < prev) return fail(SP_ERR_INVALID_INPUT_LENGTH, "sp_shape_from_wire: indptr decreases at row " + std::to_string(i - 1) + at);
+      prev = v;
+    }
+    if (prev != nd) return fail(SP_ERR_INVALID_INPUT_LENGTH, "sp_shape_from_wire: indptr does not end at the entry count" + at);
+  }
+  return SP_OK;
+}
+
+int wire_decode_device(sp_ctx* c, const sp_dims& d, uint64_t cols, const WireSlices W[3], bool timed, sp_shape* s) {
+  static const char* const names[3] = {"A", "B", "C"};
+  const size_t rows = d.num_cons, nblk = (rows + spk::WIRE_SCAN_TILE - 1) / spk::WIRE_SCAN_TILE;
+  DevOwner own;
+  spk::WireArgs a;
+  uint4* d_data[3];
+  unsigned long long *d_idx[3], *d_indptr[3];
+  uint64_t max_nnz = 0, all_nnz = 0;
+  int rc;
+  for (int m = 0; m < 3; ++m) {
+    const size_t nnz = W[m].nnz;
+    max_nnz = std::max<uint64_t>(max_nnz, nnz);
+    all_nnz += nnz;
+    spk::WireMat& wm = a.m[m];
+    if ((rc = own.alloc(&d_data[m], 2 * nnz)) || (rc = own.alloc(&d_idx[m], nnz)) || (rc = own.alloc(&d_indptr[m], rows + 1)) || (rc = own.alloc(&wm.code, nnz)) ||
+        (rc = own.alloc(&wm.idx32, nnz)) || (rc = own.alloc(&wm.sptr, rows + 1)) || (rc = own.alloc(&wm.gptr, rows + 1)))
+      return rc;
+    wm.data = d_data[m];
+    wm.idx = d_idx[m];
+    wm.indptr = d_indptr[m];
+    wm.nnz = nnz;
+  }
+  unsigned* d_words;  // totals [6] | max_len [3] | block_sums [6 nblk]
+  if ((rc = own.alloc(&a.status, 6)) || (rc = own.alloc(&d_words, 9 + 6 * nblk))) return rc;
+  a.cols = cols;
+  a.totals = d_words;
+  a.max_len = d_words + 6;
+  a.block_sums = d_words + 9;
+  a.nblk = (unsigned)nblk;
+  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  struct EvGuard {
+    hipEvent_t* e;
+    ~EvGuard() {
+      for (int i = 0; i < 5; ++i)
+        if (e[i]) hipEventDestroy(e[i]);
+    }
+  } ev_guard{ev};
+  auto mark = [&](int i) -> hipError_t { return timed ? hipEventRecord(ev[i], c->stream) : hipSuccess; };
+  if (timed)
+    for (int i = 0; i < 5; ++i) SP_HIP(hipEventCreate(&ev[i]));
+  SP_HIP(mark(0));
+  SP_HIP(hipMemsetAsync(a.status, 0xff, 6 * sizeof(unsigned long long), c->stream));
+  SP_HIP(hipMemsetAsync(d_words, 0, 9 * sizeof(unsigned), c->stream));
+  for (int m = 0; m < 3; ++m) {  // the raw bytes, once: no per-entry work on the host
+    const size_t nnz = W[m].nnz;
+    if (nnz) SP_HIP(hipMemcpyAsync(d_data[m], W[m].data, 32 * nnz, hipMemcpyHostToDevice, c->stream));
+    if (nnz) SP_HIP(hipMemcpyAsync(d_idx[m], W[m].idx, 8 * nnz, hipMemcpyHostToDevice, c->stream));
+    SP_HIP(hipMemcpyAsync(d_indptr[m], W[m].indptr, 8 * (rows + 1), hipMemcpyHostToDevice, c->stream));
+  }
+  SP_HIP(mark(1));
+  const dim3 block(spk::WIRE_BLOCK);
+  const unsigned row_blocks = (unsigned)std::min<size_t>((rows + spk::WIRE_BLOCK - 1) / spk::WIRE_BLOCK, 4096);
+  if (max_nnz) {
+    const unsigned eb = (unsigned)std::min<uint64_t>((max_nnz + spk::WIRE_BLOCK - 1) / spk::WIRE_BLOCK, 4096);
+    c->timed_kernel("wire_entries", 45ull * all_nnz, spk::k_wire_entries, dim3(eb, 3), block, a);  // 32 + 8 in, 1 + 4 out an entry
+  }
+  SP_HIP(mark(2));
+  c->timed_kernel("wire_row_counts", all_nnz + 3 * 24ull * rows, spk::k_wire_row_counts, dim3(row_blocks, 3), block, a, rows);
+  c->timed_kernel("wire_scan", 3 * 8ull * rows, spk::k_wire_scan_reduce, dim3((unsigned)nblk, 3), block, a, rows);
+  c->timed_kernel("wire_scan", 3 * 16ull * nblk, spk::k_wire_scan_blocks, dim3(1, 3), block, a);
+  c->timed_kernel("wire_scan", 3 * 16ull * rows, spk::k_wire_scan_add, dim3((unsigned)nblk, 3), block, a, rows);
+  SP_HIP(mark(3));
+  unsigned long long status[6];
+  unsigned words[9];
+  SP_HIP(hipMemcpyAsync(status, a.status, sizeof status, hipMemcpyDeviceToHost, c->stream));
+  SP_HIP(hipMemcpyAsync(words, d_words, sizeof words, hipMemcpyDeviceToHost, c->stream));
+  SP_HIP(sp::stream_sync(c->stream));
+  SP_HIP(hipGetLastError());
+  for (int m = 0; m < 3; ++m) {
+    if (status[2 * m] != spk::WIRE_STATUS_OK)
+      return fail(SP_ERR_INVALID_INPUT_LENGTH, std::string("sp_shape_from_wire: non-canonical field element at entry ") + std::to_string(status[2 * m]) + " of matrix " + names[m]);
+    if (status[2 * m + 1] != spk::WIRE_STATUS_OK)
+      return fail(SP_ERR_INVALID_INPUT_LENGTH, std::string("sp_shape_from_wire: column index out of range at entry ") + std::to_string(status[2 * m + 1]) + " of matrix " + names[m]);
+    if ((uint64_t)words[2 * m] + words[2 * m + 1] != W[m].nnz) return fail(SP_ERR_INTERNAL, "sp_shape_from_wire: the class counts do not add up to the entry count");
+  }
+  spk::WireOutArgs o;
+  for (int m = 0; m < 3; ++m)
+    if ((rc = own.alloc(&o.o[m].sidx, words[2 * m])) || (rc = own.alloc(&o.o[m].scode, words[2 * m])) || (rc = own.alloc(&o.o[m].gidx, words[2 * m + 1])) ||
+        (rc = own.alloc(&o.o[m].gval, words[2 * m + 1])))
+      return rc;
+  c->timed_kernel("wire_scatter", 46ull * all_nnz + 3 * 24ull * rows, spk::k_wire_scatter, dim3(row_blocks, 3), block, a, o, rows);
+  SP_HIP(mark(4));
+  SP_HIP(sp::stream_sync(c->stream));
+  SP_HIP(hipGetLastError());
+  if (timed)
+    for (int i = 0; i < 4; ++i) {
+      float ms = 0;
+      SP_HIP(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
+      g_wire_ms[i] = ms;
+    }
+  for (int m = 0; m < 3; ++m) {
+    SplitOnDevice& r = s->row[m];
+    r.sptr = a.m[m].sptr, r.gptr = a.m[m].gptr;
+    r.sidx = o.o[m].sidx, r.scode = o.o[m].scode, r.gidx = o.o[m].gidx, r.gval = o.o[m].gval;
+    r.max_len = words[6 + m];
+    for (void* q : {(void*)r.sptr, (void*)r.gptr, (void*)r.sidx, (void*)r.scode, (void*)r.gidx, (void*)r.gval}) own.release(q);
+    s->nnz[m] = W[m].nnz;
+  }
+  return SP_OK;  // (the raw bytes, the codes and the narrowed indices go with `own`)
+}
+
+int wire_decode_host(sp_ctx* c, const sp_dims& d, uint64_t cols, const WireSlices W[3], bool full, sp_shape** out) {
+  const size_t rows = d.num_cons;
+  std::vector<fe_t> data[3];
+  std::vector<uint32_t> idx[3];
+  std::vector<uint64_t> ptr[3];
+  for (int m = 0; m < 3; ++m) {
+    const size_t nnz = W[m].nnz;
+    data[m].resize(nnz);
+    idx[m].resize(nnz);
+    ptr[m].resize(rows + 1);
+    sp_unwire src{W[m].data, W[m].data + 32 * nnz};
+    int rc = sp_unwire_scalars(&src, nnz, reinterpret_cast<uint64_t*>(data[m].data()));
+    if (rc) return rc;
+    for (size_t k = 0; k < nnz; ++k) {
+      const uint64_t v = le64(W[m].idx + 8 * k);
+      if (v >= cols) return fail(SP_ERR_INVALID_INPUT_LENGTH, "sp_shape_from_wire: column index out of range at entry " + std::to_string(k));
+      idx[m][k] = (uint32_t)v;
+    }
+    memcpy(ptr[m].data(), W[m].indptr, 8 * (rows + 1));
+  }
+  if (full) {
+    sp_csr cs[3];
+    for (int m = 0; m < 3; ++m) cs[m] = sp_csr{reinterpret_cast<const uint64_t*>(data[m].data()), idx[m].data(), ptr[m].data()};
+    return sp_shape_from_csr(c, &cs[0], &cs[1], &cs[2], &d, out);
+  }
+  sp_shape* s = new sp_shape();
+  s->dims = d;
+  s->num_vars = d.num_shared + d.num_precommitted + d.num_rest;
+  s->num_cols = cols;
+  s->row_only = true;
+  Classifier cls;
+  for (int m = 0; m < 3; ++m) {
+    std::vector<Entry> all(W[m].nnz);
+    for (size_t r = 0; r < rows; ++r)
+      for (uint64_t k = ptr[m][r]; k < ptr[m][r + 1]; ++k) {
+        Entry& e = all[k];
+        e.major = (unsigned)r;
+        e.minor = idx[m][k];
+        e.val = data[m][k];
+        e.code = cls.code(e.val);
+      }
+    s->nnz[m] = W[m].nnz;
+    int rc = upload_split(build_split(rows, all), &s->row[m]);
+    if (rc) {
+      sp_shape_free(s);
+      return rc;
+    }
+  }
+  hipError_t e = hipDeviceSynchronize();
+  if (e != hipSuccess) {
+    sp_shape_free(s);
+    return fail(SP_ERR_NO_DEVICE, std::string("sp_shape_from_wire: ") + hipGetErrorString(e));
+  }
+  *out = s;
+  return SP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t sp_shape_wire_block(void) { return (size_t)spk::WIRE_BLOCK; }
+size_t sp_shape_wire_scan_tile(void) { return (size_t)spk::WIRE_SCAN_TILE; }
+int sp_shape_wire_device_default(void) { return WIRE_DEVICE_DEFAULT ? 1 : 0; }
+void sp_shape_from_wire_stages(double out[8]) {
+  if (out) memcpy(out, g_wire_ms, sizeof g_wire_ms);
+}
+
+int sp_shape_from_wire(sp_ctx* c, sp_unwire* r, unsigned flags, sp_dims* dims_out, sp_shape** out) {
+  if (!c || !r || !dims_out || !out) return fail(SP_ERR_INVALID_INPUT_LENGTH, "sp_shape_from_wire: null argument");
+  const bool want_dev = flags & SP_SHAPE_WIRE_DEVICE, want_host = flags & SP_SHAPE_WIRE_HOST, full = flags & SP_SHAPE_WIRE_FULL;
+  if ((flags & ~(unsigned)(SP_SHAPE_WIRE_DEVICE | SP_SHAPE_WIRE_HOST | SP_SHAPE_WIRE_FULL | SP_SHAPE_WIRE_TIMED)) || (want_dev && (want_host || full)))
+    return fail(SP_ERR_INVALID_INPUT_LENGTH, "sp_shape_from_wire: flags that exclude each other (the device decode builds the row-only shape; the full shape takes the host decode)");
+  for (double& x : g_wire_ms) x = 0;
+  const double t0 = wall_ms();
+  sp_dims d;
+  uint64_t cols = 0;
+  WireSlices W[3];
+  int rc = wire_parse_shape(r, &d, &cols, W);
+  if (rc) return rc;
+  const double t1 = wall_ms();
+  const bool device = want_dev || (!want_host && !full && WIRE_DEVICE_DEFAULT);
+  sp_shape* s = nullptr;
+  if (device) {
+    s = new sp_shape();
+    s->dims = d;
+    s->num_vars = d.num_shared + d.num_precommitted + d.num_rest;
+    s->num_cols = cols;
+    s->row_only = true;
+    if ((rc = wire_decode_device(c, d, cols, W, (flags & SP_SHAPE_WIRE_TIMED) != 0, s))) {
+      delete s;  // (it owns nothing yet: the structures are handed over at the very end of a decode that succeeded)
+      return rc;
+    }
+  } else if ((rc = wire_decode_host(c, d, cols, W, full, &s))) {
+    return rc;
+  }
+  const double t2 = wall_ms();
+  g_wire_ms[4] = t1 - t0;
+  g_wire_ms[5] = t2 - t1;
+  g_wire_ms[6] = t2 - t0;
+  g_wire_ms[7] = device ? 1 : 0;
+  *dims_out = d;
+  *out = s;
+  return SP_OK;
+}
+
 static int spmv3(sp_ctx* c, const sp_shape* s, const SplitOnDevice* mats, const uint64_t* nnz, const sp_table* z, const sp_table* const* base,
                  sp_table** outs, const char* what) {
   const size_t nrows = s->dims.num_cons;
@@ -626,6 +932,7 @@ int sp_multiply_vec_chunked(sp_ctx* c, const sp_shape* s, const sp_table* const*
 }
 int sp_multiply_vec_incremental(sp_ctx* c, const sp_shape* s, const sp_table* z, const sp_table* caz, const sp_table* cbz, const sp_table* ccz,
                                 sp_table* az, sp_table* bz, sp_table* cz) {
+  if (int rc = refuse_row_only(s, "multiply_vec_incremental")) return rc;
   sp_table* outs[3] = {az, bz, cz};
   const sp_table* base[3] = {caz, cbz, ccz};
   return spmv3(c, s, s->filtered, s->nnz_filtered, z, base, outs, "spmv_incremental");
@@ -633,6 +940,7 @@ int sp_multiply_vec_incremental(sp_ctx* c, const sp_shape* s, const sp_table* z,
 
 int sp_multiply_vec_incremental_round0(sp_ctx* c, const sp_shape* s, const sp_table* z, const sp_table* caz, const sp_table* cbz, const sp_table* ccz, sp_table* az,
                                        sp_table* bz, sp_table* cz, sp_table* p0, sp_table* p1) {
+  if (int rc = refuse_row_only(s, "multiply_vec_incremental_round0")) return rc;
   const size_t nrows = s->dims.num_cons, half = nrows / 2;
   if (nrows < 2) return fail(SP_ERR_INVALID_INPUT_LENGTH, "multiply_vec_incremental_round0: needs at least two rows");
   if (p0->cap < half || p1->cap < half) return fail(SP_ERR_INVALID_INPUT_LENGTH, "multiply_vec_incremental_round0: product tables too short");
@@ -647,6 +955,7 @@ int sp_multiply_vec_incremental_round0(sp_ctx* c, const sp_shape* s, const sp_ta
 }
 
 int sp_poly_abc(sp_ctx* c, const sp_shape* s, const sp_table* rx, const uint64_t r_[4], size_t out_len, sp_table* out) {
+  if (int rc = refuse_row_only(s, "poly_ABC")) return rc;
   if (rx->len != s->dims.num_cons) return fail(SP_ERR_INVALID_INPUT_LENGTH, "poly_ABC: rx must have num_cons elements");
   if (out_len < s->num_cols || out->cap < out_len) return fail(SP_ERR_INVALID_INPUT_LENGTH, "poly_ABC: output too short");
   spk::PolyAbcArgs a;
@@ -682,6 +991,7 @@ int sp_poly_abc(sp_ctx* c, const sp_shape* s, const sp_table* rx, const uint64_t
 size_t sp_poly_abc_batch_chunk(void) { return (size_t)spk::PAB_KC; }
 int sp_poly_abc_batch(sp_ctx* c, const sp_shape* s, size_t count, const uint64_t* r_x, size_t ell, const uint64_t* r_, size_t out_len, sp_table* const* out) {
   if (!c || !s || (count && ((ell && !r_x) || !r_ || !out))) return fail(SP_ERR_INVALID_INPUT_LENGTH, "poly_abc_batch: null argument");
+  if (int rc = refuse_row_only(s, "poly_abc_batch")) return rc;
   if (count == 0) return SP_OK;
   const size_t nrows = s->dims.num_cons;
   if (ell > (size_t)spk::PAB_MAX_ELL || ((size_t)1 << ell) != nrows) return fail(SP_ERR_INVALID_INPUT_LENGTH, "poly_abc_batch: r_x must have log2(num_cons) coordinates");

@@ -59,11 +59,6 @@ struct sp_wire {
   void u64(uint64_t v) { put(&v, 8); }
 };
 
-struct sp_unwire {
-  const uint8_t *p, *end;
-  size_t left() const { return (size_t)(end - p); }
-};
-
 namespace {
 
 inline fe_t load_fe(const uint64_t* w) {
@@ -333,6 +328,33 @@ int sp_unwire_points(sp_unwire* r, size_t n, uint64_t* out) {  // {x, y, z}: any
   }
   return SP_OK;
 }
+// HyraxCommitmentKey / HyraxVerifierKey { num_cols, ck: Vec<Affine>, h: GE }: the inverse of sp_wire_hyrax_key. ck == NULL: *num_cols alone, nothing consumed.
+int sp_unwire_hyrax_key(sp_unwire* r, uint64_t* ck, size_t cap, size_t* num_cols, uint64_t* h) {
+  if (!r || !num_cols || (ck && !h)) return fail(SP_ERR_INVALID_INPUT_LENGTH, "sp_unwire_hyrax_key: null argument");
+  const uint8_t* start = r->p;
+  uint64_t nc;
+  size_t n;
+  int rc;
+  if ((rc = sp_unwire_u64s(r, 1, &nc)) || (rc = sp_unwire_len(r, 64, &n))) {
+    r->p = start;
+    return rc;
+  }
+  if (n != nc) {
+    r->p = start;
+    return fail(SP_ERR_INVALID_INPUT_LENGTH, "wire: a Hyrax key with " + std::to_string(n) + " generators for num_cols = " + std::to_string(nc));
+  }
+  *num_cols = n;
+  if (!ck) {
+    r->p = start;
+    return SP_OK;
+  }
+  if (cap < n) {
+    r->p = start;
+    return fail(SP_ERR_INVALID_INPUT_LENGTH, "sp_unwire_hyrax_key: generator buffer too small");
+  }
+  if ((rc = sp_unwire_affines(r, n, ck)) || (rc = sp_unwire_points(r, 1, h))) return rc;
+  return SP_OK;
+}
 int sp_unwire_done(const sp_unwire* r) {  // bincode's DefaultOptions reject trailing bytes
   if (!r || r->left() != 0) return fail(SP_ERR_INVALID_INPUT_LENGTH, "wire: trailing bytes");
   return SP_OK;
@@ -350,6 +372,49 @@ int sp_vk_digest(const sp_dims* dims, const sp_csr* A, const sp_csr* Bm, const s
   if (!rc) rc = sp_wire_digest(w, out);
   sp_wire_free(w);
   return rc;
+}
+
+// The same digest from the key's own bytes (bincode of SpartanVerifierKey { vk_ee, ck_s, S }): bincode(vk_ee) || bincode(ck_s) are the first bytes as they
+// stand, and S.write_bytes() (src/r1cs/mod.rs:775-794, src/r1cs/sparse.rs:398-417) is the ten dimensions, then per matrix the three lengths and cols
+// followed by the very data / indices / indptr bytes of the bincode form - a hash over slices of the input in another order; no element is converted or
+// checked (a key that fails its load never shows its digest). Host code without shared state: a driver runs it on a thread beside the device decode.
+int sp_vk_digest_from_wire(const uint8_t* bytes, size_t n, uint8_t out[32]) {
+  if (!bytes || !n || !out) return fail(SP_ERR_INVALID_INPUT_LENGTH, "sp_vk_digest_from_wire: null argument");
+  sp_unwire r{bytes, bytes + n};
+  int rc;
+  for (int k = 0; k < 2; ++k) {  // vk_ee, ck_s: num_cols, Vec<Affine>, GE
+    uint64_t nc;
+    size_t len;
+    if ((rc = sp_unwire_u64s(&r, 1, &nc)) || (rc = sp_unwire_len(&r, 64, &len))) return rc;
+    if (r.left() < 64 * len + 96) return fail(SP_ERR_INVALID_INPUT_LENGTH, "wire: unexpected end of input");
+    r.p += 64 * len + 96;
+  }
+  sp::Sha256 sha;
+  sha.update(bytes, (size_t)(r.p - bytes));
+  if (r.left() < 80) return fail(SP_ERR_INVALID_INPUT_LENGTH, "wire: unexpected end of input");
+  sha.update(r.p, 80);
+  r.p += 80;
+  for (int m = 0; m < 3; ++m) {
+    size_t nd, ni, np;
+    if ((rc = sp_unwire_len(&r, 32, &nd))) return rc;
+    const uint8_t* data = r.p;
+    r.p += 32 * nd;
+    if ((rc = sp_unwire_len(&r, 8, &ni))) return rc;
+    const uint8_t* idx = r.p;
+    r.p += 8 * ni;
+    if ((rc = sp_unwire_len(&r, 8, &np))) return rc;
+    const uint8_t* ptr = r.p;
+    r.p += 8 * np;
+    uint64_t head[4] = {nd, ni, np, 0};
+    if ((rc = sp_unwire_u64s(&r, 1, &head[3]))) return rc;
+    sha.update(head, sizeof head);
+    sha.update(data, 32 * nd);
+    sha.update(idx, 8 * ni);
+    sha.update(ptr, 8 * np);
+  }
+  if ((rc = sp_unwire_done(&r))) return rc;
+  sha.finish(out);
+  return SP_OK;
 }
 
 // ---- SpartanSNARK (src/spartan.rs:125-137) <-> the flat word layout of DESIGN.md section 4 ----------------------------------------------------

@@ -325,6 +325,12 @@ namespace sp {
 int wait_result_slot(sp_ctx* c, const fe_t* slot, unsigned want, int nvals, fe_t* v, long* spins);
 }
 
+// the byte source of the wire formats (capi_wire.hip); sp_shape_from_wire (capi_sparse.hip) takes the arrays of a matrix as slices of it
+struct sp_unwire {
+  const uint8_t *p, *end;
+  size_t left() const { return (size_t)(end - p); }
+};
+
 struct sp_table {
   sp_ctx* ctx = nullptr;
   fe_t* d = nullptr;

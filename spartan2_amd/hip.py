@@ -912,6 +912,48 @@ class _Dims(ctypes.Structure):
                                                "num_precommitted_unpadded", "num_rest_unpadded", "num_public", "num_challenges")]
 
 
+SHAPE_WIRE_DEVICE, SHAPE_WIRE_HOST, SHAPE_WIRE_FULL, SHAPE_WIRE_TIMED = 1, 2, 4, 8  # SP_SHAPE_WIRE_* (sp_shape_from_wire's flags)
+WIRE_STAGES = ("upload", "entries", "counts_scan", "scatter", "parse", "decode", "total", "device")
+
+
+def wire_stages() -> dict:
+    """sp_shape_from_wire_stages: ms of the calling thread's last sp_shape_from_wire by stage (the first four from device events, zero unless timed)"""
+    out = (ctypes.c_double * 8)()
+    lib().sp_shape_from_wire_stages(out)
+    return {k: float(v) for k, v in zip(WIRE_STAGES, out)}
+
+
+def wire_decode_constants() -> dict:
+    """compile-time constants of the decode kernels (kernels_wire_decode.hpp) and the default decode form, read from the library"""
+    L = lib()
+    L.sp_shape_wire_block.restype = L.sp_shape_wire_scan_tile.restype = ctypes.c_size_t
+    return {"block": int(L.sp_shape_wire_block()), "scan_tile": int(L.sp_shape_wire_scan_tile()), "device_default": bool(L.sp_shape_wire_device_default())}
+
+
+def vk_digest_from_wire(data) -> bytes:
+    """sp_vk_digest_from_wire: DigestHelperTrait::digest of a SpartanVerifierKey from its own bincode bytes (host code; no context)"""
+    buf = np.frombuffer(bytes(data), dtype=np.uint8)
+    out = np.zeros(32, dtype=np.uint8)
+    check(lib().sp_vk_digest_from_wire(p8(buf) if len(buf) else None, ctypes.c_size_t(len(buf)), p8(out)))
+    return out.tobytes()
+
+
+def unwire_hyrax_key(data):
+    """sp_unwire_hyrax_key on `data` (which must hold exactly one key): -> (ck (num_cols, 8) uint64, h (8,) uint64) as Montgomery limbs"""
+    buf = np.frombuffer(bytes(data), dtype=np.uint8)
+    r = ctypes.c_void_p()
+    check(lib().sp_unwire_new(p8(buf) if len(buf) else None, ctypes.c_size_t(len(buf)), ctypes.byref(r)))
+    try:
+        n = ctypes.c_size_t(0)
+        check(lib().sp_unwire_hyrax_key(r, None, ctypes.c_size_t(0), ctypes.byref(n), None))
+        ck, h = np.zeros((max(n.value, 1), 8), dtype=np.uint64), np.zeros(8, dtype=np.uint64)
+        check(lib().sp_unwire_hyrax_key(r, p64(ck), ctypes.c_size_t(n.value), ctypes.byref(n), p64(h)))
+        check(lib().sp_unwire_done(r))
+        return ck[: n.value], h
+    finally:
+        lib().sp_unwire_free(r)
+
+
 class Shape:
     """SplitR1CSShape on the device. mats: 3 x (data F (nnz,4) uint64, indices uint32, indptr uint64) in the padded layout."""
 
@@ -982,6 +1024,43 @@ class Shape:
         arr = (ctypes.c_void_p * max(n, 1))(*[t.h for t in outs])
         check(lib().sp_poly_abc_batch(self.ctx.h, self.h, ctypes.c_size_t(n), p64(r_x) if n else None, ctypes.c_size_t(r_x.shape[1]), p64(r) if n else None,
                                       ctypes.c_size_t(out_len), arr))
+
+    @classmethod
+    def from_wire(cls, ctx, data, device_decode=None, full=False, timed=False):
+        """sp_shape_from_wire: the shape from the bincode bytes of SplitR1CSShape (what sp_wire_shape(.., 0) writes; trailing bytes are refused).
+        device_decode: True / False forces the device / host decode, None takes the library's default; full=True asks for the full shape of Shape(...)
+        through the host decode - without it the shape is row-only (multiply_vec*, matrix_evals_batched and is_sat work, poly_abc* and
+        multiply_vec_incremental* raise "row-only shape"). .dims is read from the bytes; .stages the call's times (wire_stages())."""
+        flags = SHAPE_WIRE_FULL if full else 0
+        if device_decode is not None:
+            flags |= SHAPE_WIRE_DEVICE if device_decode else SHAPE_WIRE_HOST
+        if timed:
+            flags |= SHAPE_WIRE_TIMED
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
+        r = ctypes.c_void_p()
+        check(lib().sp_unwire_new(p8(buf) if len(buf) else None, ctypes.c_size_t(len(buf)), ctypes.byref(r)))
+        self = cls.__new__(cls)
+        self.ctx, self._keep, self.h = ctx, [], ctypes.c_void_p()
+        dd = _Dims()
+        try:
+            check(lib().sp_shape_from_wire(ctx.h if ctx is not None else None, r, ctypes.c_uint(flags), ctypes.byref(dd), ctypes.byref(self.h)))
+            try:
+                check(lib().sp_unwire_done(r))
+            except SpartanHipError:
+                lib().sp_shape_free(self.h)
+                self.h = ctypes.c_void_p()
+                raise
+        finally:
+            lib().sp_unwire_free(r)
+        self.dims = {n: int(getattr(dd, n)) for n, _ in _Dims._fields_}
+        self.stages = wire_stages()
+        return self
+
+    def info(self) -> dict:
+        """sp_shape_info: entry counts of the structures the shape holds (zeros for those a row-only shape does not)"""
+        si = (ctypes.c_uint64 * 8)()
+        check(lib().sp_shape_info(self.h, si))
+        return {"nnz": [int(si[i]) for i in range(3)], "nnz_filtered": [int(si[3 + i]) for i in range(3)], "long_columns": int(si[6]), "short_columns": int(si[7])}
 
     def __del__(self):
         try:

@@ -424,6 +424,22 @@ class SpartanSNARK:
         _check(lib().ss_proof_to_bytes(self.pk, hip.p64(words), ctypes.c_size_t(len(words)), hip.p8(out), ctypes.c_size_t(n.value), ctypes.byref(n)))
         return out.tobytes()
 
+    def vk_to_bytes(self) -> bytes:
+        """The key's SpartanVerifierKey { vk_ee, ck_s, S } (src/spartan.rs:62-70) as bincode bytes (ss_vk_to_bytes): what SpartanVerifier.from_bytes loads.
+        The circuit is handed to the library again (setup keeps no copy of it) and the bytes are returned only if they hash to this key's digest."""
+        args, keep = _inst_args(self.inst)
+        fn = lib().ss_vk_to_bytes
+        fn.restype = ctypes.c_long
+        n = fn(self.pk, *args, None, ctypes.c_size_t(0))
+        if n < 0:
+            _check(n)
+        out = np.zeros(max(n, 1), dtype=np.uint8)
+        got = fn(self.pk, *args, hip.p8(out), ctypes.c_size_t(n))
+        if got < 0:
+            _check(got)
+        assert got == n, (got, n)
+        return out[:n].tobytes()
+
     def verify_bytes(self, data: bytes) -> int:
         """verify() on a serialised proof: 0 = accept, 1..6 = failed check (1 also for bytes that do not decode to a proof of this key's shape)."""
         arr = np.frombuffer(bytes(data), dtype=np.uint8).copy() if len(data) else np.zeros(1, dtype=np.uint8)
@@ -478,6 +494,61 @@ class SpartanSNARK:
             self._sha_plan = None
         if self.pk:
             lib().ss_pk_free(self.pk)
+            self.pk = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class SpartanVerifier:
+    """A verifier's key loaded from the bincode bytes of SpartanVerifierKey (ss_verifier_from_bytes): no circuit, no frontend, no setup. It holds the two
+    commitment keys, the row-major matrix structures and the digest - what verify reads - and verifies with the code SpartanSNARK's methods run."""
+
+    def __init__(self):
+        raise TypeError("use SpartanVerifier.from_bytes(ctx, data)")
+
+    @classmethod
+    def from_bytes(cls, ctx: hip.Context, data, device_decode=None, timed=False):
+        """data: SpartanSNARK.vk_to_bytes() (or the oracle's vk_bytes()). device_decode: True / False forces the device / host decode of the matrices,
+        None takes the measured default. Raises on bytes that are not a key (short, trailing, inconsistent, off-curve, non-canonical ...)."""
+        flags = 0 if device_decode is None else (hip.SHAPE_WIRE_DEVICE if device_decode else hip.SHAPE_WIRE_HOST)
+        if timed:
+            flags |= hip.SHAPE_WIRE_TIMED
+        buf = np.frombuffer(bytes(data), dtype=np.uint8) if data is not None else None
+        self = cls.__new__(cls)
+        self.ctx = ctx
+        self.pk = ctypes.c_void_p()
+        _check(lib().ss_verifier_from_bytes(ctx.h if ctx is not None else None, hip.p8(buf) if buf is not None and len(buf) else None,
+                                            ctypes.c_size_t(len(buf) if buf is not None else 0), ctypes.c_uint(flags), ctypes.byref(self.pk)))
+        self.stages = hip.wire_stages()  # of the shape's decode; .load_stages: of the whole load
+        st = (ctypes.c_double * 8)()
+        lib().ss_verifier_stages(st)
+        self.load_stages = {k: float(v) for k, v in zip(("hyrax_keys", "shape", "ck_create", "digest", "digest_wait", "total"), st)}
+        d = (ctypes.c_uint64 * 10)()
+        dig = np.zeros(32, dtype=np.uint8)
+        lib().ss_pk_info(self.pk, d, hip.p8(dig))
+        self.dims = {k: int(v) for k, v in zip(DIM_NAMES, d)}
+        self.vk_digest = dig
+        si = (ctypes.c_uint64 * 8)()
+        _check(lib().ss_pk_shape_info(self.pk, si))
+        self.shape_info = {"nnz": [int(si[i]) for i in range(3)], "nnz_filtered": [int(si[3 + i]) for i in range(3)], "long_columns": int(si[6]),
+                           "short_columns": int(si[7])}
+        return self
+
+    verify = SpartanSNARK.verify
+    verify_bytes = SpartanSNARK.verify_bytes
+    _verify_batch = SpartanSNARK._verify_batch
+    verify_batch = SpartanSNARK.verify_batch
+    verify_bytes_batch = SpartanSNARK.verify_bytes_batch
+    proof_layout = SpartanSNARK.proof_layout
+    proof_to_bytes = SpartanSNARK.proof_to_bytes
+
+    def close(self):
+        if getattr(self, "pk", None):
+            lib().ss_verifier_free(self.pk)
             self.pk = None
 
     def __del__(self):

@@ -51,27 +51,33 @@ inline size_t log2_ceil(size_t n) {
 }
 
 // SplitR1CSShape::new (src/r1cs/mod.rs:810-911)
-inline PaddedShape pad_shape(const R1CSIntView& R) {
+// the ten dimensions it gives a circuit of these sizes (:810-854): what a loaded key's dimensions are checked against
+inline sp_dims padded_dims(size_t num_cons, size_t num_shared, size_t num_precommitted, size_t num_rest, size_t num_public, size_t num_challenges) {
   const size_t width = DEFAULT_COMMITMENT_WIDTH;
-  size_t sp_ = pad_to_width(width, R.num_shared), pp = pad_to_width(width, R.num_precommitted), rp = pad_to_width(width, R.num_rest);
+  size_t sp_ = pad_to_width(width, num_shared), pp = pad_to_width(width, num_precommitted), rp = pad_to_width(width, num_rest);
   size_t nvp = sp_ + pp + rp;
-  if (nvp < R.num_public + R.num_challenges + 1) rp = std::max(R.num_public + R.num_challenges + 1, nvp) - (sp_ + pp);
+  if (nvp < num_public + num_challenges + 1) rp = std::max(num_public + num_challenges + 1, nvp) - (sp_ + pp);
   nvp = sp_ + pp + rp;
   if (next_pow2(nvp) != nvp) rp = next_pow2(nvp) - (sp_ + pp);
-  nvp = sp_ + pp + rp;
-  const size_t num_vars = R.num_shared + R.num_precommitted + R.num_rest;
-  const size_t ncp = next_pow2(R.num_cons);
+  sp_dims d;
+  d.num_cons = next_pow2(num_cons);
+  d.num_cons_unpadded = num_cons;
+  d.num_shared = sp_;
+  d.num_precommitted = pp;
+  d.num_rest = rp;
+  d.num_shared_unpadded = num_shared;
+  d.num_precommitted_unpadded = num_precommitted;
+  d.num_rest_unpadded = num_rest;
+  d.num_public = num_public;
+  d.num_challenges = num_challenges;
+  return d;
+}
+inline PaddedShape pad_shape(const R1CSIntView& R) {
   PaddedShape P;
-  P.dims.num_cons = ncp;
-  P.dims.num_cons_unpadded = R.num_cons;
-  P.dims.num_shared = sp_;
-  P.dims.num_precommitted = pp;
-  P.dims.num_rest = rp;
-  P.dims.num_shared_unpadded = R.num_shared;
-  P.dims.num_precommitted_unpadded = R.num_precommitted;
-  P.dims.num_rest_unpadded = R.num_rest;
-  P.dims.num_public = R.num_public;
-  P.dims.num_challenges = R.num_challenges;
+  P.dims = padded_dims(R.num_cons, R.num_shared, R.num_precommitted, R.num_rest, R.num_public, R.num_challenges);
+  const size_t sp_ = P.dims.num_shared, pp = P.dims.num_precommitted, nvp = sp_ + pp + P.dims.num_rest;
+  const size_t num_vars = R.num_shared + R.num_precommitted + R.num_rest;
+  const size_t ncp = P.dims.num_cons;
   // small coefficient cache: the SHA circuits only use +-2^k
   for (int m = 0; m < 3; ++m) {
     const size_t nnz = R.m[m].indptr[R.num_cons];

@@ -29,6 +29,9 @@ struct SpartanProverKey {  // src/spartan.rs:30-58
   size_t num_vars = 0, num_extra = 0, num_cols = 0;
   uint8_t vk_digest[32];
   std::vector<aff_t> gens, gens_s;
+  // a SpartanVerifierKey loaded from its bytes (verifier_from_bytes): S holds the row-major structures alone. verify, verify_batch and the byte forms
+  // read nothing else of a key; the C surface refuses such a key at every prover entry point ("verifier-only key")
+  bool verifier_only = false;
   // verify()'s device workspaces (T_x, T_y, the three products M T_y): allocated by the first verify on this key and kept - five hipMalloc / hipFree
   // pairs of 32-64 MB were half of a 3.3 ms verify. One verify at a time per key (as for every handle of the ABI).
   mutable sp_table *v_Tx = nullptr, *v_Ty = nullptr, *v_mv[3] = {nullptr, nullptr, nullptr};
@@ -162,6 +165,99 @@ SpartanProverKey* setup(sp_ctx* ctx, const R1CSIntView& R) {
 }
 
 static double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+// ---- SpartanVerifierKey { vk_ee, ck_s, S } (src/spartan.rs:62-70) to and from its bincode bytes -----------------------------------------------------------
+// Writing: setup keeps neither the circuit nor the padded CSR (its time and memory stay what they were), so the caller hands the circuit again; the stream is
+// sp_wire_hyrax_key(ck), sp_wire_hyrax_key(ck_s), sp_wire_shape(.., 0) over the re-padded circuit, and it is returned only if it hashes to the key's digest -
+// another circuit than the one the key was set up from is refused.
+std::vector<uint8_t> vk_to_bytes(const SpartanProverKey& pk, const R1CSIntView& R) {
+  if (pk.verifier_only) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "vk_to_bytes: verifier-only key (it was loaded from its bytes: keep those)");
+  PaddedShape P = pad_shape(R);
+  sp_csr cs[3];
+  padded_csr(P, cs);
+  sp_wire* w = nullptr;
+  ck(sp_wire_new(0, &w), "wire_new");
+  std::unique_ptr<sp_wire, void (*)(sp_wire*)> guard(w, sp_wire_free);
+  ck(sp_wire_hyrax_key(w, u64p(&pk.gens[0].x), pk.gens.size() - 1, u64p(&pk.gens.back().x)), "wire vk_ee");
+  ck(sp_wire_hyrax_key(w, u64p(&pk.gens_s[0].x), pk.gens_s.size() - 1, u64p(&pk.gens_s.back().x)), "wire ck_s");
+  ck(sp_wire_shape(w, &P.dims, &cs[0], &cs[1], &cs[2], 0), "wire S");
+  std::vector<uint8_t> out(sp_wire_len(w));
+  ck(sp_wire_bytes(w, out.data(), out.size()), "wire_bytes");
+  uint8_t dig[32];
+  ck(sp_vk_digest_from_wire(out.data(), out.size(), dig), "vk digest of the written bytes");
+  if (memcmp(dig, pk.vk_digest, 32) != 0) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "vk_to_bytes: the circuit is not the one this key was set up from (digest mismatch)");
+  return out;
+}
+// the length of that stream from the circuit's sizes alone (the sizing pass of the two-pass protocol)
+size_t vk_bytes_len(const SpartanProverKey& pk, const R1CSIntView& R) {
+  const size_t rows = next_pow2(R.num_cons);
+  size_t n = (8 + 8 + 64 * (pk.gens.size() - 1) + 96) + (8 + 8 + 64 * (pk.gens_s.size() - 1) + 96) + 80;
+  for (int m = 0; m < 3; ++m) n += 8 + 40 * (size_t)R.m[m].indptr[R.num_cons] + 8 + 8 + 8 * (rows + 1) + 8;
+  return n;
+}
+
+// Reading: the two Hyrax keys (sp_unwire_hyrax_key), the shape (sp_shape_from_wire: row-only, decode form by `flags` = SP_SHAPE_WIRE_*), no trailing bytes,
+// the ten dimensions those SplitR1CSShape::new gives a circuit of the unpadded sizes; the digest is hashed from the bytes on a helper thread under the
+// device work. The key is a SpartanProverKey marked verifier_only: what verify and verify_batch read of a key, and nothing else.
+// host wall-clock of the calling thread's last verifier_from_bytes, ms (ss_verifier_stages): the two Hyrax keys read, sp_shape_from_wire, the two
+// sp_ck_create, the digest on its helper thread, the wait for it behind everything else, the whole call
+static thread_local double g_vk_stage_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+SpartanProverKey* verifier_from_bytes(sp_ctx* ctx, const uint8_t* bytes, size_t n, unsigned flags) {
+  for (double& x : g_vk_stage_ms) x = 0;
+  const double t_start = now_ms();
+  if (!ctx || !bytes || n == 0) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "verifier_from_bytes: null context, null bytes or no bytes");
+  if (flags & SP_SHAPE_WIRE_FULL) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "verifier_from_bytes: a verifier's key holds the row-only shape");
+  auto pk = std::make_unique<SpartanProverKey>();
+  pk->ctx = ctx;
+  pk->verifier_only = true;
+  ck(sp_ctx_bind_thread(ctx), "device");
+  sp_unwire* r = nullptr;
+  ck(sp_unwire_new(bytes, n, &r), "unwire_new");
+  std::unique_ptr<sp_unwire, void (*)(sp_unwire*)> guard(r, sp_unwire_free);
+  auto read_key = [&](std::vector<aff_t>& gens, size_t want_cols, const char* what) {
+    size_t nc = 0;
+    ck(sp_unwire_hyrax_key(r, nullptr, 0, &nc, nullptr), what);
+    if (nc != want_cols) throw Error(SP_ERR_INVALID_INPUT_LENGTH, std::string(what) + ": num_cols is " + std::to_string(nc) + ", this build's is " + std::to_string(want_cols));
+    gens.resize(nc + 1);
+    ck(sp_unwire_hyrax_key(r, u64p(&gens[0].x), nc, &nc, u64p(&gens[nc].x)), what);
+  };
+  read_key(pk->gens, DEFAULT_COMMITMENT_WIDTH, "verifier_from_bytes: vk_ee");
+  read_key(pk->gens_s, 1, "verifier_from_bytes: ck_s");
+  const double t_keys = now_ms();
+  // the digest needs the bytes alone
+  double digest_ms = 0;
+  std::future<int> digest = std::async(std::launch::async, [&] {
+    const double t0 = now_ms();
+    const int rc = sp_vk_digest_from_wire(bytes, n, pk->vk_digest);
+    digest_ms = now_ms() - t0;
+    return rc;
+  });
+  struct Join {
+    std::future<int>& f;
+    ~Join() {
+      if (f.valid()) f.wait();
+    }
+  } join{digest};
+  ck(sp_shape_from_wire(ctx, r, flags, &pk->dims, &pk->S), "shape_from_wire");
+  ck(sp_unwire_done(r), "verifier_from_bytes");
+  const double t_shape = now_ms();
+  const sp_dims& d = pk->dims;
+  const sp_dims want = padded_dims(d.num_cons_unpadded, d.num_shared_unpadded, d.num_precommitted_unpadded, d.num_rest_unpadded, d.num_public, d.num_challenges);
+  if (memcmp(&want, &d, sizeof d) != 0) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "verifier_from_bytes: the ten dimensions are not those SplitR1CSShape::new gives the unpadded sizes");
+  pk->num_vars = d.num_shared + d.num_precommitted + d.num_rest;
+  pk->layout = SpartanLayout(d, pk->num_vars);
+  pk->num_extra = 1 + d.num_public + d.num_challenges;
+  pk->num_cols = pk->num_vars + pk->num_extra;
+  ck(sp_ck_create(ctx, u64p(&pk->gens[0].x), DEFAULT_COMMITMENT_WIDTH, u64p(&pk->gens[DEFAULT_COMMITMENT_WIDTH].x), &pk->ck), "ck_create");
+  ck(sp_ck_create(ctx, u64p(&pk->gens_s[0].x), 1, u64p(&pk->gens_s[1].x), &pk->ck_s), "ck_s_create");
+  const double t_ck = now_ms();
+  const int drc = digest.get();
+  if (drc != SP_OK) throw Error(drc, "verifier_from_bytes: the digest pass could not walk the bytes");
+  const double t_end = now_ms();
+  const double st[6] = {t_keys - t_start, t_shape - t_keys, t_ck - t_shape, digest_ms, t_end - t_ck, t_end - t_start};
+  std::copy(st, st + 6, g_vk_stage_ms);
+  return pk.release();
+}
 
 // ---- SpartanSNARK::prep_prove (src/spartan.rs:176-216) for `count` states of one key in one pass -------------------------------------------------------
 // ONE driver behind every witness source and every count. `fill_W` writes the witness segments into the zeroed tables W[0 .. count) (each segment at its
@@ -2059,6 +2155,13 @@ static int catch_all() {
   }
 }
 
+// the prover entry points take the key through this: a key loaded from its bytes holds none of the prover's structures
+static SpartanProverKey& prover_key(void* pk, const char* who) {
+  auto* k = (SpartanProverKey*)pk;
+  if (k && k->verifier_only) throw Error(SP_ERR_INVALID_INPUT_LENGTH, std::string(who) + ": verifier-only key (loaded by ss_verifier_from_bytes; proving takes the key of ss_setup)");
+  return *k;
+}
+
 extern "C" {
 const char* ss_last_error() { return g_err.c_str(); }
 void ss_set_error(const char* msg) { g_err = msg; }
@@ -2105,6 +2208,41 @@ int ss_setup(sp_ctx* ctx, size_t num_cons, size_t num_shared, size_t num_precomm
   }
 }
 void ss_pk_free(void* pk) { delete (SpartanProverKey*)pk; }
+// The key's SpartanVerifierKey as bincode bytes (see vk_to_bytes): the circuit arguments of ss_setup again. Two passes: out == NULL returns the length,
+// otherwise the bytes are written (cap must hold them) and the length returned; < 0 = error (ss_last_error), among them a circuit other than the key's.
+long ss_vk_to_bytes(void* pk, size_t num_cons, size_t num_shared, size_t num_precommitted, size_t num_rest, size_t num_public, size_t num_challenges, const int64_t* Ad,
+                    const uint32_t* Ai, const uint64_t* Ap, const int64_t* Bd, const uint32_t* Bi, const uint64_t* Bp, const int64_t* Cd, const uint32_t* Ci,
+                    const uint64_t* Cp, uint8_t* out, size_t cap) {
+  try {
+    if (!pk) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "ss_vk_to_bytes: null key");
+    const R1CSIntView R = make_view(num_cons, num_shared, num_precommitted, num_rest, num_public, num_challenges, Ad, Ai, Ap, Bd, Bi, Bp, Cd, Ci, Cp);
+    const SpartanProverKey& key = prover_key(pk, "ss_vk_to_bytes");
+    if (!out) return (long)vk_bytes_len(key, R);
+    const std::vector<uint8_t> b = vk_to_bytes(key, R);
+    if (cap < b.size()) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "ss_vk_to_bytes: buffer too small");
+    memcpy(out, b.data(), b.size());
+    return (long)b.size();
+  } catch (...) {
+    return catch_all();
+  }
+}
+// A verifier's key from those bytes (see verifier_from_bytes). flags: 0, or SP_SHAPE_WIRE_DEVICE / SP_SHAPE_WIRE_HOST to force a decode form, and
+// SP_SHAPE_WIRE_TIMED. The key is taken by ss_verify, ss_verify_bytes, ss_verify_batch, ss_verify_bytes_batch, ss_pk_info, ss_pk_shape_info,
+// ss_proof_layout, ss_proof_words and ss_proof_to_bytes; every prover entry point refuses it ("verifier-only key"). ss_verifier_free (= ss_pk_free) ends it.
+int ss_verifier_from_bytes(sp_ctx* ctx, const uint8_t* bytes, size_t n, unsigned flags, void** out_vk) {
+  try {
+    if (!out_vk) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "ss_verifier_from_bytes: null out");
+    *out_vk = nullptr;
+    *out_vk = verifier_from_bytes(ctx, bytes, n, flags);
+    return 0;
+  } catch (...) {
+    return catch_all();
+  }
+}
+void ss_verifier_free(void* vk) { delete (SpartanProverKey*)vk; }
+// ms of the calling thread's last ss_verifier_from_bytes: Hyrax keys read, sp_shape_from_wire, the two sp_ck_create, the digest (helper thread), the wait
+// for the digest behind the rest, the whole call; two spare slots
+void ss_verifier_stages(double out[8]) { memcpy(out, g_vk_stage_ms, sizeof g_vk_stage_ms); }
 int ss_pk_shape_info(void* pk_, uint64_t out[8]) { return sp_shape_info(((SpartanProverKey*)pk_)->S, out); }
 void ss_pk_info(void* pk_, uint64_t dims_out[10], uint8_t digest[32]) {
   auto* pk = (SpartanProverKey*)pk_;
@@ -2114,7 +2252,7 @@ void ss_pk_info(void* pk_, uint64_t dims_out[10], uint8_t digest[32]) {
 int ss_prep_prove(void* pk, const uint64_t* witness_u64, size_t n, int is_small, const uint8_t* tape, size_t tape_blocks, size_t* tape_used, void** out_ps) {
   try {
     Tape t{tape, tape_blocks};
-    *out_ps = prep_prove(*(SpartanProverKey*)pk, witness_u64, n, is_small != 0, t);
+    *out_ps = prep_prove(prover_key(pk, "ss_prep_prove"), witness_u64, n, is_small != 0, t);
     if (tape_used) *tape_used = t.pos;
     return 0;
   } catch (...) {
@@ -2126,7 +2264,7 @@ int ss_prep_prove_sha256(void* pk, const sp_sha256_plan* plan, const uint8_t* ms
                          void** out_ps, uint64_t out_publics[256]) {
   try {
     Tape t{tape, tape_blocks};
-    *out_ps = prep_prove_sha256(*(SpartanProverKey*)pk, plan, msg, len, is_small != 0, t, out_publics);
+    *out_ps = prep_prove_sha256(prover_key(pk, "ss_prep_prove_sha256"), plan, msg, len, is_small != 0, t, out_publics);
     if (tape_used) *tape_used = t.pos;
     return 0;
   } catch (...) {
@@ -2150,7 +2288,7 @@ int ss_prep_prove_batch_opts(void* pk, const uint64_t* const* witnesses_u64, siz
       if (!tapes[k]) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "prep_prove_batch: state " + std::to_string(k) + ": null tape");
       ts.push_back(Tape{tapes[k], tape_blocks[k]});
     }
-    std::vector<SpartanPrepSNARK*> st = prep_prove_batch(*(SpartanProverKey*)pk, witnesses_u64, n_witness, count, is_small != 0, ts.data(), flags, phase_ms);
+    std::vector<SpartanPrepSNARK*> st = prep_prove_batch(prover_key(pk, "ss_prep_prove_batch"), witnesses_u64, n_witness, count, is_small != 0, ts.data(), flags, phase_ms);
     for (size_t k = 0; k < count; ++k) {
       out_ps[k] = st[k];
       if (tape_used) tape_used[k] = ts[k].pos;
@@ -2175,7 +2313,7 @@ int ss_prep_prove_sha256_batch_opts(void* pk, const sp_sha256_plan* plan, const 
       if (!tapes[k]) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "prep_prove_batch: state " + std::to_string(k) + ": null tape");
       ts.push_back(Tape{tapes[k], tape_blocks[k]});
     }
-    std::vector<SpartanPrepSNARK*> st = prep_prove_sha256_batch(*(SpartanProverKey*)pk, plan, msgs, len, count, is_small != 0, ts.data(), out_publics, flags, phase_ms);
+    std::vector<SpartanPrepSNARK*> st = prep_prove_sha256_batch(prover_key(pk, "ss_prep_prove_sha256_batch"), plan, msgs, len, count, is_small != 0, ts.data(), out_publics, flags, phase_ms);
     for (size_t k = 0; k < count; ++k) {
       out_ps[k] = st[k];
       if (tape_used) tape_used[k] = ts[k].pos;
@@ -2223,11 +2361,12 @@ int ss_prep_export(void* pk_, void* ps_, uint64_t* comm_rows, uint64_t* caz, uin
 int ss_prep_is_sat(void* pk, void* ps, const uint64_t* publics_u64, size_t npub, const uint64_t* challenges, ss_rest_hook synth, void* synth_user,
                    const uint64_t* expect_comm_rows, sp_sat_report* report, uint64_t* bad_rows, size_t bad_rows_cap, size_t* n_bad_rows) {
   try {
+    prover_key(pk, "ss_prep_is_sat");
     if (!ps) throw Error(SP_ERR_INTERNAL, "is_sat before prep_prove");
     sp_sat_report local;
     std::vector<uint64_t> bad;
     const char* reason = nullptr;
-    const bool ok = is_sat(*(SpartanProverKey*)pk, *(SpartanPrepSNARK*)ps, publics_u64, npub, challenges, synth, synth_user, expect_comm_rows, report ? report : &local, &bad, &reason);
+    const bool ok = is_sat(prover_key(pk, "ss_prep_is_sat"), *(SpartanPrepSNARK*)ps, publics_u64, npub, challenges, synth, synth_user, expect_comm_rows, report ? report : &local, &bad, &reason);
     if (n_bad_rows) *n_bad_rows = bad.size();
     if (bad_rows) std::copy(bad.begin(), bad.begin() + std::min(bad.size(), bad_rows_cap), bad_rows);
     if (ok) return 0;
@@ -2326,7 +2465,7 @@ int ss_prove_hook(void* pk, void* ps, const uint64_t* publics_u64, size_t npub, 
   try {
     Tape t{tape, tape_blocks};
     PhaseTimes pt;
-    ProofBuf pf = prove(*(SpartanProverKey*)pk, *(SpartanPrepSNARK*)ps, publics_u64, npub, t, &pt, synth, synth_user);
+    ProofBuf pf = prove(prover_key(pk, "ss_prove"), *(SpartanPrepSNARK*)ps, publics_u64, npub, t, &pt, synth, synth_user);
     if (pf.words.size() > out_cap) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "proof buffer too small");
     memcpy(out_words, pf.words.data(), pf.words.size() * 8);
     if (tape_used) *tape_used = t.pos;
@@ -2359,7 +2498,7 @@ int ss_prove_batch_opts(void* pk, void* const* pss, size_t count, const uint64_t
     std::vector<Tape> ts;
     for (size_t k = 0; k < count; ++k) ts.push_back(Tape{tapes[k], tape_blocks[k]});
     PhaseTimes pt;
-    std::vector<ProofBuf> pf = prove_batch(*(SpartanProverKey*)pk, (SpartanPrepSNARK* const*)pss, count, publics_u64, npub, ts.data(), &pt, flags);
+    std::vector<ProofBuf> pf = prove_batch(prover_key(pk, "ss_prove_batch"), (SpartanPrepSNARK* const*)pss, count, publics_u64, npub, ts.data(), &pt, flags);
     for (size_t k = 0; k < count; ++k) {
       if (pf[k].words.size() > out_cap_each) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "proof buffer too small");
       memcpy(out_words + k * out_cap_each, pf[k].words.data(), pf[k].words.size() * 8);
@@ -2448,7 +2587,7 @@ int ss_prove_multiplexed(void** pks, void** pss, size_t n_ctx, const uint64_t* p
     std::vector<Fiber> fibers(n_ctx);
     std::vector<Scheduler> sched(threads);
     for (size_t i = 0; i < n_ctx; ++i) {
-      auto* pk = (SpartanProverKey*)pks[i];
+      auto* pk = &prover_key(pks[i], "ss_prove_multiplexed");
       auto* ps = (SpartanPrepSNARK*)pss[i];
       uint64_t* dst = out_words + i * words_cap;
       fibers[i].body = [=] {

@@ -292,6 +292,13 @@ int sp_shape_info(const sp_shape* s, uint64_t out[8]);
 #define SP_SHAPE_WIRE_HOST 2
 #define SP_SHAPE_WIRE_FULL 4
 #define SP_SHAPE_WIRE_TIMED 8
+/* SP_SHAPE_WIRE_FULL_DEVICE = the full shape of sp_shape_from_csr (row_only == false) built on the device: behind the row decode, filtered[] is the same
+ * count / scan / scatter with the filter as predicate; col[] comes from per-column counters (integer atomic sums), the walk order the host derives from the
+ * six counters of every column (O(columns): it touches no per-entry array), a stable radix sort of the entry numbers by walk position and one lane a sorted
+ * entry. Every device array is word for word sp_shape_from_csr's for the same matrices (sp_shape_compare), under each of the SPARTAN_POLYABC_ORDER / _LAYOUT /
+ * _WINDOW settings - the device path serves all of them. It excludes SP_SHAPE_WIRE_DEVICE, _HOST and _FULL (SP_SHAPE_WIRE_FULL alone stays the host decode)
+ * and combines with SP_SHAPE_WIRE_TIMED (sp_shape_from_wire_full_stages). The refusals of the row decode hold as they are. */
+#define SP_SHAPE_WIRE_FULL_DEVICE 16
 typedef struct sp_unwire sp_unwire;
 int sp_shape_from_wire(sp_ctx* ctx, sp_unwire* r, unsigned flags, sp_dims* dims_out, sp_shape** out);
 /* the last sp_shape_from_wire of the calling thread, ms: upload, entry kernel, counts + scan, scatter (device events; zero without SP_SHAPE_WIRE_TIMED),
@@ -301,6 +308,17 @@ void sp_shape_from_wire_stages(double out[8]);
 size_t sp_shape_wire_block(void);
 size_t sp_shape_wire_scan_tile(void);
 int sp_shape_wire_device_default(void);
+/* the full part of the calling thread's last SP_SHAPE_WIRE_FULL_DEVICE call, ms: filtered[], column counters and their read-back, the walk order (host),
+ * the sort, the column structure (device events; zero without SP_SHAPE_WIRE_TIMED - the walk order is host clock always), the whole full part (host clock),
+ * the digit passes of the sort, one spare slot. sp_shape_from_wire_stages keeps its eight fields: its decode and total include this part. */
+void sp_shape_from_wire_full_stages(double out[8]);
+/* compile-time constants of the sort kernels: elements a tile, bits a digit */
+size_t sp_shape_wire_sort_tile(void);
+size_t sp_shape_wire_sort_digit_bits(void);
+/* A checking tool, not a hot path: copies every device array of both shapes back and compares them on the host. SP_OK with `where_out` empty when all are equal;
+ * otherwise SP_OK with the first difference named in `where_out` by structure, matrix, array and index ("col[1].sidx[37]: 5 != 6", "row_only: 1 != 0"). A
+ * row-only shape compares its row[] alone. < 0: null argument or a failed copy. */
+int sp_shape_compare(sp_ctx* ctx, const sp_shape* a, const sp_shape* b, char* where_out, size_t cap);
 /* SplitR1CSShape::multiply_vec (:1075-1107). z has num_vars + 1 + num_public + num_challenges elements. */
 int sp_multiply_vec(sp_ctx* ctx, const sp_shape* s, const sp_table* z, sp_table* az, sp_table* bz, sp_table* cz);
 /* SplitR1CSShape::multiply_vec_batched (:1130-1166 -> PrecomputedSparseMatrix::multiply_vec_batched, sparse.rs:237-302): the three products for

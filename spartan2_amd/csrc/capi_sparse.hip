@@ -9,6 +9,8 @@
 //   k_nifs_layers      cached_step_matvec (src/neutronnova_zk.rs:1520-1600): (A, B, C) [W | 1 | X] of every instance of every state into its NIFS
 //                      layers in one launch, z never assembled (kernels_nifs_layers.hpp; the entry is sp_nifs_layers_batch, capi_nifs.hip)
 //   k_pab_*            evals_rx + poly_ABC (src/polys/eq.rs:59-117, src/r1cs/mod.rs:1235-1321) for a chunk of proofs in one walk over interleaved eq tables (kernels_polyabc_batch.hpp)
+//   k_full_*           sp_shape_from_wire's full device decode: filtered[] and the column-major col[] of sp_shape_from_csr from the uploaded bytes - column counters, a stable
+//                      radix sort of the entry numbers by walk position, one lane a sorted entry (kernels_wire_full.hpp)
 //   k_r1cs_residual    R1CSShape::is_sat / is_sat_relaxed (src/r1cs/mod.rs:358-394, :430-471): the row check behind multiply_vec (kernels_sat.hpp)
 // Entries keep the reference's classes: +-1 and |k| in 2..7 as an int8 code (add / sub / double-add chains, sparse.rs:137-155),
 // everything else as a full field coefficient.
@@ -252,6 +254,7 @@ __global__ void __launch_bounds__(256) k_polyabc_short_and_long(PolyAbcArgs a, c
 #include "kernels_spmv_multi.hpp"
 #include "kernels_nifs_layers.hpp"
 #include "kernels_wire_decode.hpp"
+#include "kernels_wire_full.hpp"
 
 // ---- host side: classification and upload ---------------------------------------------------------------------------
 namespace {
@@ -374,6 +377,27 @@ static int refuse_row_only(const sp_shape* s, const char* who) {
   return SP_OK;
 }
 
+// The three settings of poly_ABC's column structure, read once (the window with every shape that takes it). sp_shape_from_csr and the full device decode
+// of sp_shape_from_wire build under the same three.
+static int polyabc_order_mode() {
+  static const int order_mode = [] {
+    const char* e = getenv("SPARTAN_POLYABC_ORDER");  // "natural": column order as it is; "window": sorted inside windows of 4096 neighbouring columns (A/B runs)
+    return !e ? 0 : (e[0] == 'n' ? 1 : (e[0] == 'w' ? 2 : 0));
+  }();
+  return order_mode;
+}
+static size_t polyabc_window() {
+  const char* w = getenv("SPARTAN_POLYABC_WINDOW");
+  return w && atol(w) > 0 ? (size_t)atol(w) : 4096;
+}
+static bool polyabc_permuted() {
+  static const bool permuted = [] {
+    const char* e = getenv("SPARTAN_POLYABC_LAYOUT");
+    return !(e && e[0] == 'n');
+  }();
+  return permuted;
+}
+
 extern "C" {
 
 int sp_shape_from_csr(sp_ctx* c, const sp_csr* A, const sp_csr* Bm, const sp_csr* C, const sp_dims* dims, sp_shape** out) {
@@ -464,15 +488,11 @@ int sp_shape_from_csr(sp_ctx* c, const sp_csr* A, const sp_csr* Bm, const sp_csr
         if (a[k] != b[k]) return a[k] > b[k];
       return false;
     };
-    static const int order_mode = [] {
-      const char* e = getenv("SPARTAN_POLYABC_ORDER");  // "natural": column order as it is; "window": sorted inside windows of 4096 neighbouring columns (A/B runs)
-      return !e ? 0 : (e[0] == 'n' ? 1 : (e[0] == 'w' ? 2 : 0));
-    }();
+    const int order_mode = polyabc_order_mode();
     if (order_mode == 0) std::stable_sort(order.begin(), order.end(), by_len);
     else if (order_mode == 2)
     {
-      const char* w = getenv("SPARTAN_POLYABC_WINDOW");
-      const size_t win = w && atol(w) > 0 ? (size_t)atol(w) : 4096;
+      const size_t win = polyabc_window();
       for (size_t lo = 0; lo < order.size(); lo += win) std::stable_sort(order.begin() + lo, order.begin() + std::min(order.size(), lo + win), by_len);
     }
     s->n_short = order.size();
@@ -485,10 +505,7 @@ int sp_shape_from_csr(sp_ctx* c, const sp_csr* A, const sp_csr* Bm, const sp_csr
     // column through the permutation. (Config 4's synthetic instance - 3.8 M columns of 1-3 entries - walked in natural order took 1.02 ms of inner
     // sum-check against 1.45 sorted, and the SHA-256 instances the other way round, 120 against 76 us: with the storage permuted the sorted walk has both.)
     // SPARTAN_POLYABC_LAYOUT=natural keeps the columns where their numbers put them (A/B runs).
-    static const bool permuted = [] {
-      const char* e = getenv("SPARTAN_POLYABC_LAYOUT");
-      return !(e && e[0] == 'n');
-    }();
+    const bool permuted = polyabc_permuted();
     s->col_permuted = permuted;
     std::vector<unsigned> seq;
     if (permuted) {
@@ -560,7 +577,9 @@ int sp_shape_info(const sp_shape* s, uint64_t out[8]) {
 // indptr (u64 length, 8 bytes an element) and cols. wire_parse_shape takes the arrays as slices of the input and checks everything a later stage
 // dereferences through - that is O(rows) host work and ends a refused call before the first launch. The row-major structure is then built either on the
 // device from the raw bytes (wire_decode_device, kernels_wire_decode.hpp: the host touches no per-entry array) or on the host with the code behind
-// sp_shape_from_csr (wire_decode_host: sp_unwire_scalars, index narrowing, Classifier, build_split), which is also the way to a full shape.
+// sp_shape_from_csr (wire_decode_host: sp_unwire_scalars, index narrowing, Classifier, build_split), which is also a way to a full shape (SP_SHAPE_WIRE_FULL). The other
+// way (SP_SHAPE_WIRE_FULL_DEVICE) continues the device decode: wire_full_device builds filtered[], col[] and the walk order from what the row decode left on the device
+// (kernels_wire_full.hpp); the host reads six counters a column back and orders the columns, and touches no per-entry array.
 namespace {
 
 struct WireSlices {  // one matrix of the stream
@@ -645,7 +664,239 @@ int wire_parse_shape(sp_unwire* r, sp_dims* d, uint64_t* cols_out, WireSlices W[
   return SP_OK;
 }
 
-int wire_decode_device(sp_ctx* c, const sp_dims& d, uint64_t cols, const WireSlices W[3], bool timed, sp_shape* s) {
+// what the full part of the last SP_SHAPE_WIRE_FULL_DEVICE call on this thread spent where (ms): filtered[] (counts, scan, scatter), the column counters and
+// their read-back, the walk order on the host, the sort, the column structure (pointer scan and scatter) - device events, zero without SP_SHAPE_WIRE_TIMED -,
+// the whole full part (host clock), the digit passes of the sort, one spare slot
+thread_local double g_wire_full_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+
+// `cols` short columns by decreasing packed key, ties in the order they stand in (ascending column number): what std::stable_sort with sp_shape_from_csr's
+// six-count comparator gives, as a stable least-significant-digit radix sort of the 54-bit keys (a pass whose digit is the same for all is skipped)
+void sort_columns_by_key(unsigned* first, size_t n, const std::vector<uint64_t>& key) {
+  if (n < 2) return;
+  if (n < 2048) {
+    std::stable_sort(first, first + n, [&](unsigned x, unsigned y) { return key[x] > key[y]; });
+    return;
+  }
+  constexpr unsigned BITS = 11, BINS = 1u << BITS;
+  std::vector<unsigned> other(n), count(BINS);
+  unsigned *src = first, *dst = other.data();
+  for (unsigned shift = 0; shift < 54; shift += BITS) {
+    std::fill(count.begin(), count.end(), 0u);
+    for (size_t i = 0; i < n; ++i) count[(~key[src[i]] >> shift) & (BINS - 1)]++;
+    if (count[(~key[src[0]] >> shift) & (BINS - 1)] == n) continue;
+    unsigned at = 0;
+    for (unsigned b = 0; b < BINS; ++b) {
+      const unsigned t = count[b];
+      count[b] = at;
+      at += t;
+    }
+    for (size_t i = 0; i < n; ++i) dst[count[(~key[src[i]] >> shift) & (BINS - 1)]++] = src[i];
+    std::swap(src, dst);
+  }
+  if (src != first) memcpy(first, src, n * sizeof(unsigned));
+}
+
+// The full part of the device decode: filtered[], col[], the walk order. `a` holds what the row decode left on the device (codes, narrowed columns, raw
+// coefficients, row pointers; row[m]'s own arrays are not read). Every allocation goes through `own`: a refused call frees them all.
+int wire_full_device(sp_ctx* c, const sp_dims& d, uint64_t cols, const WireSlices W[3], const spk::WireArgs& a, DevOwner& own, bool timed, sp_shape* s) {
+  const double t_begin = wall_ms();
+  const size_t rows = d.num_cons, nblk_rows = a.nblk, nblk_cols = (cols + spk::WIRE_SCAN_TILE - 1) / spk::WIRE_SCAN_TILE;
+  const size_t nr_used = d.num_cons_unpadded, col_min = d.num_shared + d.num_precommitted;
+  int rc;
+  spk::FullArgs x;
+  spk::WireArgs f = a, cp = a;  // the scan kernels' view of the filtered row pointers and of the column pointers
+  uint64_t max_used = 0, all_used = 0, all_nnz = 0;
+  for (int m = 0; m < 3; ++m) {
+    x.n_used[m] = (unsigned)le64(W[m].indptr + 8 * nr_used);  // (row-major stream: the entries of the rows below nr_used are its first indptr[nr_used])
+    max_used = std::max<uint64_t>(max_used, x.n_used[m]);
+    all_used += x.n_used[m];
+    all_nnz += W[m].nnz;
+    if ((rc = own.alloc(&x.row32[m], W[m].nnz)) || (rc = own.alloc(&f.m[m].sptr, rows + 1)) || (rc = own.alloc(&f.m[m].gptr, rows + 1)) ||
+        (rc = own.alloc(&cp.m[m].sptr, cols + 1)) || (rc = own.alloc(&cp.m[m].gptr, cols + 1)))
+      return rc;
+  }
+  unsigned *d_fwords, *d_cwords, *d_pos;  // totals [6] | max_len [3] | block_sums [6 nblk]
+  if ((rc = own.alloc(&x.col_cnt, 6 * cols)) || (rc = own.alloc(&d_fwords, 9 + 6 * nblk_rows)) || (rc = own.alloc(&d_cwords, 9 + 6 * nblk_cols)) || (rc = own.alloc(&d_pos, cols)))
+    return rc;
+  x.pos = d_pos;
+  x.row_limit = nr_used, x.col_min = col_min, x.cols = cols;
+  f.totals = d_fwords, f.max_len = d_fwords + 6, f.block_sums = d_fwords + 9, f.nblk = (unsigned)nblk_rows;
+  cp.totals = d_cwords, cp.max_len = d_cwords + 6, cp.block_sums = d_cwords + 9, cp.nblk = (unsigned)nblk_cols;
+  hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  struct EvGuard {
+    hipEvent_t* e;
+    ~EvGuard() {
+      for (int i = 0; i < 6; ++i)
+        if (e[i]) hipEventDestroy(e[i]);
+    }
+  } ev_guard{ev};
+  auto mark = [&](int i) -> hipError_t { return timed ? hipEventRecord(ev[i], c->stream) : hipSuccess; };
+  if (timed)
+    for (int i = 0; i < 6; ++i) SP_HIP(hipEventCreate(&ev[i]));
+  const dim3 block(spk::WIRE_BLOCK);
+  auto capped = [](uint64_t n) { return (unsigned)std::min<uint64_t>(std::max<uint64_t>((n + spk::WIRE_BLOCK - 1) / spk::WIRE_BLOCK, 1), 4096); };
+  const unsigned row_blocks = capped(rows), col_blocks = capped(cols), used_blocks = capped(max_used);
+  auto scan = [&](const spk::WireArgs& w, size_t n) {  // exclusive scan of w.m[].sptr / gptr over n elements, in place (kernels_wire_decode.hpp)
+    c->timed_kernel("wire_scan", 3 * 8ull * n, spk::k_wire_scan_reduce, dim3(w.nblk, 3), block, w, n);
+    c->timed_kernel("wire_scan", 3 * 16ull * w.nblk, spk::k_wire_scan_blocks, dim3(1, 3), block, w);
+    c->timed_kernel("wire_scan", 3 * 16ull * n, spk::k_wire_scan_add, dim3(w.nblk, 3), block, w, n);
+  };
+  // ---- filtered[]: count, scan, scatter with the predicate
+  SP_HIP(mark(0));
+  SP_HIP(hipMemsetAsync(d_fwords, 0, 9 * sizeof(unsigned), c->stream));
+  SP_HIP(hipMemsetAsync(x.col_cnt, 0, 6 * cols * sizeof(unsigned), c->stream));
+  c->timed_kernel("wire_full_filtered", 9ull * all_nnz + 3 * 24ull * rows, spk::k_full_filt_counts, dim3(row_blocks, 3), block, a, f, x, rows);
+  scan(f, rows);
+  unsigned fwords[9];
+  SP_HIP(hipMemcpyAsync(fwords, d_fwords, sizeof fwords, hipMemcpyDeviceToHost, c->stream));
+  SP_HIP(sp::stream_sync(c->stream));
+  SP_HIP(hipGetLastError());
+  spk::WireOutArgs fo;
+  for (int m = 0; m < 3; ++m) {
+    if ((uint64_t)fwords[2 * m] + fwords[2 * m + 1] > x.n_used[m]) return fail(SP_ERR_INTERNAL, "sp_shape_from_wire: more filtered entries than entries");
+    if ((rc = own.alloc(&fo.o[m].sidx, fwords[2 * m])) || (rc = own.alloc(&fo.o[m].scode, fwords[2 * m])) || (rc = own.alloc(&fo.o[m].gidx, fwords[2 * m + 1])) ||
+        (rc = own.alloc(&fo.o[m].gval, fwords[2 * m + 1])))
+      return rc;
+  }
+  c->timed_kernel("wire_full_filtered", 46ull * all_used + 3 * 24ull * rows, spk::k_full_filt_scatter, dim3(row_blocks, 3), block, a, f, fo, x, rows);
+  SP_HIP(mark(1));
+  // ---- the six counters of every column, back to the host
+  if (max_used) c->timed_kernel("wire_full_col_counts", 9ull * all_used, spk::k_full_col_counts, dim3(used_blocks, 3), block, a, x);
+  std::vector<unsigned> cnt(6 * cols);
+  SP_HIP(hipMemcpyAsync(cnt.data(), x.col_cnt, cnt.size() * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+  SP_HIP(mark(2));
+  SP_HIP(sp::stream_sync(c->stream));
+  SP_HIP(hipGetLastError());
+  // ---- the walk order (O(columns) on the host): the rules of sp_shape_from_csr under the same three settings
+  const double t_order = wall_ms();
+  const int order_mode = polyabc_order_mode();
+  const bool permuted = polyabc_permuted();
+  std::vector<unsigned> order, long_cols, pos(cols);
+  std::vector<uint64_t> key(cols);
+  unsigned n_small[3] = {0, 0, 0}, col_max_len[3] = {0, 0, 0};
+  uint64_t sums[6] = {0, 0, 0, 0, 0, 0};
+  order.reserve(cols);
+  for (size_t i = 0; i < cols; ++i) {
+    uint64_t total = 0, k = 0;
+    for (int j = 0; j < 6; ++j) {
+      const unsigned v = cnt[(size_t)j * cols + i];
+      total += v;
+      sums[j] += v;
+      if (j < 5) k = (k << 9) | (v & 511u);  // (a short column's counts are below LONG_COLUMN = 512 each: nine bits)
+    }
+    for (int m = 0; m < 3; ++m) col_max_len[m] = std::max(col_max_len[m], cnt[(size_t)(2 * m) * cols + i] + cnt[(size_t)(2 * m + 1) * cols + i]);
+    if (total >= spk::LONG_COLUMN) long_cols.push_back((unsigned)i);
+    else {
+      key[i] = (total << 45) | k;
+      order.push_back((unsigned)i);
+    }
+  }
+  for (int m = 0; m < 3; ++m) {
+    if (sums[2 * m] + sums[2 * m + 1] != x.n_used[m]) return fail(SP_ERR_INTERNAL, "sp_shape_from_wire: the column counts do not add up to the entry count");
+    n_small[m] = (unsigned)sums[2 * m];
+  }
+  if (order_mode == 0) sort_columns_by_key(order.data(), order.size(), key);
+  else if (order_mode == 2) {
+    const size_t win = polyabc_window();
+    for (size_t lo = 0; lo < order.size(); lo += win) sort_columns_by_key(order.data() + lo, std::min(order.size(), lo + win) - lo, key);
+  }
+  if (permuted) {  // the column-major structure is stored in walk order: the short columns in `order`, then the long ones
+    for (size_t i = 0; i < order.size(); ++i) pos[order[i]] = (unsigned)i;
+    for (size_t i = 0; i < long_cols.size(); ++i) pos[long_cols[i]] = (unsigned)(order.size() + i);
+  } else {
+    for (size_t i = 0; i < cols; ++i) pos[i] = (unsigned)i;
+  }
+  const double order_ms = wall_ms() - t_order;
+  unsigned *d_order, *d_long;
+  if ((rc = own.alloc(&d_order, order.size())) || (rc = own.alloc(&d_long, long_cols.size()))) return rc;
+  SP_HIP(mark(3));
+  if (!order.empty()) SP_HIP(hipMemcpyAsync(d_order, order.data(), order.size() * sizeof(unsigned), hipMemcpyHostToDevice, c->stream));
+  if (!long_cols.empty()) SP_HIP(hipMemcpyAsync(d_long, long_cols.data(), long_cols.size() * sizeof(unsigned), hipMemcpyHostToDevice, c->stream));
+  SP_HIP(hipMemcpyAsync(d_pos, pos.data(), cols * sizeof(unsigned), hipMemcpyHostToDevice, c->stream));
+  // ---- the stable sort of the entry numbers by walk position, one digit a pass
+  unsigned passes = 1;
+  while (passes < 4 && ((cols - 1) >> (spk::FULL_SORT_BITS * passes)) != 0) ++passes;
+  spk::SortArgs sa;
+  sa.ntiles = (unsigned)std::max<uint64_t>((max_used + spk::FULL_SORT_TILE - 1) / spk::FULL_SORT_TILE, 1);
+  const size_t hist_n = (size_t)spk::FULL_SORT_BINS * sa.ntiles, nblk_hist = (hist_n + spk::WIRE_SCAN_TILE - 1) / spk::WIRE_SCAN_TILE;
+  spk::WireArgs hs = a;  // the scan kernels' view of the histograms
+  unsigned *d_hwords, *buf_k[3][2], *buf_v[3][2];
+  if ((rc = own.alloc(&d_hwords, 9 + 6 * nblk_hist))) return rc;
+  hs.totals = d_hwords, hs.max_len = d_hwords + 6, hs.block_sums = d_hwords + 9, hs.nblk = (unsigned)nblk_hist;
+  for (int m = 0; m < 3; ++m) {
+    spk::SortMat& sm = sa.m[m];
+    if ((rc = own.alloc(&sm.hist_s, hist_n + 1)) || (rc = own.alloc(&sm.hist_g, hist_n + 1))) return rc;
+    for (int b = 0; b < 2; ++b)
+      if ((rc = own.alloc(&buf_k[m][b], x.n_used[m])) || (rc = own.alloc(&buf_v[m][b], x.n_used[m]))) return rc;
+    hs.m[m].sptr = sm.hist_s, hs.m[m].gptr = sm.hist_g;
+    sm.n = x.n_used[m], sm.n_small = n_small[m];
+  }
+  for (unsigned p = 0; p < passes; ++p) {
+    for (int m = 0; m < 3; ++m) {
+      sa.m[m].keys_in = buf_k[m][(p + 1) & 1], sa.m[m].vals_in = buf_v[m][(p + 1) & 1];  // (not read by the first pass: it takes the stream itself)
+      sa.m[m].keys_out = buf_k[m][p & 1], sa.m[m].vals_out = buf_v[m][p & 1];
+    }
+    const unsigned shift = spk::FULL_SORT_BITS * p;
+    const dim3 grid(sa.ntiles, 3);
+    if (p == 0) c->timed_kernel("wire_full_sort", 9ull * all_used, spk::k_full_sort_hist<true>, grid, block, a, x, sa, shift);
+    else c->timed_kernel("wire_full_sort", 8ull * all_used, spk::k_full_sort_hist<false>, grid, block, a, x, sa, shift);
+    scan(hs, hist_n);
+    if (p == 0) c->timed_kernel("wire_full_sort", 17ull * all_used, spk::k_full_sort_scatter<true>, grid, block, a, x, sa, shift);
+    else c->timed_kernel("wire_full_sort", 16ull * all_used, spk::k_full_sort_scatter<false>, grid, block, a, x, sa, shift);
+  }
+  SP_HIP(mark(4));
+  // ---- col[]: the column pointers from the counts at their walk positions, then one lane a sorted entry
+  c->timed_kernel("wire_full_columns", 3 * 20ull * cols, spk::k_full_col_place, dim3(col_blocks, 3), block, x, cp);
+  scan(cp, cols);
+  spk::ColOutArgs co;
+  for (int m = 0; m < 3; ++m) {
+    const unsigned ng = x.n_used[m] - n_small[m];
+    if ((rc = own.alloc(&co.o[m].sidx, n_small[m])) || (rc = own.alloc(&co.o[m].scode, n_small[m])) || (rc = own.alloc(&co.o[m].gidx, ng)) || (rc = own.alloc(&co.o[m].gval, ng)))
+      return rc;
+    co.sorted[m] = buf_v[m][(passes - 1) & 1];
+    co.n_small[m] = n_small[m];
+  }
+  if (max_used) c->timed_kernel("wire_full_columns", 45ull * all_used, spk::k_full_col_scatter, dim3(used_blocks, 3), block, a, x, co);
+  SP_HIP(mark(5));
+  unsigned cwords[6];
+  SP_HIP(hipMemcpyAsync(cwords, d_cwords, sizeof cwords, hipMemcpyDeviceToHost, c->stream));
+  SP_HIP(sp::stream_sync(c->stream));
+  SP_HIP(hipGetLastError());
+  for (int m = 0; m < 3; ++m)
+    if (cwords[2 * m] != n_small[m] || cwords[2 * m] + cwords[2 * m + 1] != x.n_used[m]) return fail(SP_ERR_INTERNAL, "sp_shape_from_wire: the column pointers do not end at the entry count");
+  if (timed) {
+    float ms[5] = {0, 0, 0, 0, 0};
+    for (int i = 0; i < 5; ++i) SP_HIP(hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]));
+    g_wire_full_ms[0] = ms[0], g_wire_full_ms[1] = ms[1], g_wire_full_ms[3] = ms[3], g_wire_full_ms[4] = ms[4];
+  }
+  g_wire_full_ms[2] = order_ms;
+  g_wire_full_ms[6] = passes;
+  // ---- everything succeeded: the shape takes its structures
+  for (int m = 0; m < 3; ++m) {
+    SplitOnDevice& fm = s->filtered[m];
+    fm.sptr = f.m[m].sptr, fm.gptr = f.m[m].gptr;
+    fm.sidx = fo.o[m].sidx, fm.scode = fo.o[m].scode, fm.gidx = fo.o[m].gidx, fm.gval = fo.o[m].gval;
+    fm.max_len = fwords[6 + m];
+    SplitOnDevice& cm = s->col[m];
+    cm.sptr = cp.m[m].sptr, cm.gptr = cp.m[m].gptr;
+    cm.sidx = co.o[m].sidx, cm.scode = co.o[m].scode, cm.gidx = co.o[m].gidx, cm.gval = co.o[m].gval;
+    cm.max_len = col_max_len[m];
+    for (void* q : {(void*)fm.sptr, (void*)fm.gptr, (void*)fm.sidx, (void*)fm.scode, (void*)fm.gidx, (void*)fm.gval, (void*)cm.sptr, (void*)cm.gptr, (void*)cm.sidx,
+                    (void*)cm.scode, (void*)cm.gidx, (void*)cm.gval})
+      own.release(q);
+    s->nnz_filtered[m] = (uint64_t)fwords[2 * m] + fwords[2 * m + 1];
+  }
+  s->d_short_order = d_order, s->d_long_cols = d_long;
+  own.release(d_order);
+  own.release(d_long);
+  s->n_short = order.size();
+  s->n_long_cols = long_cols.size();
+  s->col_permuted = permuted;
+  g_wire_full_ms[5] = wall_ms() - t_begin;
+  return SP_OK;
+}
+
+int wire_decode_device(sp_ctx* c, const sp_dims& d, uint64_t cols, const WireSlices W[3], bool timed, bool full, sp_shape* s) {
   static const char* const names[3] = {"A", "B", "C"};
   const size_t rows = d.num_cons, nblk = (rows + spk::WIRE_SCAN_TILE - 1) / spk::WIRE_SCAN_TILE;
   DevOwner own;
@@ -735,6 +986,7 @@ int wire_decode_device(sp_ctx* c, const sp_dims& d, uint64_t cols, const WireSli
       SP_HIP(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
       g_wire_ms[i] = ms;
     }
+  if (full && (rc = wire_full_device(c, d, cols, W, a, own, timed, s))) return rc;  // (it hands its structures over last: a refusal leaves `s` owning nothing)
   for (int m = 0; m < 3; ++m) {
     SplitOnDevice& r = s->row[m];
     r.sptr = a.m[m].sptr, r.gptr = a.m[m].gptr;
@@ -813,13 +1065,96 @@ int sp_shape_wire_device_default(void) { return WIRE_DEVICE_DEFAULT ? 1 : 0; }
 void sp_shape_from_wire_stages(double out[8]) {
   if (out) memcpy(out, g_wire_ms, sizeof g_wire_ms);
 }
+size_t sp_shape_wire_sort_tile(void) { return (size_t)spk::FULL_SORT_TILE; }
+size_t sp_shape_wire_sort_digit_bits(void) { return (size_t)spk::FULL_SORT_BITS; }
+void sp_shape_from_wire_full_stages(double out[8]) {
+  if (out) memcpy(out, g_wire_full_ms, sizeof g_wire_full_ms);
+}
+
+// A checking tool: every device array of both shapes copied back and compared on the host. `where` names the first difference by structure, matrix, array
+// and index ("col[1].sidx[37]: 5 != 6"); it is empty when there is none.
+int sp_shape_compare(sp_ctx* c, const sp_shape* a, const sp_shape* b, char* where, size_t cap) {
+  if (!c || !a || !b || !where || !cap) return fail(SP_ERR_INVALID_INPUT_LENGTH, "sp_shape_compare: null argument");
+  where[0] = 0;
+  std::string diff;
+  auto differ = [&](const std::string& what) {
+    diff = what;
+    snprintf(where, cap, "%s", diff.c_str());
+    return SP_OK;
+  };
+  auto scalar = [&](const char* name, uint64_t x, uint64_t y) {
+    if (diff.empty() && x != y) diff = std::string(name) + ": " + std::to_string(x) + " != " + std::to_string(y);
+  };
+  SP_HIP(sp::stream_sync(c->stream));
+  static const char* const dim_names[10] = {"num_cons", "num_cons_unpadded", "num_shared", "num_precommitted", "num_rest", "num_shared_unpadded", "num_precommitted_unpadded",
+                                            "num_rest_unpadded", "num_public", "num_challenges"};
+  const uint64_t *da = reinterpret_cast<const uint64_t*>(&a->dims), *db = reinterpret_cast<const uint64_t*>(&b->dims);
+  static_assert(sizeof(sp_dims) == 10 * sizeof(uint64_t), "sp_dims is ten words");
+  for (int i = 0; i < 10; ++i) scalar((std::string("dims.") + dim_names[i]).c_str(), da[i], db[i]);
+  scalar("num_cols", a->num_cols, b->num_cols);
+  scalar("row_only", a->row_only, b->row_only);
+  if (!diff.empty()) return differ(diff);
+  int rc = SP_OK;
+  auto arrays = [&](const std::string& name, const void* x, const void* y, size_t n, size_t elem) {  // elem: bytes an element
+    if (!diff.empty() || rc || !n) return;
+    std::vector<uint8_t> hx(n * elem), hy(n * elem);
+    if (hipMemcpy(hx.data(), x, n * elem, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(hy.data(), y, n * elem, hipMemcpyDeviceToHost) != hipSuccess) {
+      rc = fail(SP_ERR_NO_DEVICE, "sp_shape_compare: hipMemcpy of " + name);
+      return;
+    }
+    if (!memcmp(hx.data(), hy.data(), n * elem)) return;
+    size_t i = 0;
+    while (!memcmp(hx.data() + i * elem, hy.data() + i * elem, elem)) ++i;
+    diff = name + "[" + std::to_string(i) + "]";
+    if (elem <= 4) {
+      uint32_t vx = 0, vy = 0;
+      memcpy(&vx, hx.data() + i * elem, elem);
+      memcpy(&vy, hy.data() + i * elem, elem);
+      diff += ": " + std::to_string(vx) + " != " + std::to_string(vy);
+    }
+  };
+  auto split = [&](const char* structure, int m, const SplitOnDevice& x, const SplitOnDevice& y, size_t n_major) {
+    const std::string at = std::string(structure) + "[" + std::to_string(m) + "].";
+    scalar((at + "max_len").c_str(), x.max_len, y.max_len);
+    arrays(at + "sptr", x.sptr, y.sptr, n_major + 1, 4);
+    arrays(at + "gptr", x.gptr, y.gptr, n_major + 1, 4);
+    if (!diff.empty() || rc) return;
+    unsigned ns = 0, ng = 0;  // (equal in both by now)
+    if (hipMemcpy(&ns, x.sptr + n_major, 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(&ng, x.gptr + n_major, 4, hipMemcpyDeviceToHost) != hipSuccess) {
+      rc = fail(SP_ERR_NO_DEVICE, "sp_shape_compare: hipMemcpy of " + at + "sptr");
+      return;
+    }
+    arrays(at + "sidx", x.sidx, y.sidx, ns, 4);
+    arrays(at + "scode", x.scode, y.scode, ns, 1);
+    arrays(at + "gidx", x.gidx, y.gidx, ng, 4);
+    arrays(at + "gval", x.gval, y.gval, ng, sizeof(fe_t));
+  };
+  for (int m = 0; m < 3; ++m) scalar(("nnz[" + std::to_string(m) + "]").c_str(), a->nnz[m], b->nnz[m]);
+  for (int m = 0; m < 3; ++m) split("row", m, a->row[m], b->row[m], a->dims.num_cons);
+  if (!a->row_only) {
+    for (int m = 0; m < 3; ++m) scalar(("nnz_filtered[" + std::to_string(m) + "]").c_str(), a->nnz_filtered[m], b->nnz_filtered[m]);
+    scalar("n_short", a->n_short, b->n_short);
+    scalar("n_long_cols", a->n_long_cols, b->n_long_cols);
+    scalar("col_permuted", a->col_permuted, b->col_permuted);
+    for (int m = 0; m < 3; ++m) split("filtered", m, a->filtered[m], b->filtered[m], a->dims.num_cons);
+    arrays("short_order", a->d_short_order, b->d_short_order, a->n_short, 4);
+    arrays("long_cols", a->d_long_cols, b->d_long_cols, a->n_long_cols, 4);
+    for (int m = 0; m < 3; ++m) split("col", m, a->col[m], b->col[m], a->num_cols);
+  }
+  if (rc) return rc;
+  return diff.empty() ? SP_OK : differ(diff);
+}
 
 int sp_shape_from_wire(sp_ctx* c, sp_unwire* r, unsigned flags, sp_dims* dims_out, sp_shape** out) {
   if (!c || !r || !dims_out || !out) return fail(SP_ERR_INVALID_INPUT_LENGTH, "sp_shape_from_wire: null argument");
   const bool want_dev = flags & SP_SHAPE_WIRE_DEVICE, want_host = flags & SP_SHAPE_WIRE_HOST, full = flags & SP_SHAPE_WIRE_FULL;
-  if ((flags & ~(unsigned)(SP_SHAPE_WIRE_DEVICE | SP_SHAPE_WIRE_HOST | SP_SHAPE_WIRE_FULL | SP_SHAPE_WIRE_TIMED)) || (want_dev && (want_host || full)))
+  const bool full_dev = flags & SP_SHAPE_WIRE_FULL_DEVICE;
+  if ((flags & ~(unsigned)(SP_SHAPE_WIRE_DEVICE | SP_SHAPE_WIRE_HOST | SP_SHAPE_WIRE_FULL | SP_SHAPE_WIRE_TIMED | SP_SHAPE_WIRE_FULL_DEVICE)) || (want_dev && (want_host || full)))
     return fail(SP_ERR_INVALID_INPUT_LENGTH, "sp_shape_from_wire: flags that exclude each other (the device decode builds the row-only shape; the full shape takes the host decode)");
+  if (full_dev && (want_dev || want_host || full))
+    return fail(SP_ERR_INVALID_INPUT_LENGTH, "sp_shape_from_wire: flags that exclude each other (SP_SHAPE_WIRE_FULL_DEVICE builds the full shape on the device and takes no other form)");
   for (double& x : g_wire_ms) x = 0;
+  for (double& x : g_wire_full_ms) x = 0;
   const double t0 = wall_ms();
   sp_dims d;
   uint64_t cols = 0;
@@ -827,15 +1162,15 @@ int sp_shape_from_wire(sp_ctx* c, sp_unwire* r, unsigned flags, sp_dims* dims_ou
   int rc = wire_parse_shape(r, &d, &cols, W);
   if (rc) return rc;
   const double t1 = wall_ms();
-  const bool device = want_dev || (!want_host && !full && WIRE_DEVICE_DEFAULT);
+  const bool device = full_dev || want_dev || (!want_host && !full && WIRE_DEVICE_DEFAULT);
   sp_shape* s = nullptr;
   if (device) {
     s = new sp_shape();
     s->dims = d;
     s->num_vars = d.num_shared + d.num_precommitted + d.num_rest;
     s->num_cols = cols;
-    s->row_only = true;
-    if ((rc = wire_decode_device(c, d, cols, W, (flags & SP_SHAPE_WIRE_TIMED) != 0, s))) {
+    s->row_only = !full_dev;
+    if ((rc = wire_decode_device(c, d, cols, W, (flags & SP_SHAPE_WIRE_TIMED) != 0, full_dev, s))) {
       delete s;  // (it owns nothing yet: the structures are handed over at the very end of a decode that succeeded)
       return rc;
     }

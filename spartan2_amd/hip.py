@@ -913,7 +913,24 @@ class _Dims(ctypes.Structure):
 
 
 SHAPE_WIRE_DEVICE, SHAPE_WIRE_HOST, SHAPE_WIRE_FULL, SHAPE_WIRE_TIMED = 1, 2, 4, 8  # SP_SHAPE_WIRE_* (sp_shape_from_wire's flags)
+SHAPE_WIRE_FULL_DEVICE = 16  # ... the full shape built on the device
 WIRE_STAGES = ("upload", "entries", "counts_scan", "scatter", "parse", "decode", "total", "device")
+WIRE_FULL_STAGES = ("filtered", "column_counts", "order", "sort", "columns", "full_total", "sort_passes", "spare")
+
+
+def wire_full_stages() -> dict:
+    """sp_shape_from_wire_full_stages: ms of the full part of the calling thread's last SP_SHAPE_WIRE_FULL_DEVICE call by stage (device events, zero unless
+    timed; order and full_total are host clock) and the sort's digit passes"""
+    out = (ctypes.c_double * 8)()
+    lib().sp_shape_from_wire_full_stages(out)
+    return {k: float(v) for k, v in zip(WIRE_FULL_STAGES, out)}
+
+
+def wire_full_constants() -> dict:
+    """compile-time constants of the full decode's sort kernels (kernels_wire_full.hpp), read from the library"""
+    L = lib()
+    L.sp_shape_wire_sort_tile.restype = L.sp_shape_wire_sort_digit_bits.restype = ctypes.c_size_t
+    return {"sort_tile": int(L.sp_shape_wire_sort_tile()), "digit_bits": int(L.sp_shape_wire_sort_digit_bits())}
 
 
 def wire_stages() -> dict:
@@ -1026,12 +1043,13 @@ class Shape:
                                       ctypes.c_size_t(out_len), arr))
 
     @classmethod
-    def from_wire(cls, ctx, data, device_decode=None, full=False, timed=False):
+    def from_wire(cls, ctx, data, device_decode=None, full=False, timed=False, full_device=False):
         """sp_shape_from_wire: the shape from the bincode bytes of SplitR1CSShape (what sp_wire_shape(.., 0) writes; trailing bytes are refused).
         device_decode: True / False forces the device / host decode, None takes the library's default; full=True asks for the full shape of Shape(...)
         through the host decode - without it the shape is row-only (multiply_vec*, matrix_evals_batched and is_sat work, poly_abc* and
-        multiply_vec_incremental* raise "row-only shape"). .dims is read from the bytes; .stages the call's times (wire_stages())."""
-        flags = SHAPE_WIRE_FULL if full else 0
+        multiply_vec_incremental* raise "row-only shape"). full_device=True asks for the same full shape built on the device (SP_SHAPE_WIRE_FULL_DEVICE; it
+        excludes the other three). .dims is read from the bytes; .stages the call's times (wire_stages()), .full_stages those of the full part."""
+        flags = (SHAPE_WIRE_FULL if full else 0) | (SHAPE_WIRE_FULL_DEVICE if full_device else 0)
         if device_decode is not None:
             flags |= SHAPE_WIRE_DEVICE if device_decode else SHAPE_WIRE_HOST
         if timed:
@@ -1054,7 +1072,14 @@ class Shape:
             lib().sp_unwire_free(r)
         self.dims = {n: int(getattr(dd, n)) for n, _ in _Dims._fields_}
         self.stages = wire_stages()
+        self.full_stages = wire_full_stages()
         return self
+
+    def compare(self, other) -> str:
+        """sp_shape_compare: "" when every device array of both shapes is equal, else the first difference by structure, matrix, array and index"""
+        where = ctypes.create_string_buffer(256)
+        check(lib().sp_shape_compare(self.ctx.h, self.h, other.h, where, ctypes.c_size_t(len(where))))
+        return where.value.decode()
 
     def info(self) -> dict:
         """sp_shape_info: entry counts of the structures the shape holds (zeros for those a row-only shape does not)"""

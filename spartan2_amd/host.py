@@ -440,6 +440,22 @@ class SpartanSNARK:
         assert got == n, (got, n)
         return out[:n].tobytes()
 
+    def pk_to_bytes(self) -> bytes:
+        """The key's SpartanProverKey { ck, ck_s, S, vk_digest } (src/spartan.rs:42-49) as bincode bytes (ss_pk_to_bytes): vk_to_bytes() followed by the 32
+        digest bytes - what SpartanProver.from_bytes loads."""
+        args, keep = _inst_args(self.inst)
+        fn = lib().ss_pk_to_bytes
+        fn.restype = ctypes.c_long
+        n = fn(self.pk, *args, None, ctypes.c_size_t(0))
+        if n < 0:
+            _check(n)
+        out = np.zeros(max(n, 1), dtype=np.uint8)
+        got = fn(self.pk, *args, hip.p8(out), ctypes.c_size_t(n))
+        if got < 0:
+            _check(got)
+        assert got == n, (got, n)
+        return out[:n].tobytes()
+
     def verify_bytes(self, data: bytes) -> int:
         """verify() on a serialised proof: 0 = accept, 1..6 = failed check (1 also for bytes that do not decode to a proof of this key's shape)."""
         arr = np.frombuffer(bytes(data), dtype=np.uint8).copy() if len(data) else np.zeros(1, dtype=np.uint8)
@@ -556,6 +572,98 @@ class SpartanVerifier:
             self.close()
         except Exception:
             pass
+
+
+SS_PK_TRUST_DIGEST = 1 << 16  # ss_prover_from_bytes flag: take the stored digest as it is (outside the SP_SHAPE_WIRE_* range)
+
+
+class _CallerInstance:
+    """what SpartanSNARK's prep methods read of an instance, for a key that has none: the caller's witness words and public values"""
+
+    def __init__(self, witness, publics):
+        self.witness = np.ascontiguousarray(witness, dtype=np.uint64).reshape(-1)
+        self.publics = np.ascontiguousarray(publics if publics is not None else [], dtype=np.uint64).reshape(-1)
+
+
+class SpartanProver:
+    """A prover's key loaded from the bincode bytes of SpartanProverKey (ss_prover_from_bytes): no circuit, no frontend instance, no setup. The key is
+    an ordinary prover key - the full shape, both commitment keys, the digest - and proves and verifies with the code SpartanSNARK's methods run."""
+
+    def __init__(self):
+        raise TypeError("use SpartanProver.from_bytes(ctx, data)")
+
+    @classmethod
+    def from_bytes(cls, ctx: hip.Context, data, trust_digest=False, full_device=None, timed=False):
+        """data: SpartanSNARK.pk_to_bytes(). By default the digest is hashed from the bytes and a key whose stored digest differs is refused;
+        trust_digest=True takes the stored one (SS_PK_TRUST_DIGEST). full_device: True / False forces the device / host build of the full shape
+        (SP_SHAPE_WIRE_FULL_DEVICE / SP_SHAPE_WIRE_FULL), None takes the measured default."""
+        flags = 0 if full_device is None else (hip.SHAPE_WIRE_FULL_DEVICE if full_device else hip.SHAPE_WIRE_FULL)
+        if trust_digest:
+            flags |= SS_PK_TRUST_DIGEST
+        if timed:
+            flags |= hip.SHAPE_WIRE_TIMED
+        buf = np.frombuffer(bytes(data), dtype=np.uint8) if data is not None else None
+        self = cls.__new__(cls)
+        self.ctx = ctx
+        self.inst = None
+        self.pk = ctypes.c_void_p()
+        self.ps = None
+        self.batch = []
+        self.publics = np.zeros(0, dtype=np.uint64)
+        self._sha_plan = None
+        _check(lib().ss_prover_from_bytes(ctx.h if ctx is not None else None, hip.p8(buf) if buf is not None and len(buf) else None,
+                                          ctypes.c_size_t(len(buf) if buf is not None else 0), ctypes.c_uint(flags), ctypes.byref(self.pk)))
+        self.stages = hip.wire_stages()  # of the shape's decode; .full_stages: of its full part; .load_stages: of the whole load
+        self.full_stages = hip.wire_full_stages()
+        st = (ctypes.c_double * 8)()
+        lib().ss_prover_stages(st)
+        self.load_stages = {k: float(v) for k, v in zip(("hyrax_keys", "shape", "ck_create", "digest", "digest_wait", "total", "full_device", "digest_hashed"), st)}
+        d = (ctypes.c_uint64 * 10)()
+        dig = np.zeros(32, dtype=np.uint8)
+        lib().ss_pk_info(self.pk, d, hip.p8(dig))
+        self.dims = {k: int(v) for k, v in zip(DIM_NAMES, d)}
+        self.vk_digest = dig
+        si = (ctypes.c_uint64 * 8)()
+        _check(lib().ss_pk_shape_info(self.pk, si))
+        self.shape_info = {"nnz": [int(si[i]) for i in range(3)], "nnz_filtered": [int(si[3 + i]) for i in range(3)], "long_columns": int(si[6]),
+                           "short_columns": int(si[7])}
+        return self
+
+    def prep_prove(self, tape: np.ndarray, witness, publics, is_small=True):
+        """SpartanSNARK.prep_prove on the caller's witness words; the prove() that follows states `publics`"""
+        self.inst = _CallerInstance(witness, publics)
+        return SpartanSNARK.prep_prove(self, tape, is_small)
+
+    def prep_prove_batch(self, tapes, witnesses=None, msgs=None, publics=None, is_small=True, **opts):
+        """SpartanSNARK.prep_prove_batch from `msgs`, or from `witnesses` (K arrays of witness words) with `publics` (K arrays of public values)"""
+        if witnesses is not None:
+            if publics is None or len(publics) != len(witnesses):
+                raise ValueError("prep_prove_batch: one array of public values for every witness")
+            witnesses = [_CallerInstance(w, p) for w, p in zip(witnesses, publics)]
+        elif msgs is None:
+            raise ValueError("prep_prove_batch: a key loaded from its bytes has no instance of its own (pass witnesses= and publics=, or msgs=)")
+        return SpartanSNARK.prep_prove_batch(self, tapes, witnesses=witnesses, msgs=msgs, is_small=is_small, **opts)
+
+    prep_prove_sha256 = SpartanSNARK.prep_prove_sha256
+    _prep_prove_loop = SpartanSNARK._prep_prove_loop
+    _free_ps = SpartanSNARK._free_ps
+    _free_batch = SpartanSNARK._free_batch
+    _rest_hook = SpartanSNARK._rest_hook
+    prep_phases = SpartanSNARK.prep_phases
+    set_flags = SpartanSNARK.set_flags
+    prep_export = SpartanSNARK.prep_export
+    prove = SpartanSNARK.prove
+    prove_batch = SpartanSNARK.prove_batch
+    is_sat = SpartanSNARK.is_sat
+    verify = SpartanSNARK.verify
+    verify_bytes = SpartanSNARK.verify_bytes
+    _verify_batch = SpartanSNARK._verify_batch
+    verify_batch = SpartanSNARK.verify_batch
+    verify_bytes_batch = SpartanSNARK.verify_bytes_batch
+    proof_layout = SpartanSNARK.proof_layout
+    proof_to_bytes = SpartanSNARK.proof_to_bytes
+    close = SpartanSNARK.close
+    __del__ = SpartanSNARK.__del__
 
 
 # ---- NeutronNovaNIFS::prove (spartan2_amd/host/neutronnova_nifs.cpp) ----------------------------------------------------------

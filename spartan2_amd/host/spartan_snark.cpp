@@ -32,6 +32,8 @@ struct SpartanProverKey {  // src/spartan.rs:30-58
   // a SpartanVerifierKey loaded from its bytes (verifier_from_bytes): S holds the row-major structures alone. verify, verify_batch and the byte forms
   // read nothing else of a key; the C surface refuses such a key at every prover entry point ("verifier-only key")
   bool verifier_only = false;
+  // a key loaded from its bytes, a verifier's or a prover's (prover_from_bytes): vk_to_bytes and pk_to_bytes refuse it - the caller holds the bytes
+  bool from_bytes = false;
   // verify()'s device workspaces (T_x, T_y, the three products M T_y): allocated by the first verify on this key and kept - five hipMalloc / hipFree
   // pairs of 32-64 MB were half of a 3.3 ms verify. One verify at a time per key (as for every handle of the ABI).
   mutable sp_table *v_Tx = nullptr, *v_Ty = nullptr, *v_mv[3] = {nullptr, nullptr, nullptr};
@@ -172,6 +174,7 @@ static double now_ms() { return std::chrono::duration<double, std::milli>(std::c
 // another circuit than the one the key was set up from is refused.
 std::vector<uint8_t> vk_to_bytes(const SpartanProverKey& pk, const R1CSIntView& R) {
   if (pk.verifier_only) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "vk_to_bytes: verifier-only key (it was loaded from its bytes: keep those)");
+  if (pk.from_bytes) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "vk_to_bytes: a key loaded from its bytes (keep those)");
   PaddedShape P = pad_shape(R);
   sp_csr cs[3];
   padded_csr(P, cs);
@@ -202,14 +205,41 @@ size_t vk_bytes_len(const SpartanProverKey& pk, const R1CSIntView& R) {
 // host wall-clock of the calling thread's last verifier_from_bytes, ms (ss_verifier_stages): the two Hyrax keys read, sp_shape_from_wire, the two
 // sp_ck_create, the digest on its helper thread, the wait for it behind everything else, the whole call
 static thread_local double g_vk_stage_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-SpartanProverKey* verifier_from_bytes(sp_ctx* ctx, const uint8_t* bytes, size_t n, unsigned flags) {
-  for (double& x : g_vk_stage_ms) x = 0;
+// ... and of its last prover_from_bytes (ss_prover_stages): the same six, then 1 / 0 = the shape was built on the device / the host, 1 / 0 = the digest was
+// hashed / trusted
+static thread_local double g_pk_stage_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+// which form of the full shape a prover load without a forcing flag takes: measured (profiles/prover_key.md), by the rule of profiles/verifier_key.md -
+// the device form only if its median lies below the host form's minimum
+static constexpr bool PK_FULL_DEVICE_DEFAULT = true;
+enum : unsigned { SS_PK_TRUST_DIGEST = 1u << 16 };  // (outside the SP_SHAPE_WIRE_* range)
+
+// One loader behind both keys. A verifier's (prover == false): the bytes are SpartanVerifierKey, the shape row-only, the digest hashed from them. A
+// prover's: SpartanProverKey { ck, ck_s, S, vk_digest } (src/spartan.rs:42-49) - for Hyrax ck serialises as vk_ee does, so the stream is the verifier's
+// bytes followed by the 32 raw digest bytes (bincode writes [u8; 32] without a length); the shape is the FULL shape, and the stored digest is compared with
+// the hash of the bytes before it unless SS_PK_TRUST_DIGEST takes it as the reference's Deserialize does.
+static SpartanProverKey* key_from_bytes(sp_ctx* ctx, const uint8_t* bytes, size_t n, unsigned flags, bool prover) {
+  const std::string who_s = prover ? "prover_from_bytes" : "verifier_from_bytes";
+  const char* const who = who_s.c_str();
+  double* const stage_ms = prover ? g_pk_stage_ms : g_vk_stage_ms;
+  for (int i = 0; i < 8; ++i) stage_ms[i] = 0;
   const double t_start = now_ms();
-  if (!ctx || !bytes || n == 0) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "verifier_from_bytes: null context, null bytes or no bytes");
-  if (flags & SP_SHAPE_WIRE_FULL) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "verifier_from_bytes: a verifier's key holds the row-only shape");
+  if (!ctx || !bytes || n == 0) throw Error(SP_ERR_INVALID_INPUT_LENGTH, who_s + ": null context, null bytes or no bytes");
+  bool trust_digest = false;
+  if (!prover) {
+    if (flags & SP_SHAPE_WIRE_FULL) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "verifier_from_bytes: a verifier's key holds the row-only shape");
+  } else {
+    trust_digest = flags & SS_PK_TRUST_DIGEST;
+    flags &= ~(unsigned)SS_PK_TRUST_DIGEST;
+    if (flags & (SP_SHAPE_WIRE_DEVICE | SP_SHAPE_WIRE_HOST)) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "prover_from_bytes: a prover's key holds the full shape (SP_SHAPE_WIRE_FULL_DEVICE or SP_SHAPE_WIRE_FULL)");
+    if (!(flags & (SP_SHAPE_WIRE_FULL_DEVICE | SP_SHAPE_WIRE_FULL))) flags |= PK_FULL_DEVICE_DEFAULT ? SP_SHAPE_WIRE_FULL_DEVICE : SP_SHAPE_WIRE_FULL;
+    if (n <= 32) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "prover_from_bytes: unexpected end of input (no room for the 32 digest bytes)");
+    n -= 32;  // the key's bytes; the stored digest lies behind them
+  }
+  const uint8_t* const stored_digest = bytes + n;
   auto pk = std::make_unique<SpartanProverKey>();
   pk->ctx = ctx;
-  pk->verifier_only = true;
+  pk->verifier_only = !prover;
+  pk->from_bytes = true;
   ck(sp_ctx_bind_thread(ctx), "device");
   sp_unwire* r = nullptr;
   ck(sp_unwire_new(bytes, n, &r), "unwire_new");
@@ -221,12 +251,16 @@ SpartanProverKey* verifier_from_bytes(sp_ctx* ctx, const uint8_t* bytes, size_t 
     gens.resize(nc + 1);
     ck(sp_unwire_hyrax_key(r, u64p(&gens[0].x), nc, &nc, u64p(&gens[nc].x)), what);
   };
-  read_key(pk->gens, DEFAULT_COMMITMENT_WIDTH, "verifier_from_bytes: vk_ee");
-  read_key(pk->gens_s, 1, "verifier_from_bytes: ck_s");
+  read_key(pk->gens, DEFAULT_COMMITMENT_WIDTH, prover ? "prover_from_bytes: ck" : "verifier_from_bytes: vk_ee");
+  read_key(pk->gens_s, 1, prover ? "prover_from_bytes: ck_s" : "verifier_from_bytes: ck_s");
   const double t_keys = now_ms();
   // the digest needs the bytes alone
   double digest_ms = 0;
-  std::future<int> digest = std::async(std::launch::async, [&] {
+  std::future<int> digest = std::async(trust_digest ? std::launch::deferred : std::launch::async, [&] {
+    if (trust_digest) {
+      memcpy(pk->vk_digest, stored_digest, 32);
+      return (int)SP_OK;
+    }
     const double t0 = now_ms();
     const int rc = sp_vk_digest_from_wire(bytes, n, pk->vk_digest);
     digest_ms = now_ms() - t0;
@@ -239,11 +273,11 @@ SpartanProverKey* verifier_from_bytes(sp_ctx* ctx, const uint8_t* bytes, size_t 
     }
   } join{digest};
   ck(sp_shape_from_wire(ctx, r, flags, &pk->dims, &pk->S), "shape_from_wire");
-  ck(sp_unwire_done(r), "verifier_from_bytes");
+  ck(sp_unwire_done(r), who);
   const double t_shape = now_ms();
   const sp_dims& d = pk->dims;
   const sp_dims want = padded_dims(d.num_cons_unpadded, d.num_shared_unpadded, d.num_precommitted_unpadded, d.num_rest_unpadded, d.num_public, d.num_challenges);
-  if (memcmp(&want, &d, sizeof d) != 0) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "verifier_from_bytes: the ten dimensions are not those SplitR1CSShape::new gives the unpadded sizes");
+  if (memcmp(&want, &d, sizeof d) != 0) throw Error(SP_ERR_INVALID_INPUT_LENGTH, who_s + ": the ten dimensions are not those SplitR1CSShape::new gives the unpadded sizes");
   pk->num_vars = d.num_shared + d.num_precommitted + d.num_rest;
   pk->layout = SpartanLayout(d, pk->num_vars);
   pk->num_extra = 1 + d.num_public + d.num_challenges;
@@ -252,11 +286,29 @@ SpartanProverKey* verifier_from_bytes(sp_ctx* ctx, const uint8_t* bytes, size_t 
   ck(sp_ck_create(ctx, u64p(&pk->gens_s[0].x), 1, u64p(&pk->gens_s[1].x), &pk->ck_s), "ck_s_create");
   const double t_ck = now_ms();
   const int drc = digest.get();
-  if (drc != SP_OK) throw Error(drc, "verifier_from_bytes: the digest pass could not walk the bytes");
+  if (drc != SP_OK) throw Error(drc, who_s + ": the digest pass could not walk the bytes");
+  if (prover && memcmp(pk->vk_digest, stored_digest, 32) != 0)
+    throw Error(SP_ERR_INVALID_INPUT_LENGTH, "prover_from_bytes: vk_digest: the stored digest is not the digest of the key's bytes (a prover under it makes proofs no verifier accepts)");
   const double t_end = now_ms();
   const double st[6] = {t_keys - t_start, t_shape - t_keys, t_ck - t_shape, digest_ms, t_end - t_ck, t_end - t_start};
-  std::copy(st, st + 6, g_vk_stage_ms);
+  std::copy(st, st + 6, stage_ms);
+  if (prover) stage_ms[6] = (flags & SP_SHAPE_WIRE_FULL_DEVICE) ? 1 : 0, stage_ms[7] = trust_digest ? 0 : 1;
   return pk.release();
+}
+SpartanProverKey* verifier_from_bytes(sp_ctx* ctx, const uint8_t* bytes, size_t n, unsigned flags) {
+  return key_from_bytes(ctx, bytes, n, flags, false);
+}
+// A prover's key from the bytes pk_to_bytes writes: flags = SP_SHAPE_WIRE_FULL_DEVICE / SP_SHAPE_WIRE_FULL to force the form of the shape's decode (neither:
+// PK_FULL_DEVICE_DEFAULT), SP_SHAPE_WIRE_TIMED, SS_PK_TRUST_DIGEST. The key is an ordinary SpartanProverKey (verifier_only == false).
+SpartanProverKey* prover_from_bytes(sp_ctx* ctx, const uint8_t* bytes, size_t n, unsigned flags) {
+  return key_from_bytes(ctx, bytes, n, flags, true);
+}
+// SpartanProverKey { ck, ck_s, S, vk_digest } as bincode: the verifier's bytes (vk_ee and ck serialise alike for Hyrax), then the digest
+std::vector<uint8_t> pk_to_bytes(const SpartanProverKey& pk, const R1CSIntView& R) {
+  if (pk.from_bytes) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "pk_to_bytes: a key loaded from its bytes (keep those)");
+  std::vector<uint8_t> out = vk_to_bytes(pk, R);
+  out.insert(out.end(), pk.vk_digest, pk.vk_digest + 32);
+  return out;
 }
 
 // ---- SpartanSNARK::prep_prove (src/spartan.rs:176-216) for `count` states of one key in one pass -------------------------------------------------------
@@ -2217,6 +2269,7 @@ long ss_vk_to_bytes(void* pk, size_t num_cons, size_t num_shared, size_t num_pre
     if (!pk) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "ss_vk_to_bytes: null key");
     const R1CSIntView R = make_view(num_cons, num_shared, num_precommitted, num_rest, num_public, num_challenges, Ad, Ai, Ap, Bd, Bi, Bp, Cd, Ci, Cp);
     const SpartanProverKey& key = prover_key(pk, "ss_vk_to_bytes");
+    if (key.from_bytes) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "ss_vk_to_bytes: a key loaded from its bytes (keep those)");
     if (!out) return (long)vk_bytes_len(key, R);
     const std::vector<uint8_t> b = vk_to_bytes(key, R);
     if (cap < b.size()) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "ss_vk_to_bytes: buffer too small");
@@ -2226,6 +2279,40 @@ long ss_vk_to_bytes(void* pk, size_t num_cons, size_t num_shared, size_t num_pre
     return catch_all();
   }
 }
+// The key's SpartanProverKey { ck, ck_s, S, vk_digest } as bincode bytes: ss_vk_to_bytes's protocol and bytes, followed by the 32 digest bytes.
+long ss_pk_to_bytes(void* pk, size_t num_cons, size_t num_shared, size_t num_precommitted, size_t num_rest, size_t num_public, size_t num_challenges, const int64_t* Ad,
+                    const uint32_t* Ai, const uint64_t* Ap, const int64_t* Bd, const uint32_t* Bi, const uint64_t* Bp, const int64_t* Cd, const uint32_t* Ci,
+                    const uint64_t* Cp, uint8_t* out, size_t cap) {
+  try {
+    if (!pk) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "ss_pk_to_bytes: null key");
+    const R1CSIntView R = make_view(num_cons, num_shared, num_precommitted, num_rest, num_public, num_challenges, Ad, Ai, Ap, Bd, Bi, Bp, Cd, Ci, Cp);
+    const SpartanProverKey& key = prover_key(pk, "ss_pk_to_bytes");
+    if (key.from_bytes) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "ss_pk_to_bytes: a key loaded from its bytes (keep those)");
+    if (!out) return (long)vk_bytes_len(key, R) + 32;
+    const std::vector<uint8_t> b = pk_to_bytes(key, R);
+    if (cap < b.size()) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "ss_pk_to_bytes: buffer too small");
+    memcpy(out, b.data(), b.size());
+    return (long)b.size();
+  } catch (...) {
+    return catch_all();
+  }
+}
+// A prover's key from those bytes (see key_from_bytes): no circuit, no setup. flags: SP_SHAPE_WIRE_FULL_DEVICE / SP_SHAPE_WIRE_FULL force the device / host
+// form of the full shape (neither: ss_prover_full_device_default), SP_SHAPE_WIRE_TIMED, SS_PK_TRUST_DIGEST (1 << 16) takes the stored digest unhashed. Every
+// prover and verifier entry point takes the key as it takes ss_setup's; ss_vk_to_bytes / ss_pk_to_bytes refuse it; ss_pk_free ends it.
+int ss_prover_from_bytes(sp_ctx* ctx, const uint8_t* bytes, size_t n, unsigned flags, void** out_pk) {
+  try {
+    if (!out_pk) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "ss_prover_from_bytes: null out");
+    *out_pk = nullptr;
+    *out_pk = prover_from_bytes(ctx, bytes, n, flags);
+    return 0;
+  } catch (...) {
+    return catch_all();
+  }
+}
+// ms of the calling thread's last ss_prover_from_bytes: ss_verifier_stages' six, then 1 / 0 = shape on the device / host, 1 / 0 = digest hashed / trusted
+void ss_prover_stages(double out[8]) { memcpy(out, g_pk_stage_ms, sizeof g_pk_stage_ms); }
+int ss_prover_full_device_default(void) { return PK_FULL_DEVICE_DEFAULT ? 1 : 0; }
 // A verifier's key from those bytes (see verifier_from_bytes). flags: 0, or SP_SHAPE_WIRE_DEVICE / SP_SHAPE_WIRE_HOST to force a decode form, and
 // SP_SHAPE_WIRE_TIMED. The key is taken by ss_verify, ss_verify_bytes, ss_verify_batch, ss_verify_bytes_batch, ss_pk_info, ss_pk_shape_info,
 // ss_proof_layout, ss_proof_words and ss_proof_to_bytes; every prover entry point refuses it ("verifier-only key"). ss_verifier_free (= ss_pk_free) ends it.

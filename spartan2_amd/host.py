@@ -1152,6 +1152,31 @@ class NeutronNovaZkSNARK:
         _check(lib().nnz_proof_to_bytes(self.pk, hip.p64(words), ctypes.c_size_t(len(words)), hip.p8(out), ctypes.c_size_t(n.value), ctypes.byref(n)))
         return out.tobytes()
 
+    def _key_to_bytes(self, fn) -> bytes:
+        a1, k1 = _inst_args(self.steps[0])
+        a2, k2 = _inst_args(self.core)
+        fn.restype = ctypes.c_long
+        n = fn(self.pk, *a1, *a2, None, ctypes.c_size_t(0))
+        if n < 0:
+            _check(n)
+        out = np.zeros(max(n, 1), dtype=np.uint8)
+        got = fn(self.pk, *a1, *a2, hip.p8(out), ctypes.c_size_t(n))
+        if got < 0:
+            _check(got)
+        assert got == n, (got, n)
+        return out[:n].tobytes()
+
+    def vk_to_bytes(self) -> bytes:
+        """The key's NeutronNovaVerifierKey { ck, vk_ee, S_step, S_core, vc_shape, vc_shape_regular, vc_ck, vc_vk } (src/neutronnova_zk.rs:1289-1303) as bincode
+        bytes (nnz_vk_to_bytes): what NeutronNovaVerifier.from_bytes loads. Both circuits are handed to the library again (setup keeps no copy of them) and
+        the bytes are returned only if they hash to this key's digest."""
+        return self._key_to_bytes(lib().nnz_vk_to_bytes)
+
+    def pk_to_bytes(self) -> bytes:
+        """The key's NeutronNovaProverKey { ck, S_step, S_core, vk_digest, vc_shape, vc_shape_regular, vc_ck } (src/neutronnova_zk.rs:1276-1287) as bincode
+        bytes (nnz_pk_to_bytes): what NeutronNovaProver.from_bytes loads."""
+        return self._key_to_bytes(lib().nnz_pk_to_bytes)
+
     def proof_from_bytes(self, data: bytes) -> np.ndarray:
         arr = np.frombuffer(bytes(data), dtype=np.uint8).copy() if len(data) else np.zeros(1, dtype=np.uint8)
         lib().nnz_proof_words.restype = ctypes.c_size_t
@@ -1217,3 +1242,172 @@ class NeutronNovaZkSNARK:
             self.close()
         except Exception:
             pass
+
+
+# ---- NeutronNova keys from their bytes (neutronnova_zk.cpp nn_key_from_bytes) --------------------------------------------------------------------------
+NN_KEY_STAGES = ("hyrax_key", "S_step", "S_core", "vc_shapes", "ck_create", "digest", "digest_wait", "total")
+
+
+class _KeyShape(hip.Shape):
+    """S_step / S_core of a NeutronNova key seen through hip.Shape (compare, info, dims): the key owns the handle"""
+
+    def __init__(self, ctx, h, dims):
+        self.ctx, self.h, self.dims, self._keep = ctx, h, dims, []
+
+    def __del__(self):
+        pass
+
+
+def nn_key_shapes(obj):
+    """(S_step, S_core) of a NeutronNovaZkSNARK, NeutronNovaVerifier or NeutronNovaProver as hip.Shape views; they live as long as the key does"""
+    L = lib()
+    L.nnz_pk_shape.restype = ctypes.c_void_p
+    d = (ctypes.c_uint64 * 23)()
+    L.nnz_pk_dims(obj.pk, d)
+    dims = [{k: int(v) for k, v in zip(DIM_NAMES, d[10 * i : 10 * i + 10])} for i in range(2)]
+    return tuple(_KeyShape(obj.ctx, ctypes.c_void_p(L.nnz_pk_shape(obj.pk, i)), dims[i]) for i in range(2))
+
+
+def nn_vk_digest_from_bytes(data, prover=False) -> bytes:
+    """nnz_vk_digest_from_bytes: DigestHelperTrait::digest of a NeutronNovaVerifierKey from its own bincode bytes, or (prover=True) from the bytes of the
+    NeutronNovaProverKey beside it (host code; no context)"""
+    buf = np.frombuffer(bytes(data), dtype=np.uint8)
+    out = np.zeros(32, dtype=np.uint8)
+    _check(lib().nnz_vk_digest_from_bytes(hip.p8(buf) if len(buf) else None, ctypes.c_size_t(len(buf)), int(bool(prover)), hip.p8(out)))
+    return out.tobytes()
+
+
+def _nn_key_load(self, fn, ctx, data, num_steps, flags):
+    """what both loaded keys are made of: the handle, info and digest as NeutronNovaZkSNARK has them, the shapes' dimensions, the load's stages"""
+    buf = np.frombuffer(bytes(data), dtype=np.uint8) if data is not None else None
+    self.ctx = ctx
+    self.num_steps = int(num_steps)
+    self.pk = ctypes.c_void_p()
+    self.ps = None
+    self.batch = []
+    self.batch_prep_phases = None
+    self.batch_prove_phases = None
+    self._sha_plan = None
+    _check(fn(ctx.h if ctx is not None else None, hip.p8(buf) if buf is not None and len(buf) else None, ctypes.c_size_t(len(buf) if buf is not None else 0),
+              ctypes.c_size_t(self.num_steps), ctypes.c_uint(flags), ctypes.byref(self.pk)))
+    st = (ctypes.c_double * 8)()
+    lib().nnz_key_stages(st)
+    self.load_stages = {k: float(v) for k, v in zip(NN_KEY_STAGES, st)}
+    self.wire_stages = hip.wire_stages()  # of S_core's decode, the later of the two
+    self.wire_full_stages = hip.wire_full_stages()
+    info = (ctypes.c_uint64 * 8)()
+    dig = np.zeros(32, dtype=np.uint8)
+    lib().nnz_pk_info(self.pk, info, hip.p8(dig))
+    self.info = dict(zip(("nb", "nx", "ny", "vc_rounds", "vc_vars", "vc_cons", "vc_cons_unpadded", "vc_public"), [int(x) for x in info]))
+    self.vk_digest = dig
+    d = (ctypes.c_uint64 * 23)()
+    lib().nnz_pk_dims(self.pk, d)
+    self.dims = {k: int(v) for k, v in zip(DIM_NAMES, d[:10])}
+    self.dims_core = {k: int(v) for k, v in zip(DIM_NAMES, d[10:20])}
+    lib().nnz_proof_words.restype = ctypes.c_size_t
+    return self
+
+
+class NeutronNovaVerifier:
+    """A verifier's key loaded from the bincode bytes of NeutronNovaVerifierKey (nnz_verifier_from_bytes): no circuits, no frontend, no setup. It holds
+    the two commitment keys, the row-major structures of S_step and S_core, the verifier circuit's shape and the digest - what verify reads - and verifies
+    with the code NeutronNovaZkSNARK's methods run."""
+
+    def __init__(self):
+        raise TypeError("use NeutronNovaVerifier.from_bytes(ctx, data, num_steps)")
+
+    @classmethod
+    def from_bytes(cls, ctx: hip.Context, data, num_steps, device_decode=None, timed=False):
+        """data: NeutronNovaZkSNARK.vk_to_bytes(). num_steps: the step count of the proofs to verify - the key fixes only ceil(log2) of it, so one key
+        serves e.g. 3 and 4 steps. device_decode: True / False forces the device / host decode of the matrices, None takes the measured default. Raises on
+        bytes that are not a key of that step count (short, trailing, inconsistent, not equalized, another verifier circuit ...)."""
+        flags = 0 if device_decode is None else (hip.SHAPE_WIRE_DEVICE if device_decode else hip.SHAPE_WIRE_HOST)
+        if timed:
+            flags |= hip.SHAPE_WIRE_TIMED
+        return _nn_key_load(cls.__new__(cls), lib().nnz_verifier_from_bytes, ctx, data, num_steps, flags)
+
+    def stages(self) -> dict:
+        """ms of the load by stage (NN_KEY_STAGES; host clock), and of S_core's sp_shape_from_wire under "wire" (device events when timed)"""
+        return dict(self.load_stages, wire=dict(self.wire_stages))
+
+    verify = NeutronNovaZkSNARK.verify
+    verify_bytes = NeutronNovaZkSNARK.verify_bytes
+    _verify_batch = NeutronNovaZkSNARK._verify_batch
+    verify_batch = NeutronNovaZkSNARK.verify_batch
+    verify_bytes_batch = NeutronNovaZkSNARK.verify_bytes_batch
+    proof_to_bytes = NeutronNovaZkSNARK.proof_to_bytes
+    proof_from_bytes = NeutronNovaZkSNARK.proof_from_bytes
+
+    def close(self):
+        if getattr(self, "pk", None):
+            lib().nnz_pk_free(self.pk)
+            self.pk = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class NeutronNovaProver:
+    """A prover's key loaded from the bincode bytes of NeutronNovaProverKey (nnz_prover_from_bytes): no circuits, no frontend instances, no setup. The key
+    is an ordinary prover key - both full shapes, both commitment keys, the verifier circuit's shape, the digest - and proves and verifies with the code
+    NeutronNovaZkSNARK's methods run."""
+
+    def __init__(self):
+        raise TypeError("use NeutronNovaProver.from_bytes(ctx, data, num_steps)")
+
+    @classmethod
+    def from_bytes(cls, ctx: hip.Context, data, num_steps, trust_digest=False, full_device=None, timed=False):
+        """data: NeutronNovaZkSNARK.pk_to_bytes(). num_steps: the step count to prove (see NeutronNovaVerifier.from_bytes). By default the digest is hashed
+        from the bytes and a key whose stored digest differs is refused; trust_digest=True takes the stored one (SS_PK_TRUST_DIGEST). full_device: True /
+        False forces the device / host build of the full shapes (SP_SHAPE_WIRE_FULL_DEVICE / SP_SHAPE_WIRE_FULL), None takes the measured default."""
+        flags = 0 if full_device is None else (hip.SHAPE_WIRE_FULL_DEVICE if full_device else hip.SHAPE_WIRE_FULL)
+        if trust_digest:
+            flags |= SS_PK_TRUST_DIGEST
+        if timed:
+            flags |= hip.SHAPE_WIRE_TIMED
+        self = _nn_key_load(cls.__new__(cls), lib().nnz_prover_from_bytes, ctx, data, num_steps, flags)
+        self.steps = [None] * self.num_steps  # (is_sat counts them; the key has no instances: every prep method takes the caller's words)
+        self.core = None
+        return self
+
+    stages = NeutronNovaVerifier.stages
+
+    @staticmethod
+    def _instances(step_witnesses, step_publics, core_witness, core_publics):
+        if len(step_witnesses) != len(step_publics):
+            raise ValueError("prep_prove: one array of public values for every step witness")
+        return [_CallerInstance(w, p) for w, p in zip(step_witnesses, step_publics)], _CallerInstance(core_witness, core_publics)
+
+    def prep_prove(self, tape: np.ndarray, step_witnesses, step_publics, core_witness, core_publics, is_small=True):
+        """NeutronNovaZkSNARK.prep_prove on the caller's witness words: one array of witness words and one of public values per step, and the core's"""
+        steps, core = self._instances(step_witnesses, step_publics, core_witness, core_publics)
+        return NeutronNovaZkSNARK.prep_prove(self, tape, is_small, _steps=steps, _core=core)
+
+    def prep_prove_batch(self, tapes, witnesses=None, blocks=None, is_small=True, **opts):
+        """NeutronNovaZkSNARK.prep_prove_batch from `blocks`, or from `witnesses`: witnesses[k] = (step_witnesses, step_publics, core_witness, core_publics)"""
+        if witnesses is not None:
+            witnesses = [self._instances(*w) for w in witnesses]
+        elif blocks is None:
+            raise ValueError("prep_prove_batch: a key loaded from its bytes has no instances of its own (pass witnesses= or blocks=)")
+        return NeutronNovaZkSNARK.prep_prove_batch(self, tapes, witnesses=witnesses, blocks=blocks, is_small=is_small, **opts)
+
+    _words = staticmethod(NeutronNovaZkSNARK._words)
+    _ensure_sha_plan = NeutronNovaZkSNARK._ensure_sha_plan
+    prep_prove_sha256 = NeutronNovaZkSNARK.prep_prove_sha256
+    _free_batch = NeutronNovaZkSNARK._free_batch
+    _state = NeutronNovaZkSNARK._state
+    prove = NeutronNovaZkSNARK.prove
+    prove_batch = NeutronNovaZkSNARK.prove_batch
+    is_sat = NeutronNovaZkSNARK.is_sat
+    verify = NeutronNovaZkSNARK.verify
+    verify_bytes = NeutronNovaZkSNARK.verify_bytes
+    _verify_batch = NeutronNovaZkSNARK._verify_batch
+    verify_batch = NeutronNovaZkSNARK.verify_batch
+    verify_bytes_batch = NeutronNovaZkSNARK.verify_bytes_batch
+    proof_to_bytes = NeutronNovaZkSNARK.proof_to_bytes
+    proof_from_bytes = NeutronNovaZkSNARK.proof_from_bytes
+    close = NeutronNovaZkSNARK.close
+    __del__ = NeutronNovaZkSNARK.__del__

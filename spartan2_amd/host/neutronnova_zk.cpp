@@ -98,6 +98,10 @@ struct NNZkKey {
   NNLayout layout;  // of a proof under this key (proof_layout.hpp)
   size_t nb = 0, nx = 0, ny = 0, num_steps = 0, num_vars = 0;
   uint8_t vk_digest[32];
+  // a key loaded from its bytes (nn_key_from_bytes): a verifier's holds row-only shapes and is refused by every prover entry point; both keep the width-32
+  // key's generators as the bytes gave them (vc_gens: 32 bases + h) and are refused by the writers
+  bool verifier_only = false, from_bytes = false;
+  std::vector<aff_t> vc_gens;
   // verify(): eq tables and the three M * T_y products of the matrix evaluations, allocated on first use
   mutable sp_table *v_Tx = nullptr, *v_Ty = nullptr, *v_mv[3] = {nullptr, nullptr, nullptr};
   // r_b, r_x and r_y are fields of the proof, so the commitment fold and the matrix evaluations can start before the transcript has been replayed:
@@ -250,6 +254,305 @@ static NNZkKey* nn_setup(sp_ctx* ctx, const R1CSIntView& Rs, const R1CSIntView& 
     throw;
   }
   return pk;
+}
+
+// ---- NeutronNovaVerifierKey / NeutronNovaProverKey (src/neutronnova_zk.rs:1276-1303) to and from their bincode bytes -------------------------------------
+// Derived field order, little-endian, fixint:
+//   verifier: ck, vk_ee, S_step, S_core, vc_shape, vc_shape_regular, vc_ck, vc_vk                        (`digest` is #[serde(skip)])
+//   prover:   ck, S_step, S_core, vk_digest (32 raw bytes, no length), vc_shape, vc_shape_regular, vc_ck
+// For Hyrax a verifier key serialises as its commitment key does (vk_ee as ck, vc_vk as vc_ck). The shapes are the derived Serialize of SplitR1CSShape
+// (sp_wire_shape(.., 0)); the verifier-circuit shapes are vcirc::Shape::write_bincode.
+enum : unsigned { SS_PK_TRUST_DIGEST = 1u << 16 };  // the flag of ss_prover_from_bytes (spartan_snark.cpp), with its meaning: take the stored digest as it is
+static double nn_now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+// A bounds-checked walk over key bytes for the digest: it reads lengths and skips arrays, and converts or checks no element.
+struct NNKeyWalk {
+  const uint8_t *p, *end;
+  size_t left() const { return (size_t)(end - p); }
+  uint64_t u64() {
+    if (left() < 8) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "wire: unexpected end of input");
+    uint64_t v;
+    memcpy(&v, p, 8);
+    p += 8;
+    return v;
+  }
+  const uint8_t* skip(uint64_t count, size_t elem) {  // count elements of elem bytes
+    if (elem && count > left() / elem) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "wire: length prefix exceeds the input");
+    const uint8_t* at = p;
+    p += (size_t)count * elem;
+    return at;
+  }
+  void hyrax_key() {  // num_cols, Vec<Affine>, GE
+    u64();
+    skip(u64(), 64);
+    skip(96, 1);
+  }
+  void matrix_vecs(const uint8_t* at[3], uint64_t head[4]) {  // SparseMatrix { data, indices, indptr, cols }: where the three arrays lie, and the lengths + cols
+    head[0] = u64(), at[0] = skip(head[0], 32);
+    head[1] = u64(), at[1] = skip(head[1], 8);
+    head[2] = u64(), at[2] = skip(head[2], 8);
+    head[3] = u64();
+  }
+};
+
+// DigestHelperTrait::digest of NeutronNovaVerifierKey (SHA-256 over write_bytes, src/neutronnova_zk.rs:1305-1333) from the key's own serde bytes. write_bytes
+// is bincode(ck) || bincode(vk_ee) || S_step.write_bytes() || S_core.write_bytes() || bincode of the last four fields; SplitR1CSShape::write_bytes and
+// SparseMatrix::write_digest_bytes write the sequences of the derived Serialize with the three lengths and cols in front of each matrix (as in
+// sp_vk_digest_from_wire), so the hash streams slices of the input and transcodes no entry array. `prover`: the bytes are a NeutronNovaProverKey - ck stands
+// for vk_ee and vc_ck for vc_vk (each is hashed twice), and the 32 stored digest bytes behind S_core are stepped over (*stored, when asked for).
+static void nn_vk_digest_from_bytes(const uint8_t* bytes, size_t n, bool prover, uint8_t out[32], const uint8_t** stored = nullptr) {
+  struct Sink {
+    sp_wire* w = nullptr;
+    ~Sink() { sp_wire_free(w); }
+  } sink;
+  ck(sp_wire_new(1, &sink.w), "wire sink");
+  auto hash = [&](const void* at, size_t len) { ck(sp_wire_raw(sink.w, (const uint8_t*)at, len), "wire_raw"); };
+  NNKeyWalk r{bytes, bytes + n};
+  r.hyrax_key();
+  if (prover) hash(bytes, (size_t)(r.p - bytes));
+  else r.hyrax_key();
+  hash(bytes, (size_t)(r.p - bytes));
+  for (int s = 0; s < 2; ++s) {  // S_step, S_core
+    hash(r.skip(80, 1), 80);
+    for (int m = 0; m < 3; ++m) {
+      const uint8_t* at[3];
+      uint64_t head[4];
+      r.matrix_vecs(at, head);
+      hash(head, sizeof head);
+      hash(at[0], 32 * (size_t)head[0]);
+      hash(at[1], 8 * (size_t)head[1]);
+      hash(at[2], 8 * (size_t)head[2]);
+    }
+  }
+  if (!prover) {  // vc_shape, vc_shape_regular, vc_ck, vc_vk as they stand
+    hash(r.p, r.left());
+  } else {
+    const uint8_t* dig = r.skip(32, 1);
+    if (stored) *stored = dig;
+    const uint8_t* vc = r.p;
+    const uint8_t* at[3];
+    uint64_t head[4];
+    r.skip(3, 8);  // SplitMultiRoundR1CSShape: num_cons, num_cons_unpadded, num_rounds,
+    for (int v = 0; v < 3; ++v) r.skip(r.u64(), 8);  // three Vec<usize>,
+    r.skip(2, 8);                                    // num_public, width,
+    for (int m = 0; m < 3; ++m) r.matrix_vecs(at, head);
+    r.skip(3, 8);  // R1CSShape: num_cons, num_vars, num_io
+    for (int m = 0; m < 3; ++m) r.matrix_vecs(at, head);
+    hash(vc, (size_t)(r.p - vc));
+    const uint8_t* key = r.p;
+    r.hyrax_key();
+    if (r.left()) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "wire: trailing bytes");
+    hash(key, (size_t)(r.p - key));  // vc_ck,
+    hash(key, (size_t)(r.p - key));  // and again for vc_vk
+  }
+  ck(sp_wire_digest(sink.w, out), "vk digest");
+}
+
+// Writing: setup keeps neither circuit (its time and memory stay what they were), so the caller hands both again; they are padded and equalized as nn_setup
+// does, and the bytes are returned only if they hash to the key's digest - other circuits than those the key was set up from are refused.
+static void nn_refuse_loaded(const NNZkKey& pk, const char* who) {
+  if (pk.from_bytes) throw Error(SP_ERR_INVALID_INPUT_LENGTH, std::string(who) + ": a key loaded from its bytes (keep those)");
+}
+static std::vector<uint8_t> nn_key_to_bytes(const NNZkKey& pk, const R1CSIntView& Rs, const R1CSIntView& Rc, bool prover) {
+  const char* who = prover ? "pk_to_bytes" : "vk_to_bytes";
+  nn_refuse_loaded(pk, who);
+  PaddedShape Ps = pad_shape(Rs), Pc = pad_shape(Rc);
+  equalize(Ps, Pc);
+  sp_wire* w = nullptr;
+  ck(sp_wire_new(0, &w), "wire_new");
+  std::unique_ptr<sp_wire, void (*)(sp_wire*)> guard(w, sp_wire_free);
+  const uint64_t *g = u64p(&pk.gens[0].x), *h = u64p(&pk.gens[DEFAULT_COMMITMENT_WIDTH].x), *vh = u64p(&pk.gens[32].x);
+  ck(sp_wire_hyrax_key(w, g, DEFAULT_COMMITMENT_WIDTH, h), "wire ck");
+  if (!prover) ck(sp_wire_hyrax_key(w, g, DEFAULT_COMMITMENT_WIDTH, h), "wire vk_ee");
+  sp_csr cs[3];
+  padded_csr(Ps, cs);
+  ck(sp_wire_shape(w, &Ps.dims, &cs[0], &cs[1], &cs[2], 0), "wire S_step");
+  padded_csr(Pc, cs);
+  ck(sp_wire_shape(w, &Pc.dims, &cs[0], &cs[1], &cs[2], 0), "wire S_core");
+  if (prover) ck(sp_wire_raw(w, pk.vk_digest, 32), "wire vk_digest");
+  pk.vc.write_bincode(w, false);
+  pk.vc.write_bincode(w, true);
+  ck(sp_wire_hyrax_key(w, g, 32, vh), "wire vc_ck");
+  if (!prover) ck(sp_wire_hyrax_key(w, g, 32, vh), "wire vc_vk");
+  std::vector<uint8_t> out(sp_wire_len(w));
+  ck(sp_wire_bytes(w, out.data(), out.size()), "wire_bytes");
+  uint8_t dig[32];
+  nn_vk_digest_from_bytes(out.data(), out.size(), prover, dig);
+  if (memcmp(dig, pk.vk_digest, 32) != 0)
+    throw Error(SP_ERR_INVALID_INPUT_LENGTH, std::string(who) + ": the circuits are not those this key was set up from (digest mismatch)");
+  return out;
+}
+// the length of that stream from the circuits' sizes alone (the sizing pass of the two-pass protocol)
+static size_t nn_key_bytes_len(const NNZkKey& pk, const R1CSIntView& Rs, const R1CSIntView& Rc, bool prover) {
+  nn_refuse_loaded(pk, prover ? "pk_to_bytes" : "vk_to_bytes");
+  sp_wire* w = nullptr;
+  ck(sp_wire_new(0, &w), "wire_new");
+  std::unique_ptr<sp_wire, void (*)(sp_wire*)> guard(w, sp_wire_free);
+  pk.vc.write_bincode(w, false);
+  pk.vc.write_bincode(w, true);
+  const size_t rows = std::max(next_pow2(Rs.num_cons), next_pow2(Rc.num_cons)), keys = prover ? 1 : 2;
+  size_t n = keys * (16 + 64 * DEFAULT_COMMITMENT_WIDTH + 96) + keys * (16 + 64 * 32 + 96) + sp_wire_len(w) + (prover ? 32 : 0);
+  for (const R1CSIntView* R : {&Rs, &Rc}) {
+    n += 80;
+    for (int m = 0; m < 3; ++m) n += 8 + 40 * (size_t)R->m[m].indptr[R->num_cons] + 8 + 8 + 8 * (rows + 1) + 8;
+  }
+  return n;
+}
+
+// Reading: ONE loader behind both keys, as key_from_bytes is for Spartan's. ck through sp_unwire_hyrax_key (DEFAULT_COMMITMENT_WIDTH wide); a verifier's
+// vk_ee must be ck byte for byte; S_step and S_core through sp_shape_from_wire, twice on the one cursor - row-only for a verifier (verify and verify_batch
+// read the shapes through sp_shape_matrix_evals_batched alone), full for a prover, the decode form by `flags` = SP_SHAPE_WIRE_* under the exclusions of the
+// Spartan loaders; a prover's stored digest; the two verifier-circuit shapes, which are a function of (nb, nx, ny, width): they are rebuilt from
+// nb = ceil(log2 num_steps) and S_step's nx and ny and compared byte for byte, never parsed into matrices - so one key serves every step count with the same
+// nb, as the reference's does (it fixes num_rounds_b alone); vc_ck (32 wide; a verifier's vc_vk equal to it), whose generators the key keeps as the bytes
+// give them; no trailing bytes. The checks are the post-conditions of SplitR1CSShape::equalize and the refusals of nn_setup. The digest is hashed from the
+// bytes on a helper thread under the device work; a prover compares it with the stored one unless SS_PK_TRUST_DIGEST takes that as the reference's
+// Deserialize does. Every refusal frees what the load had allocated (the key's destructor).
+// which form of the row-only / full shapes a load without a forcing flag takes: measured at config 3's shapes (profiles/nn_keys.md) by the rule of
+// profiles/verifier_key.md - the device form only if its median lies below the host form's minimum
+static constexpr bool NN_VK_DEVICE_DEFAULT = true;
+static constexpr bool NN_PK_FULL_DEVICE_DEFAULT = true;
+// host wall-clock of the calling thread's last load, ms (nnz_key_stages): ck (and vk_ee) read, S_step, S_core, the verifier-circuit shapes rebuilt and
+// compared + vc_ck read, the two sp_ck_create, the digest on its helper thread, the wait for it behind everything else, the whole call
+static thread_local double g_nn_key_stage_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+
+static NNZkKey* nn_key_from_bytes(sp_ctx* ctx, const uint8_t* bytes, size_t n, size_t num_steps, unsigned flags, bool prover) {
+  const std::string who_s = prover ? "nnz_prover_from_bytes" : "nnz_verifier_from_bytes";
+  auto refuse = [&](const std::string& what) -> Error { return Error(SP_ERR_INVALID_INPUT_LENGTH, who_s + ": " + what); };
+  for (double& x : g_nn_key_stage_ms) x = 0;
+  const double t_start = nn_now_ms();
+  if (!ctx || !bytes || n == 0) throw refuse("null context, null bytes or no bytes");
+  if (num_steps < 2) throw refuse("num_steps: at least two step circuits (the verifier circuit has no NIFS round to take its claim from)");
+  bool trust_digest = false;
+  if (!prover) {
+    if (flags & (SP_SHAPE_WIRE_FULL | SP_SHAPE_WIRE_FULL_DEVICE)) throw refuse("a verifier's key holds the row-only shapes");
+    if (!(flags & (SP_SHAPE_WIRE_DEVICE | SP_SHAPE_WIRE_HOST))) flags |= NN_VK_DEVICE_DEFAULT ? SP_SHAPE_WIRE_DEVICE : SP_SHAPE_WIRE_HOST;
+  } else {
+    trust_digest = flags & SS_PK_TRUST_DIGEST;
+    flags &= ~(unsigned)SS_PK_TRUST_DIGEST;
+    if (flags & (SP_SHAPE_WIRE_DEVICE | SP_SHAPE_WIRE_HOST)) throw refuse("a prover's key holds the full shapes (SP_SHAPE_WIRE_FULL_DEVICE or SP_SHAPE_WIRE_FULL)");
+    if (!(flags & (SP_SHAPE_WIRE_FULL_DEVICE | SP_SHAPE_WIRE_FULL))) flags |= NN_PK_FULL_DEVICE_DEFAULT ? SP_SHAPE_WIRE_FULL_DEVICE : SP_SHAPE_WIRE_FULL;
+  }
+  auto pk = std::make_unique<NNZkKey>();
+  pk->ctx = ctx;
+  pk->num_steps = num_steps;
+  pk->verifier_only = !prover;
+  pk->from_bytes = true;
+  ck(sp_ctx_bind_thread(ctx), "device");
+  sp_unwire* r = nullptr;
+  ck(sp_unwire_new(bytes, n, &r), "unwire_new");
+  std::unique_ptr<sp_unwire, void (*)(sp_unwire*)> guard(r, sp_unwire_free);
+  auto at = [&] { return n - sp_unwire_left(r); };  // the cursor's offset
+  auto named = [&](int rc, const char* field) {
+    if (rc != SP_OK) throw Error(rc, who_s + ": " + field + ": " + sp_last_error());
+  };
+  auto read_key = [&](std::vector<aff_t>& gens, size_t want_cols, const char* field) {
+    size_t nc = 0;
+    named(sp_unwire_hyrax_key(r, nullptr, 0, &nc, nullptr), field);
+    if (nc != want_cols) throw refuse(std::string(field) + ": num_cols is " + std::to_string(nc) + ", this build's is " + std::to_string(want_cols));
+    gens.resize(nc + 1);
+    named(sp_unwire_hyrax_key(r, u64p(&gens[0].x), nc, &nc, u64p(&gens[nc].x)), field);
+  };
+  auto same_key_again = [&](size_t from, const char* field, const char* as) {  // the next `len` bytes are the key at `from` once more
+    const size_t len = at() - from;
+    if (sp_unwire_left(r) < len) throw refuse(std::string(field) + ": wire: unexpected end of input");
+    if (memcmp(bytes + from, bytes + from + len, len) != 0) throw refuse(std::string(field) + " is not " + as + " (for Hyrax the two are the same generators)");
+    std::vector<uint64_t> over(len / 8);
+    named(sp_unwire_u64s(r, over.size(), over.data()), field);
+  };
+  read_key(pk->gens, DEFAULT_COMMITMENT_WIDTH, "ck");
+  if (!prover) same_key_again(0, "vk_ee", "ck");
+  const double t_keys = nn_now_ms();
+  // the digest needs the bytes alone
+  double digest_ms = 0;
+  const uint8_t* stored_digest = nullptr;
+  std::future<void> digest = std::async(trust_digest ? std::launch::deferred : std::launch::async, [&] {
+    if (trust_digest) return;
+    const double t0 = nn_now_ms();
+    nn_vk_digest_from_bytes(bytes, n, prover, pk->vk_digest);
+    digest_ms = nn_now_ms() - t0;
+  });
+  struct Join {
+    std::future<void>& f;
+    ~Join() {
+      if (f.valid()) f.wait();
+    }
+  } join{digest};
+  named(sp_shape_from_wire(ctx, r, flags, &pk->dims, &pk->S_step), "S_step");
+  const double t_step = nn_now_ms();
+  named(sp_shape_from_wire(ctx, r, flags, &pk->dims_core, &pk->S_core), "S_core");
+  const double t_core = nn_now_ms();
+  if (prover) {
+    if (sp_unwire_left(r) < 32) throw refuse("vk_digest: wire: unexpected end of input");
+    stored_digest = bytes + at();
+    uint64_t over[4];
+    named(sp_unwire_u64s(r, 4, over), "vk_digest");
+  }
+  const sp_dims &d = pk->dims, &dc = pk->dims_core;
+  const size_t nv = d.num_shared + d.num_precommitted + d.num_rest, nvc = dc.num_shared + dc.num_precommitted + dc.num_rest;
+  // SplitR1CSShape::new pads to powers of two (the sum-checks and the layout count rounds from them) ...
+  if (next_pow2(d.num_cons) != d.num_cons || next_pow2(nv) != nv) throw refuse("S_step: num_cons or the padded variable total is no power of two");
+  // ... and equalize (src/r1cs/mod.rs:913-971) leaves both shapes with the larger constraint count and the larger variable total
+  if (d.num_cons != dc.num_cons) throw refuse("S_core: num_cons is " + std::to_string(dc.num_cons) + ", S_step's is " + std::to_string(d.num_cons) + " (the shapes are not equalized)");
+  if (nv != nvc) throw refuse("S_core: the padded variable total is " + std::to_string(nvc) + ", S_step's is " + std::to_string(nv) + " (the shapes are not equalized)");
+  // the refusals of nn_setup
+  if (d.num_shared != dc.num_shared) throw refuse("S_core: num_shared: step and core circuits with different padded shared segments (one shared commitment serves both)");
+  if (d.num_challenges || dc.num_challenges) throw refuse(std::string(d.num_challenges ? "S_step" : "S_core") + ": num_challenges: step / core circuits with verifier challenges are not driven by this layer");
+  if (d.num_rest_unpadded && d.num_shared + d.num_precommitted)
+    throw refuse("S_step: num_rest_unpadded: step circuits with rest variables beside shared / precommitted ones (the reference's fold drops the rest segment)");
+  pk->num_vars = nv;
+  pk->nb = log2_ceil(next_pow2(num_steps));
+  pk->nx = log2_ceil(d.num_cons);
+  pk->ny = log2_ceil(nv) + 1;
+  pk->vc = vcirc::Shape::from_circuit(vcirc::Circuit(pk->nb, pk->nx, pk->ny, 32));
+  {
+    sp_wire* w = nullptr;
+    ck(sp_wire_new(0, &w), "wire_new");
+    std::unique_ptr<sp_wire, void (*)(sp_wire*)> wguard(w, sp_wire_free);
+    size_t from = 0;
+    for (int regular = 0; regular < 2; ++regular) {
+      const char* field = regular ? "vc_shape_regular" : "vc_shape";
+      pk->vc.write_bincode(w, regular != 0);
+      std::vector<uint8_t> want(sp_wire_len(w));
+      ck(sp_wire_bytes(w, want.data(), want.size()), "wire_bytes");
+      const size_t len = want.size() - from;
+      if (sp_unwire_left(r) < len) throw refuse(std::string(field) + ": wire: unexpected end of input");
+      if (memcmp(bytes + at(), want.data() + from, len) != 0)
+        throw refuse(std::string(field) + ": not the verifier circuit of nb = " + std::to_string(pk->nb) + " (num_steps = " + std::to_string(num_steps) + "), nx = " +
+                     std::to_string(pk->nx) + ", ny = " + std::to_string(pk->ny) + ", width 32");
+      std::vector<uint64_t> over(len / 8);
+      named(sp_unwire_u64s(r, over.size(), over.data()), field);
+      from = want.size();
+    }
+  }
+  const size_t vc_ck_at = at();
+  read_key(pk->vc_gens, 32, "vc_ck");
+  if (!prover) same_key_again(vc_ck_at, "vc_vk", "vc_ck");
+  named(sp_unwire_done(r), prover ? "behind vc_ck" : "behind vc_vk");
+  pk->layout = NNLayout(pk->dims, pk->dims_core, num_steps, pk->vc);
+  const double t_vc = nn_now_ms();
+  ck(sp_ck_create(ctx, u64p(&pk->gens[0].x), DEFAULT_COMMITMENT_WIDTH, u64p(&pk->gens[DEFAULT_COMMITMENT_WIDTH].x), &pk->ck), "ck_create");
+  ck(sp_ck_create(ctx, u64p(&pk->vc_gens[0].x), 32, u64p(&pk->vc_gens[32].x), &pk->vc_ck), "vc_ck_create");
+  const double t_ck = nn_now_ms();
+  try {
+    digest.get();
+  } catch (const Error& e) {
+    throw Error(e.code, who_s + ": the digest pass could not walk the bytes: " + e.what());
+  }
+  if (trust_digest) memcpy(pk->vk_digest, stored_digest, 32);
+  else if (prover && memcmp(pk->vk_digest, stored_digest, 32) != 0)
+    throw refuse("vk_digest: the stored digest is not the digest of the key's bytes (a prover under it makes proofs no verifier accepts)");
+  const double t_end = nn_now_ms();
+  const double st[8] = {t_keys - t_start, t_step - t_keys, t_core - t_step, t_vc - t_core, t_ck - t_vc, digest_ms, t_end - t_ck, t_end - t_start};
+  std::copy(st, st + 8, g_nn_key_stage_ms);
+  return pk.release();
+}
+// the prover entry points take the key through this: a verifier's key holds row-only shapes
+static NNZkKey& nn_prover_key(void* pk, const char* who) {
+  auto* k = (NNZkKey*)pk;
+  if (k && k->verifier_only)
+    throw Error(SP_ERR_INVALID_INPUT_LENGTH, std::string(who) + ": verifier-only key (loaded by nnz_verifier_from_bytes; proving takes the key of nnz_setup or nnz_prover_from_bytes)");
+  return *k;
 }
 
 // The witness of one circuit as a device table [shared | precommitted | rest] at the padded offsets (bellpepper/r1cs.rs:306-409): the machine words cross the bus
@@ -2440,6 +2743,93 @@ int nnz_setup(sp_ctx* ctx, size_t num_steps, size_t num_cons, size_t num_shared,
   }
 }
 void nnz_pk_free(void* pk) { delete (NNZkKey*)pk; }
+// The key's NeutronNovaVerifierKey / NeutronNovaProverKey as bincode bytes (see nn_key_to_bytes): the circuit arguments of nnz_setup again, ss_vk_to_bytes's
+// protocol. Two passes: out == NULL returns the length, otherwise the bytes are written (cap must hold them) and the length returned; < 0 = error
+// (ss_last_error), among them other circuits than the key's and a key that was itself loaded from bytes ("keep those").
+static long nnz_key_to_bytes(const char* who, bool prover, void* pk, const R1CSIntView& Rs, const R1CSIntView& Rc, uint8_t* out, size_t cap) {
+  try {
+    if (!pk) throw Error(SP_ERR_INVALID_INPUT_LENGTH, std::string(who) + ": null key");
+    const NNZkKey& key = *(NNZkKey*)pk;
+    nn_refuse_loaded(key, who);
+    if (!out) return (long)nn_key_bytes_len(key, Rs, Rc, prover);
+    const std::vector<uint8_t> b = nn_key_to_bytes(key, Rs, Rc, prover);
+    if (cap < b.size()) throw Error(SP_ERR_INVALID_INPUT_LENGTH, std::string(who) + ": buffer too small");
+    memcpy(out, b.data(), b.size());
+    return (long)b.size();
+  } catch (...) {
+    return catch_all_nn();
+  }
+}
+long nnz_vk_to_bytes(void* pk, size_t num_cons, size_t num_shared, size_t num_precommitted, size_t num_rest, size_t num_public, size_t num_challenges, const int64_t* Ad,
+                     const uint32_t* Ai, const uint64_t* Ap, const int64_t* Bd, const uint32_t* Bi, const uint64_t* Bp, const int64_t* Cd, const uint32_t* Ci,
+                     const uint64_t* Cp, size_t c_num_cons, size_t c_num_shared, size_t c_num_precommitted, size_t c_num_rest, size_t c_num_public,
+                     size_t c_num_challenges, const int64_t* cAd, const uint32_t* cAi, const uint64_t* cAp, const int64_t* cBd, const uint32_t* cBi, const uint64_t* cBp,
+                     const int64_t* cCd, const uint32_t* cCi, const uint64_t* cCp, uint8_t* out, size_t cap) {
+  return nnz_key_to_bytes("nnz_vk_to_bytes", false, pk, make_view(num_cons, num_shared, num_precommitted, num_rest, num_public, num_challenges, Ad, Ai, Ap, Bd, Bi, Bp, Cd, Ci, Cp),
+                          make_view(c_num_cons, c_num_shared, c_num_precommitted, c_num_rest, c_num_public, c_num_challenges, cAd, cAi, cAp, cBd, cBi, cBp, cCd, cCi, cCp), out,
+                          cap);
+}
+long nnz_pk_to_bytes(void* pk, size_t num_cons, size_t num_shared, size_t num_precommitted, size_t num_rest, size_t num_public, size_t num_challenges, const int64_t* Ad,
+                     const uint32_t* Ai, const uint64_t* Ap, const int64_t* Bd, const uint32_t* Bi, const uint64_t* Bp, const int64_t* Cd, const uint32_t* Ci,
+                     const uint64_t* Cp, size_t c_num_cons, size_t c_num_shared, size_t c_num_precommitted, size_t c_num_rest, size_t c_num_public,
+                     size_t c_num_challenges, const int64_t* cAd, const uint32_t* cAi, const uint64_t* cAp, const int64_t* cBd, const uint32_t* cBi, const uint64_t* cBp,
+                     const int64_t* cCd, const uint32_t* cCi, const uint64_t* cCp, uint8_t* out, size_t cap) {
+  return nnz_key_to_bytes("nnz_pk_to_bytes", true, pk, make_view(num_cons, num_shared, num_precommitted, num_rest, num_public, num_challenges, Ad, Ai, Ap, Bd, Bi, Bp, Cd, Ci, Cp),
+                          make_view(c_num_cons, c_num_shared, c_num_precommitted, c_num_rest, c_num_public, c_num_challenges, cAd, cAi, cAp, cBd, cBi, cBp, cCd, cCi, cCp), out,
+                          cap);
+}
+// A verifier's key from the bytes nnz_vk_to_bytes writes (see nn_key_from_bytes): no circuit, no setup. The key does not hold the step count (the reference
+// fixes num_rounds_b alone), so the caller states it. flags: 0, or SP_SHAPE_WIRE_DEVICE / SP_SHAPE_WIRE_HOST to force a decode form, and SP_SHAPE_WIRE_TIMED.
+// The verify family, nnz_pk_info, nnz_proof_words and nnz_proof_to_bytes / _from_bytes take the key; every prover entry point refuses it ("verifier-only
+// key"); nnz_pk_free ends it.
+int nnz_verifier_from_bytes(sp_ctx* ctx, const uint8_t* bytes, size_t n, size_t num_steps, unsigned flags, void** out_vk) {
+  try {
+    if (!out_vk) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "nnz_verifier_from_bytes: null out");
+    *out_vk = nullptr;
+    *out_vk = nn_key_from_bytes(ctx, bytes, n, num_steps, flags, false);
+    return 0;
+  } catch (...) {
+    return catch_all_nn();
+  }
+}
+// A prover's key from the bytes nnz_pk_to_bytes writes. flags: SP_SHAPE_WIRE_FULL_DEVICE / SP_SHAPE_WIRE_FULL force the device / host form of the two full
+// shapes (neither: nnz_prover_full_device_default), SP_SHAPE_WIRE_TIMED, SS_PK_TRUST_DIGEST (1 << 16) takes the stored digest unhashed. Every entry point
+// takes the key as it takes nnz_setup's, except nnz_vk_to_bytes / nnz_pk_to_bytes.
+int nnz_prover_from_bytes(sp_ctx* ctx, const uint8_t* bytes, size_t n, size_t num_steps, unsigned flags, void** out_pk) {
+  try {
+    if (!out_pk) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "nnz_prover_from_bytes: null out");
+    *out_pk = nullptr;
+    *out_pk = nn_key_from_bytes(ctx, bytes, n, num_steps, flags, true);
+    return 0;
+  } catch (...) {
+    return catch_all_nn();
+  }
+}
+// ms of the calling thread's last nnz_verifier_from_bytes / nnz_prover_from_bytes: ck (and vk_ee) read, S_step, S_core, the verifier-circuit shapes compared
+// and vc_ck read, the two sp_ck_create, the digest (helper thread; 0 when trusted), the wait for it behind the rest, the whole call
+// The verifier key's digest from key bytes alone (nn_vk_digest_from_bytes; host code, no context): prover != 0 = the bytes are a prover's key, whose stored
+// digest is stepped over. No element is converted or checked - a key that fails its load never shows its digest.
+int nnz_vk_digest_from_bytes(const uint8_t* bytes, size_t n, int prover, uint8_t out[32]) {
+  try {
+    if (!bytes || !n || !out) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "nnz_vk_digest_from_bytes: null argument");
+    nn_vk_digest_from_bytes(bytes, n, prover != 0, out);
+    return 0;
+  } catch (...) {
+    return catch_all_nn();
+  }
+}
+void nnz_key_stages(double out[8]) { memcpy(out, g_nn_key_stage_ms, sizeof g_nn_key_stage_ms); }
+int nnz_verifier_device_default(void) { return NN_VK_DEVICE_DEFAULT ? 1 : 0; }
+int nnz_prover_full_device_default(void) { return NN_PK_FULL_DEVICE_DEFAULT ? 1 : 0; }
+// the key's shapes, for sp_shape_compare / sp_shape_info (which: 0 = S_step, 1 = S_core); the key keeps owning them
+const sp_shape* nnz_pk_shape(void* pk, int which) { return pk ? (which ? ((NNZkKey*)pk)->S_core : ((NNZkKey*)pk)->S_step) : nullptr; }
+// out: the ten dimensions of S_step, then of S_core, then num_steps, 1 / 0 = verifier-only, 1 / 0 = loaded from bytes
+void nnz_pk_dims(void* pk_, uint64_t out[23]) {
+  auto* pk = (NNZkKey*)pk_;
+  memcpy(out, &pk->dims, sizeof(sp_dims));
+  memcpy(out + 10, &pk->dims_core, sizeof(sp_dims));
+  out[20] = pk->num_steps, out[21] = pk->verifier_only, out[22] = pk->from_bytes;
+}
 // out: nb, nx, ny, vc rounds, vc total vars, vc num_cons, vc num_cons_unpadded, vc num_public; digest = the vk digest (SHA-256 over NeutronNovaVerifierKey::write_bytes)
 void nnz_pk_info(void* pk_, uint64_t out[8], uint8_t digest[32]) {
   auto* pk = (NNZkKey*)pk_;
@@ -2453,7 +2843,7 @@ int nnz_prep_prove_sha256(void* pk, const sp_sha256_plan* plan, const uint8_t* b
                           void** out_ps) {
   try {
     Tape t{tape, tape_blocks};
-    *out_ps = nn_prep_prove_sha256(*(NNZkKey*)pk, plan, blocks, n, is_small != 0, t);
+    *out_ps = nn_prep_prove_sha256(nn_prover_key(pk, "nnz_prep_prove_sha256"), plan, blocks, n, is_small != 0, t);
     if (tape_used) *tape_used = t.pos;
     return 0;
   } catch (...) {
@@ -2464,7 +2854,7 @@ int nnz_prep_prove(void* pk, size_t n, const uint64_t* step_wit, size_t wit_len,
                    int is_small, const uint8_t* tape, size_t tape_blocks, size_t* tape_used, void** out_ps) {
   try {
     Tape t{tape, tape_blocks};
-    *out_ps = nn_prep_prove(*(NNZkKey*)pk, n, step_wit, wit_len, step_pub, npub, core_wit, core_pub, is_small != 0, t);
+    *out_ps = nn_prep_prove(nn_prover_key(pk, "nnz_prep_prove"), n, step_wit, wit_len, step_pub, npub, core_wit, core_pub, is_small != 0, t);
     if (tape_used) *tape_used = t.pos;
     return 0;
   } catch (...) {
@@ -2500,7 +2890,7 @@ int nnz_prep_prove_batch_opts(void* pk, size_t count, const size_t* n, const uin
     if (!pk || !n || !step_wit || !wit_len || !step_pub || !core_wit || !core_pub || !tapes || !tape_blocks || !out_ps)
       throw Error(SP_ERR_INVALID_INPUT_LENGTH, "prep_prove_batch: null argument");
     std::vector<Tape> ts = nnz_batch_tapes(count, tapes, tape_blocks);
-    nnz_batch_out(nn_prep_prove_batch(*(NNZkKey*)pk, count, n, step_wit, wit_len, step_pub, npub, core_wit, core_pub, is_small != 0, ts.data(), flags, phase_ms), ts, tape_used,
+    nnz_batch_out(nn_prep_prove_batch(nn_prover_key(pk, "nnz_prep_prove_batch"), count, n, step_wit, wit_len, step_pub, npub, core_wit, core_pub, is_small != 0, ts.data(), flags, phase_ms), ts, tape_used,
                   out_ps);
     return 0;
   } catch (...) {
@@ -2519,7 +2909,7 @@ int nnz_prep_prove_sha256_batch_opts(void* pk, const sp_sha256_plan* plan, size_
     if (count == 0) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "prep_prove_batch: count must be at least 1");
     if (!pk || !plan || !blocks || !n || !tapes || !tape_blocks || !out_ps) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "prep_prove_batch: null argument");
     std::vector<Tape> ts = nnz_batch_tapes(count, tapes, tape_blocks);
-    nnz_batch_out(nn_prep_prove_sha256_batch(*(NNZkKey*)pk, plan, count, blocks, n, is_small != 0, ts.data(), flags, phase_ms), ts, tape_used, out_ps);
+    nnz_batch_out(nn_prep_prove_sha256_batch(nn_prover_key(pk, "nnz_prep_prove_sha256_batch"), plan, count, blocks, n, is_small != 0, ts.data(), flags, phase_ms), ts, tape_used, out_ps);
     return 0;
   } catch (...) {
     return catch_all_nn();
@@ -2538,7 +2928,7 @@ int nnz_prep_is_sat(void* pk, void* ps, sp_sat_report* reports, uint64_t* bad_ro
     if (!ps || !reports) throw Error(SP_ERR_INTERNAL, "is_sat before prep_prove");
     std::vector<uint64_t> bad;
     const char* reason = nullptr;
-    const bool ok = nn_is_sat(*(NNZkKey*)pk, *(NNZkPrep*)ps, reports, &bad, &reason);
+    const bool ok = nn_is_sat(nn_prover_key(pk, "nnz_prep_is_sat"), *(NNZkPrep*)ps, reports, &bad, &reason);
     if (n_bad_rows) *n_bad_rows = bad.size() / 2;
     if (bad_rows) std::copy(bad.begin(), bad.begin() + 2 * std::min(bad.size() / 2, bad_rows_cap), bad_rows);
     if (ok) return 0;
@@ -2561,7 +2951,7 @@ static int nnz_prove_impl(void* pk, void* ps, const uint8_t* tape, size_t tape_b
                           bool reference_order) {
   try {
     Tape t{tape, tape_blocks};
-    ProofBuf pf = nn_prove(*(NNZkKey*)pk, *(NNZkPrep*)ps, t, phase_ms, reference_order);
+    ProofBuf pf = nn_prove(nn_prover_key(pk, reference_order ? "nnz_prove_reference_order" : "nnz_prove"), *(NNZkPrep*)ps, t, phase_ms, reference_order);
     if (pf.words.size() > out_cap) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "proof buffer too small");
     memcpy(out_words, pf.words.data(), pf.words.size() * 8);
     if (tape_used) *tape_used = t.pos;
@@ -2593,7 +2983,7 @@ int nnz_prove_batch_opts(void* pk, void* const* ps, size_t count, const uint8_t*
       if (!tapes[k] || !out_words[k]) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "prove_batch: proof " + std::to_string(k) + ": null tape or output");
       ts.push_back(Tape{tapes[k], tape_blocks[k]});
     }
-    const NNZkKey& key = *(NNZkKey*)pk;
+    const NNZkKey& key = nn_prover_key(pk, "nnz_prove_batch");
     if (key.layout.words() > out_cap) throw Error(SP_ERR_INVALID_INPUT_LENGTH, "proof buffer too small");
     NNBatchPhases ph;
     std::vector<ProofBuf> pf = nn_prove_batch(key, (NNZkPrep* const*)ps, ts.data(), count, flags, &ph);
